@@ -43,7 +43,7 @@ def _bench(args, distributed, tag, nproc=1):
     cmd = [sys.executable]
     if distributed:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
-    cmd += [os.path.join(ROOT, "bench.py")] + args
+    cmd += [os.path.join(ROOT, "bench.py"), "--full"] + args            # the collective's cost and the per-rank checks are --full figures
     out = _run_child(cmd, env, tag)
     line = [l for l in out.splitlines() if l.startswith("{")][-1]
     return json.loads(line)

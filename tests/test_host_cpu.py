@@ -129,6 +129,18 @@ def test_bench_config_shorthand_and_explicit_flags():
     assert (a.shape, a.batch, a.conformers, a.model, a.gpus) == ("esol", 256, 5, "schnet", 1)          # BASELINE configs[1] on one GPU
 
 
+def test_bench_plain_run_times_one_block_and_full_keeps_three():
+    """A plain bench.py run times exactly --steps steps (one block); --full keeps the three blocks it always had; an explicit --blocks wins."""
+    import importlib.util, os
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.blocks, a.full, a.dump_outputs) == (7, 2, 1, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert (a.blocks, a.full, a.dump_outputs) == (3, True, "out")
+    assert bench.parse(["--blocks", "2"]).blocks == 2 and bench.parse(["--full", "--blocks", "1"]).blocks == 1
+
+
 def test_slice_rule_of_the_batched_weight_gradients():
     """ops._late_slices: ~1 400 workgroups per launch of <= 24 jobs, a multiple of 8 per job, never more than the library's default (one per 128
     rows: the workspace and the reducer are sized by it); the forced knob obeys the same cap."""

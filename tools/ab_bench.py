@@ -23,11 +23,11 @@ for o in ovrs:
     subprocess.check_call(["make", "-C", src, "-s", "-j16"] + mk, stderr=subprocess.DEVNULL)
     libs.append((os.path.basename(o.rstrip("/")), os.path.join(tmp, "pkg", "libconan_fgw_hip.so")))
 runner = ("import sys, runpy; sys.path.insert(0, %r)\nfrom conan_fgw_amd import _lib\nif %%r: _lib._SO = %%r\n"
-          "sys.argv = ['bench.py', '--no-cpu-baseline'] + %r\nrunpy.run_path(%r, run_name='__main__')" % (ROOT, extra, os.path.join(ROOT, "bench.py")))
+          "sys.argv = ['bench.py', '--full', '--no-cpu-baseline'] + %r\nrunpy.run_path(%r, run_name='__main__')" % (ROOT, extra, os.path.join(ROOT, "bench.py")))
 w = max(len(t) for t, _ in libs)
 for rnd in range(rounds):
     for tag, so in libs:
-        out = subprocess.run([sys.executable, "-c", runner % (bool(so), so)], capture_output=True, text=True).stdout.strip().splitlines()
+        out = subprocess.run([sys.executable, "-c", runner % (bool(so), so)], capture_output=True, text=True, check=True, timeout=900).stdout.strip().splitlines()
         d = json.loads(out[-1])
         print(tag.ljust(w), "step %.4f ms  eager %.4f ms  forward %s ms" % (d["ms_per_step"], d["eager"]["ms_per_step"], (d.get("forward_only") or {}).get("ms_per_step")), flush=True)
 for t in tmps:
