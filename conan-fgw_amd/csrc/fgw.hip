@@ -69,7 +69,9 @@ __global__ void k_fgw_init(const float *__restrict__ Cs, const float *__restrict
 // MODE 2: the four matrices in LDS; 1: only the coupling (Mr / K) in LDS; 0: everything in the global scratch.  A template parameter,
 // not a runtime flag: a pointer chosen at run time between LDS and global memory compiles to flat_* accesses for every
 // element of the Sinkhorn passes.
-template <int MODE, bool KL, int NW, bool SECOND = false>      // KL: loss_fun = "kl_loss"; SECOND: the pass behind k_fgw_coupling_big (see fgw_small.hip)
+// PPA: solver="PPA" (bregman.py:127-128: tens - eps * log(T) before every Sinkhorn call) — the Sinkhorn kernel matrix is multiplied entrywise by
+// the previous coupling (K_ij = T_ij exp(Mr_ij - ref_j)), and on the exact log-domain pass log(T_ij) is added to Mr (a zero entry is a masked -inf).
+template <int MODE, bool KL, int NW, bool SECOND = false, bool PPA = false>      // KL: loss_fun = "kl_loss"; SECOND: the pass behind k_fgw_coupling_big (see fgw_small.hip)
 __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
     const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb,
     FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw,
@@ -176,6 +178,7 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
 
     // ---- projected gradient loop (bregman.py:119-157)
     int cpt = 0, sk_total = 0;
+    [[maybe_unused]] int ppa_zero = 0;                                  // PPA: a row / column of the kernel matrix vanished (flags bit 2)
     double err = 1.0;
     while (err > (double)prm.inner_tol && cpt < prm.max_iter) {
         // A = C1 @ T ; G = A @ (2 C2)^T on fp64 MFMA ; tens = base - 2*alpha*G ; Mr = -tens/eps
@@ -213,7 +216,11 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
         for (int j = lane; j < N; j += 64) {                              // K = exp(Mr - ref_j), partial column sums
             const double ref = v[j];
             double cs = 0.0;
-            for (int i = wave; i < N; i += NW) { const double k = exp_fast(Mr[i * P + j] - ref); Mr[i * P + j] = k; cs += k; }
+            for (int i = wave; i < N; i += NW) {
+                double k = exp_fast(Mr[i * P + j] - ref);
+                if constexpr (PPA) k *= (double)Tl[i * P + j];              // (Tl: the previous coupling until the T store below)
+                Mr[i * P + j] = k; cs += k;
+            }
             psm[wave * N + j] = cs;
         }
         __syncthreads();
@@ -274,6 +281,14 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
             // ---- exact log-domain Sinkhorn (sinkhorn.py:393-433), restarted from u = v = 0 on a re-formed Mr
             __syncthreads();
             form_mr();
+            if constexpr (PPA) {
+                __syncthreads();
+                for (int t = tid; t < NN; t += NT) {
+                    const int i = t / N, j = t - i * N;
+                    const float tp = Tl[i * P + j];
+                    Mr[i * P + j] = tp > 0.f ? Mr[i * P + j] + log((double)tp) : -__builtin_inf();
+                }
+            }
             // (a node without mass has log-weight -inf and its potential is -inf after its first update; it starts there, so that it never
             // enters the other side's first log-sum-exp: the rectangular problem fgw.py embeds has no such node at all)
             for (int i = tid; i < N; i += NT) { u[i] = loga[i] < -1.0e300 ? loga[i] : 0.0; v[i] = logb[i] < -1.0e300 ? logb[i] : 0.0; }     // sinkhorn.py:393-394
@@ -297,6 +312,9 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
                     double sm = 0.0;
 #pragma unroll
                     for (int w = 0; w < NW; ++w) sm += psm[w * N + j] * exp_lse(pm[w * N + j] - M);
+                    if constexpr (PPA) {      // a column that is -inf throughout: massless (stays -inf), or the reference's NaN case
+                        if (!(sm > 0.0)) { v[j] = logb[j] < -1.0e300 ? logb[j] : __builtin_inf(); if (logb[j] >= -1.0e300) ppa_zero = 1; continue; }
+                    }
                     v[j] = logb[j] - (log_acc(sm) + M);
                 }
                 __syncthreads();
@@ -316,6 +334,9 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
                     double sm = 0.0;
 #pragma unroll
                     for (int w = 0; w < NW; ++w) sm += psm[w * N + i] * exp_lse(pm[w * N + i] - M);
+                    if constexpr (PPA) {
+                        if (!(sm > 0.0)) { u[i] = loga[i] < -1.0e300 ? loga[i] : __builtin_inf(); if (loga[i] >= -1.0e300) ppa_zero = 1; continue; }
+                    }
                     u[i] = loga[i] - (log_acc(sm) + M);
                 }
                 __syncthreads();
@@ -363,6 +384,7 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
     }
     __syncthreads();
     for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; Tg[t] = Tl[i * P + j]; }
+    if constexpr (PPA) { if (__syncthreads_or(ppa_zero) && tid == 0) atomicOr(&info[b * 4 + 3], 4); }
     if (tid == 0) { atomicAdd(&info[b * 4 + 1], cpt); atomicAdd(&info[b * 4 + 2], sk_total); }
     FGW_PROF(8);      // T -> global
     // ---- contributions to the barycenter update (summed over s by k_fgw_update_parts)
@@ -1027,10 +1049,52 @@ long long conan_fgw_workspace_bytes(int B, int K, int N, int d) {
     return (long long)bytes;
 }
 
+// solver = 1 (PPA) / 2 (BAPG): the outer loop of fgw_fwd_impl with the general initialisation and update kernels and the solver's coupling
+// kernel — PPA: k_fgw_coupling<MODE, KL, GEN_NW, false, true>; BAPG: k_fgw_coupling_bapg (fgw_bapg.hip).  Dense structure only (the caller
+// expands ragged input first); no fast / big / register-resident path, no padded-node merge (flags bit 1 stays 0).
+static int fgw_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
+                          const float *init_Y, FgwDims D, const conan_fgw_params &prm, float *Y, float *C, float *T, float *T_iter, int *info,
+                          float *errs, double *Cw, double *Yw, int *active, char *sc_c, fgw_part_t *Ypart, fgw_part_t *Cpart, int solver,
+                          hipStream_t s) {
+    const int B = D.B, K = D.K, N = D.N;
+    const size_t NN = (size_t)N * N, NP = (size_t)N * D.P;
+    const bool kl = prm.loss_fun != 0;
+    const FgwAdj none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    k_fgw_init<<<B, 256, 0, s>>>(Cs, init_C, init_Y, D, prm.max_iter, Cw, Yw, active, info, errs, Y, C, none);
+    const size_t lc = coupling_lds(N), vec_c = (size_t)((6 + 2 * GEN_NW) * N + 16) * 8, mr_bytes = NP * 8;
+    const int mode = lc <= LDS_LIMIT ? 2 : (vec_c + mr_bytes <= LDS_LIMIT ? 1 : 0);
+    const size_t lds_bytes = mode == 2 ? lc : vec_c + (mode == 1 ? mr_bytes : 0);
+    for (int outer = 0; outer < prm.max_iter; ++outer) {
+        const int y_zero = (outer == 0 && !init_Y) ? 1 : 0;
+        if (solver == 2) {
+            conan_fgw_bapg_coupling(Ys, Cs, ps, p, D, prm, outer, y_zero, Cw, Yw, active, T, info, sc_c, coupling_scratch_stride(NP), Ypart, Cpart, s);
+        } else {
+#define CONAN_PPA(M, KLV)                                                                                                           \
+    do {                                                                                                                            \
+        if (lds_bytes > 64 * 1024)                                                                                                  \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling<M, KLV, GEN_NW, false, true>),                 \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                                  \
+        k_fgw_coupling<M, KLV, GEN_NW, false, true><<<B * K, 64 * GEN_NW, lds_bytes, s>>>(Ys, Cs, ps, p, D, prm, outer, y_zero, Cw, Yw, active, \
+                                                                                          T, info, sc_c, Ypart, Cpart, nullptr, none);  \
+    } while (0)
+            if (mode == 2) { if (kl) CONAN_PPA(2, true); else CONAN_PPA(2, false); }
+            else if (mode == 1) { if (kl) CONAN_PPA(1, true); else CONAN_PPA(1, false); }
+            else { if (kl) CONAN_PPA(0, true); else CONAN_PPA(0, false); }
+#undef CONAN_PPA
+        }
+        if (T_iter)
+            (void)hipMemcpyAsync(T_iter + (size_t)outer * B * K * NN, T, (size_t)B * K * NN * sizeof(float), hipMemcpyDeviceToDevice, s);
+        conan_fgw_small_update(p, lambdas, D, prm, outer, Ypart, Cpart, Cw, Yw, active, info, errs, Y, C, nullptr, nullptr, nullptr, s);
+    }
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
 static int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
                         const float *init_C, const float *init_Y, int B, int K, int N, int d,
                         const conan_fgw_params *params_in, float *Y, float *C, float *T, float *T_iter, int *info,
-                        float *errs, void *workspace, void *stream, FgwAdj adj) {
+                        float *errs, void *workspace, void *stream, FgwAdj adj, int solver = 0) {
+    if (solver < 0 || solver > 2) return CONAN_E_BADARG;
     if (!Ys || (!Cs && !adj.rowptr) || !params_in || !Y || !C || !T || !info || !errs || !workspace || B <= 0 || K <= 0 || N <= 0 || d <= 0)
         return CONAN_E_BADARG;
     conan_fgw_params params_v = *params_in;
@@ -1061,13 +1125,16 @@ static int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const
         // load stage are the square-loss ones of the model path (k_fgw_coupling_fast for N <= 64, k_fgw_coupling_big above); any other shape /
         // loss expands the graphs into the scratch once and continues on the dense path.
         adj.dense = reinterpret_cast<float *>(static_cast<char *>(workspace) + conan_fgw_workspace_bytes(B, K, N, d));
-        const bool ragged_ok = !kl && (small ? conan_fgw_fast_supported(N, d, 1) : big_lds(N, true) <= LDS_LIMIT);
+        const bool ragged_ok = solver == 0 && !kl && (small ? conan_fgw_fast_supported(N, d, 1) : big_lds(N, true) <= LDS_LIMIT);
         if (!ragged_ok) {
             k_adj_dense<<<B * K, 256, 0, s>>>(adj, N);
             Cs = adj.dense;
             adj.rowptr = nullptr;
         }
     }
+
+    if (solver != 0) return fgw_fwd_solver(Ys, Cs, ps, p, lambdas, init_C, init_Y, D, *params, Y, C, T, T_iter, info, errs, Cw, Yw, active, sc_c,
+                                           Ypart, Cpart, solver, s);
 
     // size-ordered dealing of the coupling workgroups (speed only): k_fgw_coupling_fast and k_fgw_coupling_big
     if (adj.rowptr && !kl && (B & 7) == 0 && B <= 4096 && (small || (CONAN_FGW_BIG_ORDER && big_lds(N, true) <= LDS_LIMIT))) adj.order = order_ws;
@@ -1157,6 +1224,24 @@ int conan_fgw_barycenter_fwd_ragged(const float *Ys, const int *graph_ptr, const
     if (!graph_ptr || !rowptr || !col || !tgt) return CONAN_E_BADARG;
     return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
                         FgwAdj{graph_ptr, rowptr, col, tgt, nullptr});
+}
+
+int conan_fgw_barycenter_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
+                                    const float *init_C, const float *init_Y, int B, int K, int N, int d,
+                                    const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
+                                    float *errs, void *workspace, void *stream, int solver) {
+    if (!Cs) return CONAN_E_BADARG;
+    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
+                        FgwAdj{nullptr, nullptr, nullptr, nullptr, nullptr}, solver);
+}
+
+int conan_fgw_barycenter_fwd_ragged_solver(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
+                                           const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
+                                           int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T,
+                                           float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver) {
+    if (!graph_ptr || !rowptr || !col || !tgt) return CONAN_E_BADARG;
+    return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
+                        FgwAdj{graph_ptr, rowptr, col, tgt, nullptr}, solver);
 }
 
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,

@@ -1,0 +1,204 @@
+// Coupling solve of fgw_barycenters(..., solver="BAPG") for gfx950: the reference's fgw_bregman (bregman.py:170-279; marginal_loss=False,
+// symmetric), called for every input graph in every outer iteration (barycenter.py:118-160) with the outer max_iter and tol = 1e-4.
+//
+// One workgroup per (molecule b, input graph s), grid B*K; it takes the place of k_fgw_coupling in the outer loop of fgw.hip and hands the
+// update stage the same things (T, Ypart = T Z, Cpart = T h(C2) T^T).  One iteration of the solve is two Bregman half-steps
+//
+//     T <- T * exp(-df(T) / eps);  T <- diag(p / rowsum T) T          df(T) = -2 alpha hC1 T hC2^T + (1 - alpha) M
+//     T <- T * exp(-df(T) / eps);  T <- T diag(q / colsum T)          (hC1 = C1; hC2 = 2 C2, or log(C2 + 1e-15) for kl_loss)
+//
+// and ||T - Tprev||_F is compared with the tol at cpt % 10 == 0.  There is no inner Sinkhorn: the two N^3 products per half-step (A = C1 T,
+// G = A hC2^T on fp64 MFMA) are the whole cost.  The arithmetic is the reference's multiplicative form in fp64, so it underflows where the
+// reference does: a row or column of the iterate whose sum is zero makes the next scaling 0/0 (the reference's NaN, after which it only
+// warns).  The kernel computes the same NaN and raises flags bit 2 of info for the molecule.
+//
+// Matrices (pitch P): T, A and Mb = (1 - alpha) M in fp64, the previous iterate Tp in fp32 (only read by the error check: its rounding moves
+// ||T - Tprev|| by ~1e-8 of ||T||, far below the tol).  28 bytes per entry: in LDS up to N = 64 (LDS = true), else in the coupling scratch
+// of the general kernel's global mode (L2-resident).  C1 (fp64) and C2 (fp32) are read from global memory by the products, as in k_fgw_coupling.
+#include "fgw_common.h"
+
+namespace {
+
+constexpr int BAPG_NW = 8;
+
+__host__ __device__ inline size_t bapg_vec_bytes(int N, int NW = BAPG_NW) { return (size_t)((5 + NW) * N + 16) * 8; }
+
+template <bool LDS, bool KL, int NW>
+__global__ void __launch_bounds__(64 * NW) k_fgw_coupling_bapg(
+    const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb,
+    FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw,
+    const int *__restrict__ active, float *__restrict__ Tw, int *__restrict__ info, char *__restrict__ scratch, size_t scratch_stride,
+    fgw_part_t *__restrict__ Ypart, fgw_part_t *__restrict__ Cpart) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NT = 64 * NW;
+    const int cid = blockIdx.x;
+    const int b = cid / D.K, s = cid % D.K;
+    if (!fgw_active(active, D.B, b, outer)) return;
+    const int N = D.N, P = D.P, d = D.d;
+    const int NN = N * N, NP = N * P;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    // ---- carve: [(5 + NW) N + 16] doubles of vectors, then the matrices (LDS or this coupling's scratch slice)
+    double *pa = reinterpret_cast<double *>(smem), *qb = pa + N, *sc = pa + 2 * N, *y2a = pa + 3 * N, *z2a = pa + 4 * N;
+    double *red = pa + 5 * N, *pm = red + 16;                  // pm[NW][N]: per-wavefront partial sums
+    char *mats = LDS ? smem + bapg_vec_bytes(N, NW) : scratch + (size_t)cid * scratch_stride;
+    double *T = reinterpret_cast<double *>(mats), *A = T + NP, *Mb = A + NP;
+    float *Tp = reinterpret_cast<float *>(Mb + NP);
+
+    const float *Z = Ys + ((size_t)b * D.K + s) * N * d;
+    const float *C2 = Cs + ((size_t)b * D.K + s) * NN;
+    const double *C1 = Cw + (size_t)b * NN;
+    const double *Y = Yw + (size_t)b * N * d;
+    float *Tg = Tw + ((size_t)b * D.K + s) * NN;
+    const double alpha = (double)prm.alpha, eps = (double)prm.epsilon;
+
+    // ---- marginals (uniform when not given) and squared feature norms
+    for (int i = tid; i < N; i += NT) {
+        pa[i] = pb ? (double)pb[(size_t)b * N + i] : 1.0 / (double)N;
+        qb[i] = ps ? (double)ps[((size_t)b * D.K + s) * N + i] : 1.0 / (double)N;
+    }
+    {   // 8 lanes per index, strided partial sums combined by xor-shuffles (fixed order)
+        constexpr int LPI = 8;
+        for (int i0 = 0; i0 < N; i0 += NT / LPI) {
+            const int i = i0 + tid / LPI, sub = tid % LPI;
+            double y2 = 0.0, z2 = 0.0;
+            if (i < N)
+                for (int c = sub; c < d; c += LPI) {
+                    const double yy = Y[i * d + c], zz = (double)Z[i * d + c];
+                    y2 += yy * yy; z2 += zz * zz;
+                }
+#pragma unroll
+            for (int o = 1; o < LPI; o <<= 1) { y2 += __shfl_xor(y2, o, 64); z2 += __shfl_xor(z2, o, 64); }
+            if (i < N && sub == 0) { y2a[i] = y2; z2a[i] = z2; }
+        }
+    }
+    __syncthreads();
+    // ---- T0: warm start from the previous outer iteration, else outer(p, q)      (bregman.py:197-198)
+    for (int t = tid; t < NN; t += NT) {
+        const int i = t / N, j = t - i * N;
+        T[i * P + j] = (outer > 0 && prm.warmstart) ? (double)Tg[t] : pa[i] * qb[j];
+    }
+    // ---- Mb = (1 - alpha) M,  M = clamp(|y_i|^2 + |z_j|^2 - 2 y_i.z_j, 0)    (utils.py:154-171)
+    if (!y_zero) mm_f64_glb<NW, true>(N, N, d, Y, d, Z, d, [&](int i, int j, double v) { Mb[i * P + j] = v; });
+    __syncthreads();
+    for (int t = tid; t < NN; t += NT) {
+        const int i = t / N, j = t - i * N;
+        double m = -2.0 * (y_zero ? 0.0 : Mb[i * P + j]);
+        m += y2a[i]; m += z2a[j];
+        m = m > 0.0 ? m : 0.0;
+        Mb[i * P + j] = (1.0 - alpha) * m;
+    }
+    __syncthreads();
+
+    // T <- T * exp(-df(T) / eps) in place (the second product reads A, not T).  Entries of a massless row / column (fgw.py's embedding of
+    // other sizes) stay exactly zero: the rectangular problem of the reference has no such entries.
+    auto bregman_factor = [&]() {
+        mm_f64_glb<NW, false>(N, N, N, C1, N, T, P, [&](int i, int j, double v) { A[i * P + j] = v; });      // A = C1 T
+        __syncthreads();
+        auto upd = [&](int i, int j, double g) {        // g = (A hC2^T)_ij / c with c = 2 (square: hC2 = 2 C2, folded into the factor) or 1
+            const double x = T[i * P + j] * exp(-(-(KL ? 2.0 : 4.0) * alpha * g + Mb[i * P + j]) / eps);
+            T[i * P + j] = (pa[i] > 0.0 && qb[j] > 0.0) ? x : 0.0;
+        };
+        if constexpr (KL)
+            mm_f64<NW>(N, N, N, [&](int i, int k) { return A[i * P + k]; }, [&](int k, int j) { return log((double)C2[j * N + k] + 1e-15); }, upd);
+        else
+            mm_f64_glb<NW, true>(N, N, N, A, P, C2, N, upd);
+        __syncthreads();
+    };
+
+    int cpt = 0, zero_sum = 0;
+    double err = 1e15;                                                  // bregman.py:240
+    while (err > (double)prm.inner_tol && cpt < prm.max_iter) {
+        const bool check = cpt % 10 == 0;
+        if (check)
+            for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; Tp[i * P + j] = (float)T[i * P + j]; }
+        // ---- rows: T <- T exp(-df/eps); T <- diag(p / rowsum T) T
+        bregman_factor();
+        for (int i = lane; i < N; i += 64) {                            // lane <-> row, the wavefronts split the columns
+            double rs = 0.0;
+            for (int j = wave; j < N; j += NW) rs += T[i * P + j];
+            pm[wave * N + i] = rs;
+        }
+        __syncthreads();
+        for (int i = tid; i < N; i += NT) {
+            double rs = 0.0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) rs += pm[w * N + i];
+            if (pa[i] > 0.0 && !(rs > 0.0)) zero_sum = 1;
+            sc[i] = pa[i] > 0.0 ? pa[i] / rs : 0.0;                     // p_i / 0: the reference's NaN (inf * 0) follows
+        }
+        __syncthreads();
+        for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; T[i * P + j] *= sc[i]; }
+        __syncthreads();
+        // ---- columns: T <- T exp(-df/eps); T <- T diag(q / colsum T)
+        bregman_factor();
+        for (int j = lane; j < N; j += 64) {                            // lane <-> column, the wavefronts split the rows
+            double cs = 0.0;
+            for (int i = wave; i < N; i += NW) cs += T[i * P + j];
+            pm[wave * N + j] = cs;
+        }
+        __syncthreads();
+        for (int j = tid; j < N; j += NT) {
+            double cs = 0.0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) cs += pm[w * N + j];
+            if (qb[j] > 0.0 && !(cs > 0.0)) zero_sum = 1;
+            sc[j] = qb[j] > 0.0 ? qb[j] / cs : 0.0;
+        }
+        __syncthreads();
+        double e2 = 0.0;
+        for (int t = tid; t < NN; t += NT) {
+            const int i = t / N, j = t - i * N;
+            const double x = T[i * P + j] * sc[j];
+            T[i * P + j] = x;
+            if (check) { const double df = x - (double)Tp[i * P + j]; e2 += df * df; }
+        }
+        if (check) err = sqrt(block_sum_d<NW>(e2, red));              // (NaN ends the loop, as in the reference)
+        else __syncthreads();
+        ++cpt;
+    }
+    if (__syncthreads_or(zero_sum) && tid == 0) atomicOr(&info[b * 4 + 3], 4);
+    for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; Tg[t] = (float)T[i * P + j]; }
+    if (tid == 0) atomicAdd(&info[b * 4 + 1], cpt);                     // BAPG iterations (word 2, Sinkhorn iterations, stays 0)
+    // ---- contributions to the barycenter update (summed over s by k_fgw_update_parts)
+    if (!prm.fixed_features) {                                          // Ypart = T @ Z                      (utils.py:90-95)
+        fgw_part_t *Yp = Ypart + ((size_t)b * D.K + s) * N * d;
+        mm_f64_glb<NW, false>(N, d, N, T, P, Z, d, [&](int i, int c, double v) { Yp[(size_t)i * d + c] = (fgw_part_t)v; });
+    }
+    if (!prm.fixed_structure) {                                         // Cpart = T @ h(C2) @ T^T            (utils.py:67-87)
+        fgw_part_t *Cp = Cpart + ((size_t)b * D.K + s) * NN;
+        if constexpr (KL)
+            mm_f64<NW>(N, N, N, [&](int i, int k) { return T[i * P + k]; },
+                       [&](int k, int j) { const double cv = (double)C2[k * N + j]; return log(cv > 1e-15 ? cv : 1e-15); },
+                       [&](int i, int j, double v) { A[i * P + j] = v; });
+        else
+            mm_f64_glb<NW, false>(N, N, N, T, P, C2, N, [&](int i, int j, double v) { A[i * P + j] = v; });
+        __syncthreads();
+        mm_f64_glb<NW, true>(N, N, N, A, P, T, P, [&](int i, int j, double v) { Cp[i * N + j] = (fgw_part_t)v; });
+    }
+}
+
+constexpr size_t BAPG_LDS_LIMIT = 160 * 1024;
+
+}  // namespace
+
+size_t conan_fgw_bapg_lds(int N) { return bapg_vec_bytes(N) + (size_t)N * fgw_pitch(N) * 28; }
+
+void conan_fgw_bapg_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer,
+                             int y_zero, const double *Cw, const double *Yw, const int *active, float *Tw, int *info, char *scratch,
+                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s) {
+    const size_t full = conan_fgw_bapg_lds(D.N);
+    const bool lds = full <= BAPG_LDS_LIMIT;
+    const size_t bytes = lds ? full : bapg_vec_bytes(D.N);
+#define BAPG_LAUNCH(L, KLV)                                                                                                          \
+    do {                                                                                                                             \
+        if (bytes > 64 * 1024)                                                                                                       \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling_bapg<L, KLV, BAPG_NW>),                         \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);                                       \
+        k_fgw_coupling_bapg<L, KLV, BAPG_NW><<<D.B * D.K, 64 * BAPG_NW, bytes, s>>>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, \
+                                                                                  Tw, info, scratch, scratch_stride, Ypart, Cpart);  \
+    } while (0)
+    if (lds) { if (prm.loss_fun) BAPG_LAUNCH(true, true); else BAPG_LAUNCH(true, false); }
+    else { if (prm.loss_fun) BAPG_LAUNCH(false, true); else BAPG_LAUNCH(false, false); }
+#undef BAPG_LAUNCH
+}

@@ -1058,3 +1058,9 @@ void conan_fgw_small_update(const float *pb, const float *lambdas, FgwDims D, co
                             const fgw_part_t *Ypart, const fgw_part_t *Cpart, double *Cw, double *Yw, int *active, int *info,
                             float *errs, float *Yout, float *Cout, double *yvec, const float *Tw, const float *Ys, hipStream_t s);
 int conan_fgw_update_chunk(int K, int N, int d, int B);
+// solver="BAPG" coupling solve (fgw_bapg.hip): one workgroup per (molecule, input graph), any N; `scratch` + cid * scratch_stride is the
+// coupling's slice of the global scratch (28 bytes per N x P entry), used when its matrices do not fit in LDS.
+size_t conan_fgw_bapg_lds(int N);
+void conan_fgw_bapg_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer,
+                             int y_zero, const double *Cw, const double *Yw, const int *active, float *Tw, int *info, char *scratch,
+                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s);

@@ -2,13 +2,18 @@
 (conan_fgw/src/model/fgw/barycenter.py:7-31 `fgw_barycenters`, :393-399 `normalize_tensor`).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
-barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  Option values that exist in
-the reference but are not reached by any model (`BAPG`, `PPA`, `stop_criterion="loss"` — the latter is broken in the reference
-itself) raise `NotImplementedError`.  Input graphs of any size (n_s != N, ragged lists) are solved by embedding them in a
-square problem with massless nodes (below).  Runs on the GPU only.
+barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
+reference (bregman.py:8-67): `solver="PGD"` (every model), `"PPA"` (PGD with the proximal term -epsilon log(T), bregman.py:127-128) and
+`"BAPG"` (Bregman projections, fgw_bregman, bregman.py:170-279; the Sinkhorn keywords numItermax / stopThr / method are ignored, as in the
+reference).  BAPG's multiplicative iteration underflows where the reference's does (small epsilon, wide features): a zero row or column sum
+of an iterate gives NaN outputs, as the reference's, and the reference's warning.  Options that exist in the reference but are not reached by
+any caller (`symmetric=False`, `stop_criterion="loss"` — the latter is broken in the reference itself) raise
+`NotImplementedError`.  Input graphs of any size (n_s != N, ragged lists) are solved by embedding them in a square problem with massless
+nodes (below).  Runs on the GPU only (PPA / BAPG with CPU tensors: `NotImplementedError`).
 """
 from __future__ import annotations
 
+import warnings
 from typing import List, Optional, Sequence, Union
 
 import torch
@@ -27,13 +32,13 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
         raise ValueError(f"Unknown `stop_criterion='{stop_criterion}'`. Use one of: {'barycenter', 'loss'}.")
     if solver not in ["PGD", "PPA", "BAPG"]:
         raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % solver)
-    if solver != "PGD" or stop_criterion != "barycenter":
-        raise NotImplementedError("only solver='PGD', stop_criterion='barycenter' (the path every ConAN model takes, "
-                                  "schnet_no_sum.py:281-306) is implemented on this backend")
+    if stop_criterion != "barycenter":
+        raise NotImplementedError("only stop_criterion='barycenter' (the path every ConAN model takes, schnet_no_sum.py:281-306) is "
+                                  "implemented on this backend")
     if not symmetric:
         raise NotImplementedError("symmetric=False is not reached by any ConAN model")
     method = kwargs.pop("method", "sinkhorn_log")
-    if str(method).lower() != "sinkhorn_log":
+    if solver != "BAPG" and str(method).lower() != "sinkhorn_log":      # (fgw_bregman takes no Sinkhorn keywords, bregman.py:52-67)
         raise NotImplementedError("only method='sinkhorn_log' is implemented")
     num_iter_max = int(kwargs.pop("numItermax", 100))          # sinkhorn.py:12
     stop_thr = float(kwargs.pop("stopThr", 1e-5))              # sinkhorn.py:13
@@ -43,6 +48,8 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
         raise ValueError("If Y is fixed it must be initialized")
 
     N = int(N)
+    if solver != "PGD" and not all(torch.is_tensor(y) and y.is_cuda for y in (Ys.unbind(0) if torch.is_tensor(Ys) else Ys)):
+        raise NotImplementedError(f"solver='{solver}' runs on the GPU only: pass CUDA (ROCm) tensors")
     Ys_l = [y.to(torch.float32) for y in (Ys.unbind(0) if torch.is_tensor(Ys) else Ys)]
     Cs_l = [c.to(torch.float32) for c in (Cs.unbind(0) if torch.is_tensor(Cs) else Cs)]
     K, d = len(Ys_l), Ys_l[0].shape[1]
@@ -103,8 +110,11 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
         init_C=init_C.to(torch.float32).view(1, N, N), init_Y=None if init_Y is None else init_Y.to(torch.float32).view(1, N, d),
         alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, inner_tol=1e-4, num_iter_max=num_iter_max, stop_thr=stop_thr,
         fixed_structure=fixed_structure, fixed_features=fixed_features, warmstart=warmstartT, loss_fun=loss_fun, keep_iterates=bool(log),
-        cs_small_int=small_int)
+        cs_small_int=small_int, solver=solver)
     Y, C, T, info, errs = res[:5]
+    if solver != "PGD" and int(info[0, 3].item()) & 4:
+        # an iterate with a zero row / column sum: the reference's NaN case, where it only warns (bregman.py:159-162, :270-273)
+        warnings.warn("Solver failed to produce a transport plan. You might want to increase the regularization parameter `epsilon`.")
     if embedded:
         Y, C = Y[:, :N_user], C[:, :N_user, :N_user]
     if not log:

@@ -881,6 +881,9 @@ PROD_FGW = dict(alpha=0.1, epsilon=0.1, max_iter=5, tol=1e-2, inner_tol=1e-4, nu
                 fixed_structure=False, fixed_features=False, warmstart=True)       # schnet_no_sum.py:281-306
 
 
+FGW_SOLVERS = {"PGD": 0, "PPA": 1, "BAPG": 2}               # the `solver` codes of conan_fgw_barycenter_fwd_solver (bregman.py:8-67)
+
+
 class _FgwBarycenterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Ys, Cs, ps, p, lambdas, init_C, init_Y, params):
@@ -902,7 +905,18 @@ class _FgwBarycenterFn(torch.autograd.Function):
         info = torch.empty(B, 4, dtype=i32, device=dev)
         errs = torch.empty(B, 2, prm.max_iter, dtype=f32, device=dev)
         import ctypes
-        if adj is None:
+        solver = FGW_SOLVERS[params.get("solver", "PGD")]
+        if solver != 0:              # PPA / BAPG: the same argument lists plus the solver code (PGD keeps the original entry points)
+            if adj is None:
+                ws = torch.empty(int(lib().conan_fgw_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
+                call("conan_fgw_barycenter_fwd_solver", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
+                     B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver)
+            else:
+                ws = torch.empty(int(lib().conan_fgw_workspace_bytes_ragged(B, K, N, d)), dtype=torch.uint8, device=dev)
+                call("conan_fgw_barycenter_fwd_ragged_solver", ptr(Ys, f32), ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32),
+                     ptr(adj.tgt, i32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C),
+                     ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver)
+        elif adj is None:
             ws = torch.empty(int(lib().conan_fgw_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
             call("conan_fgw_barycenter_fwd", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
                  B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr())
@@ -938,7 +952,11 @@ def fgw_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, 
     (+ T_iter [max_iter,B,K,N,N] with keep_iterates=True: the couplings after every outer iteration, barycenter.py:196).
     Gradient flows to Ys only (through the final couplings as constants), like the reference.
     `adjacency=graph` (a RadiusGraph with B * K conformer graphs, Cs=None): the input structures are to_dense_adj of those graphs, read by the
-    coupling kernels from the ragged neighbour lists — no [B,K,N,N] tensor exists (what the models do)."""
+    coupling kernels from the ragged neighbour lists — no [B,K,N,N] tensor exists (what the models do).
+    `solver` = "PGD" (default: the models' solver), "PPA" or "BAPG" — the reference's three coupling solvers (bregman.py:8-67); info[:, 3] bit 2
+    is raised for a molecule whose BAPG / PPA iterate had a zero row or column sum (the reference's NaN case)."""
+    if params.get("solver", "PGD") not in FGW_SOLVERS:
+        raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % params["solver"])
     prm = dict(PROD_FGW)
     prm.update(params)
     opt = lambda t: _c(t) if t is not None else None

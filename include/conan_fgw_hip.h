@@ -564,6 +564,25 @@ int conan_fgw_barycenter_fwd_ragged(const float *Ys, const int *graph_ptr, const
                                     const conan_fgw_params *params /* (host) */, float *Y, float *C, float *T, float *T_iter, int *info,
                                     float *errs, void *workspace, void *stream);
 
+/* The same two solves with the reference's choice of coupling solver (fgw_barycenters(..., solver=S), barycenter.py:118-160 -> bregman.py:8-67):
+ * solver 0 = "PGD" (runs exactly what conan_fgw_barycenter_fwd / _ragged run), 1 = "PPA" (bregman.py:70-167: PGD whose Sinkhorn cost carries
+ * -epsilon log(T) of the previous coupling; numItermax / stopThr as for PGD), 2 = "BAPG" (fgw_bregman, bregman.py:170-279 with
+ * marginal_loss=False: two Bregman projections per iteration in fp64 multiplicative form, no inner Sinkhorn; num_iter_max / stop_thr unused).
+ * Inner iterations run up to max_iter with tol inner_tol, the error ||T - Tprev|| checked at every 10th, as in the reference.  Same workspace
+ * (conan_fgw_workspace_bytes / _ragged), same outputs.  info word 1 counts the PGD (PPA) or BAPG iterations, word 2 the Sinkhorn iterations
+ * (0 for BAPG).  flags bit 2: an iterate of a coupling solve had a zero row or column sum (underflow of the multiplicative form; the
+ * reference's NaN case, where it only warns) — the molecule's outputs are then NaN as the reference's are.  Bits 0 and 1 stay 0 for
+ * solvers 1 and 2 (general kernels only, no padded-node merge; ragged input is expanded to the dense scratch first).  Returns
+ * CONAN_E_BADARG for any other solver value. */
+int conan_fgw_barycenter_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
+                                    const float *init_C, const float *init_Y, int B, int K, int N, int d,
+                                    const conan_fgw_params *params /* (host) */, float *Y, float *C, float *T, float *T_iter,
+                                    int *info, float *errs, void *workspace, void *stream, int solver);
+int conan_fgw_barycenter_fwd_ragged_solver(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
+                                           const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
+                                           int B, int K, int N, int d, const conan_fgw_params *params /* (host) */, float *Y, float *C,
+                                           float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver);
+
 /* dYs[b,s,j,:] = lambdas[s] * sum_i T[b,s,i,j] * (1/p[b,i]) * dY[b,i,:]  — the whole backward of the block given the
  * saved couplings (the reference solves them under torch.no_grad(), barycenter.py:120). */
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,
