@@ -22,6 +22,9 @@ FGW_PROF_ACCESSOR(conan_debug_fgw_prof_large)
 FGW_PROF_TRACE_ACCESSOR(conan_debug_fgw_trace_large)
 #endif
 
+#ifndef CONAN_FGW_ASYM_C1T
+#define CONAN_FGW_ASYM_C1T 1        // (A/B switch) ASYM, modes 1 / 2: B = C1^T T from a transposed fp64 copy of C1 (the coupling's free scratch) instead of the element-reader form
+#endif
 namespace {
 // bytes of global scratch per coupling workgroup (Mr, A, base fp64 + T fp32 = 28 B per matrix entry), rounded to 16 B so that every
 // workgroup's fp64 region is aligned whatever the parity of N*P
@@ -71,7 +74,15 @@ __global__ void k_fgw_init(const float *__restrict__ Cs, const float *__restrict
 // element of the Sinkhorn passes.
 // PPA: solver="PPA" (bregman.py:127-128: tens - eps * log(T) before every Sinkhorn call) — the Sinkhorn kernel matrix is multiplied entrywise by
 // the previous coupling (K_ij = T_ij exp(Mr_ij - ref_j)), and on the exact log-domain pass log(T_ij) is added to Mr (a zero entry is a masked -inf).
-template <int MODE, bool KL, int NW, bool SECOND = false, bool PPA = false>      // KL: loss_fun = "kl_loss"; SECOND: the pass behind k_fgw_coupling_big (see fgw_small.hip)
+// ASYM: symmetric=False / None (bregman.py:98-128 with constCt, hC1t, hC2t = init_matrix(C1^T, C2^T)): the cost is the mean of the gradients of
+// the problem and of its transpose,
+//     tens = alpha (c_i + c'_i + r_j + r'_j - (h1(C1) T h2(C2)^T)_ij - (h1(C1)^T T h2(C2))_ij) + (1 - alpha) M_ij
+// with c' / r' the row sums of the transposed matrices (staging pass) and the second product formed after the first one in the Sinkhorn
+// cost's storage (B = C1^T T in Al's storage once A is consumed; C1^T from a transposed fp64 copy in the coupling's scratch slice, which
+// modes 1 / 2 leave free, and in mode 0 through the element-reader form of the product).  Bit 1 of y_zero
+// selects symmetric=None: the coupling solve checks torch.allclose(C1, C1^T, atol=1e-10) and the same for C2 (bregman.py:103-104) and takes
+// the symmetric form above when both hold — a workgroup-uniform runtime branch inside this instantiation.
+template <int MODE, bool KL, int NW, bool SECOND = false, bool PPA = false, bool ASYM = false>      // KL: loss_fun = "kl_loss"; SECOND: the pass behind k_fgw_coupling_big (see fgw_small.hip)
 __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
     const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb,
     FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw,
@@ -80,6 +91,8 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
     constexpr bool LDS_MODE = MODE == 2, MR_LDS = MODE >= 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = 64 * NW;
+    [[maybe_unused]] int sym_auto = 0;                                  // ASYM: symmetric=None (decided per coupling solve)
+    if constexpr (ASYM) { sym_auto = y_zero >> 1; y_zero &= 1; }
     auto solve = [&](const int cid) {
     const int b = cid / D.K, s = cid % D.K;
     if (!fgw_active(active, D.B, b, outer)) return;
@@ -152,6 +165,35 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
             if (i < N && sub == 0) { ra[i] = r1; rb[i] = r2; y2a[i] = y2; z2a[i] = z2; }
         }
     }
+    // ASYM: c'_i = sum_k f1(C1[k,i]) p_k and r'_j = sum_k q_k f2(C2[k,j]) (init_matrix of the transposes) in pm[0:N] / pm[N:2N] (not live
+    // before the Sinkhorn loop), and the symmetry test of symmetric=None, |x_ik - x_ki| <= 1e-10 + 1e-5 |x_ki| (torch.allclose)
+    [[maybe_unused]] bool asym = false;
+    if constexpr (ASYM) {
+        int nonsym = 0;
+        constexpr int LPI = 8;
+        for (int i0 = 0; i0 < N; i0 += NT / LPI) {
+            const int i = i0 + tid / LPI, sub = tid % LPI;
+            double r1 = 0.0, r2 = 0.0;
+            if (i < N)
+                for (int k = sub; k < N; k += LPI) {
+                    const double c1t = C1[k * N + i], c2t = (double)C2[k * N + i];
+                    r1 += (KL ? c1t * log(c1t + 1e-15) - c1t : c1t * c1t) * u[k];
+                    r2 += v[k] * (KL ? c2t : c2t * c2t);
+                    if (sym_auto) {
+                        const double c1 = C1[i * N + k], c2 = (double)C2[i * N + k];
+                        nonsym |= !(fabs(c1 - c1t) <= 1e-10 + 1e-5 * fabs(c1t)) || !(fabs(c2 - c2t) <= 1e-10 + 1e-5 * fabs(c2t));
+                    }
+                }
+#pragma unroll
+            for (int o = 1; o < LPI; o <<= 1) { r1 += __shfl_xor(r1, o, 64); r2 += __shfl_xor(r2, o, 64); }
+            if (i < N && sub == 0) { pm[i] = r1; pm[N + i] = r2; }
+        }
+        if constexpr (CONAN_FGW_ASYM_C1T && MODE >= 1) {      // C1^T into the slice's first N x P doubles (Mr's place in mode 0: unused in 1 / 2)
+            double *c1t = reinterpret_cast<double *>(gs);
+            for (int t = tid; t < NN; t += NT) { const int i = t / N, k = t - i * N; c1t[t] = C1[k * N + i]; }
+        }
+        asym = !sym_auto || __syncthreads_or(nonsym) != 0;              // (workgroup-uniform)
+    }
     __syncthreads();
     FGW_PROF(0);      // staging: T0, per-index vectors
     // ---- base = alpha*2*constC + (1-alpha)*M,  M = clamp(|y_i|^2 + |z_j|^2 - 2 y_i.z_j, 0)   (utils.py:154-171, bregman.py:124-125)
@@ -165,6 +207,9 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
         double m = -2.0 * (y_zero ? 0.0 : base[i * P + j]);    // utils.py:159-161
         m += y2a[i]; m += z2a[j];
         m = m > 0.0 ? m : 0.0;                                  // :163
+        if constexpr (ASYM) {
+            if (asym) { base[i * P + j] = alpha * (ra[i] + pm[i] + rb[j] + pm[N + j]) + (1.0 - alpha) * m; continue; }
+        }
         base[i * P + j] = 2.0 * alpha * (ra[i] + rb[j]) + (1.0 - alpha) * m;
     }
     __syncthreads();
@@ -189,6 +234,30 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
         __syncthreads();
         FGW_PROF(3);  // A = C1 @ T
         auto form_mr = [&]() {
+            if constexpr (ASYM) {
+                if (asym) {      // G1 = A h2(C2)^T into Mr; B = C1^T T into Al (A is consumed); tens = base - alpha' (G1 + B h2(C2))
+                    if constexpr (KL)
+                        mm_f64<NW>(N, N, N, [&](int i, int k) { return Al[i * P + k]; }, [&](int k, int j) { return log((double)C2[j * N + k] + 1e-15); },
+                               [&](int i, int j, double g) { Mr[i * P + j] = g; });
+                    else
+                        mm_f64_glb<NW, true>(N, N, N, Al, P, C2, N, [&](int i, int j, double g) { Mr[i * P + j] = g; });
+                    __syncthreads();
+                    // T from its fp32 copy (the fp64 one in Mr's storage is gone): the same values
+                    if constexpr (CONAN_FGW_ASYM_C1T && MODE >= 1)
+                        mm_f64_glb<NW, false>(N, N, N, reinterpret_cast<const double *>(gs), N, Tl, P, [&](int i, int j, double v) { Al[i * P + j] = v; });
+                    else
+                        mm_f64<NW>(N, N, N, [&](int i, int k) { return C1[k * N + i]; }, [&](int k, int j) { return (double)Tl[k * P + j]; },
+                                   [&](int i, int j, double v) { Al[i * P + j] = v; });
+                    __syncthreads();
+                    if constexpr (KL)
+                        mm_f64<NW>(N, N, N, [&](int i, int k) { return Al[i * P + k]; }, [&](int k, int j) { return log((double)C2[k * N + j] + 1e-15); },
+                               [&](int i, int j, double g) { Mr[i * P + j] = -(base[i * P + j] - alpha * (Mr[i * P + j] + g)) / eps; });
+                    else      // hC2 = 2 C2
+                        mm_f64_glb<NW, false>(N, N, N, Al, P, C2, N,
+                                              [&](int i, int j, double g) { Mr[i * P + j] = -(base[i * P + j] - 2.0 * alpha * (Mr[i * P + j] + g)) / eps; });
+                    return;
+                }
+            }
             if constexpr (KL)
                 mm_f64<NW>(N, N, N, [&](int i, int k) { return Al[i * P + k]; }, [&](int k, int j) { return log((double)C2[j * N + k] + 1e-15); },
                        [&](int i, int j, double g) { Mr[i * P + j] = -(base[i * P + j] - 2.0 * alpha * g) / eps; });
@@ -280,6 +349,12 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
         if (exact) {
             // ---- exact log-domain Sinkhorn (sinkhorn.py:393-433), restarted from u = v = 0 on a re-formed Mr
             __syncthreads();
+            if constexpr (ASYM) {
+                if (asym) {      // Al holds B = C1^T T: A = C1 T again, T from its fp32 copy
+                    mm_f64_glb<NW, false>(N, N, N, C1, N, Tl, P, [&](int i, int j, double v) { Al[i * P + j] = v; });
+                    __syncthreads();
+                }
+            }
             form_mr();
             if constexpr (PPA) {
                 __syncthreads();
@@ -1049,13 +1124,14 @@ long long conan_fgw_workspace_bytes(int B, int K, int N, int d) {
     return (long long)bytes;
 }
 
-// solver = 1 (PPA) / 2 (BAPG): the outer loop of fgw_fwd_impl with the general initialisation and update kernels and the solver's coupling
-// kernel — PPA: k_fgw_coupling<MODE, KL, GEN_NW, false, true>; BAPG: k_fgw_coupling_bapg (fgw_bapg.hip).  Dense structure only (the caller
-// expands ragged input first); no fast / big / register-resident path, no padded-node merge (flags bit 1 stays 0).
+// solver = 1 (PPA) / 2 (BAPG), or symmetric != 1 (False = 0, None = -1) with any solver: the outer loop of fgw_fwd_impl with the general
+// initialisation and update kernels and the solver's coupling kernel — PGD / PPA: k_fgw_coupling<MODE, KL, GEN_NW, false, PPA, ASYM>; BAPG:
+// k_fgw_coupling_bapg (fgw_bapg.hip).  Dense structure only (the caller expands ragged input first); no fast / big / register-resident path,
+// no padded-node merge (flags bit 1 stays 0).  symmetric=None reaches the kernels as bit 1 of y_zero.
 static int fgw_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
                           const float *init_Y, FgwDims D, const conan_fgw_params &prm, float *Y, float *C, float *T, float *T_iter, int *info,
                           float *errs, double *Cw, double *Yw, int *active, char *sc_c, fgw_part_t *Ypart, fgw_part_t *Cpart, int solver,
-                          hipStream_t s) {
+                          hipStream_t s, int symmetric = 1, char *asym_scratch = nullptr) {
     const int B = D.B, K = D.K, N = D.N;
     const size_t NN = (size_t)N * N, NP = (size_t)N * D.P;
     const bool kl = prm.loss_fun != 0;
@@ -1067,20 +1143,28 @@ static int fgw_fwd_solver(const float *Ys, const float *Cs, const float *ps, con
     for (int outer = 0; outer < prm.max_iter; ++outer) {
         const int y_zero = (outer == 0 && !init_Y) ? 1 : 0;
         if (solver == 2) {
-            conan_fgw_bapg_coupling(Ys, Cs, ps, p, D, prm, outer, y_zero, Cw, Yw, active, T, info, sc_c, coupling_scratch_stride(NP), Ypart, Cpart, s);
+            conan_fgw_bapg_coupling(Ys, Cs, ps, p, D, prm, outer, y_zero, Cw, Yw, active, T, info, sc_c, coupling_scratch_stride(NP), Ypart, Cpart, s,
+                                    symmetric, asym_scratch);
         } else {
-#define CONAN_PPA(M, KLV)                                                                                                           \
+#define CONAN_GEN(M, KLV, PPAV, ASV)                                                                                                \
     do {                                                                                                                            \
         if (lds_bytes > 64 * 1024)                                                                                                  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling<M, KLV, GEN_NW, false, true>),                 \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling<M, KLV, GEN_NW, false, PPAV, ASV>),            \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                                  \
-        k_fgw_coupling<M, KLV, GEN_NW, false, true><<<B * K, 64 * GEN_NW, lds_bytes, s>>>(Ys, Cs, ps, p, D, prm, outer, y_zero, Cw, Yw, active, \
-                                                                                          T, info, sc_c, Ypart, Cpart, nullptr, none);  \
+        k_fgw_coupling<M, KLV, GEN_NW, false, PPAV, ASV><<<B * K, 64 * GEN_NW, lds_bytes, s>>>(Ys, Cs, ps, p, D, prm, outer,            \
+            y_zero | (ASV && symmetric < 0 ? 2 : 0), Cw, Yw, active, T, info, sc_c, Ypart, Cpart, nullptr, none);                   \
     } while (0)
-            if (mode == 2) { if (kl) CONAN_PPA(2, true); else CONAN_PPA(2, false); }
-            else if (mode == 1) { if (kl) CONAN_PPA(1, true); else CONAN_PPA(1, false); }
-            else { if (kl) CONAN_PPA(0, true); else CONAN_PPA(0, false); }
-#undef CONAN_PPA
+#define CONAN_MODES(PPAV, ASV)                                                                                                      \
+    do {                                                                                                                            \
+        if (mode == 2) { if (kl) CONAN_GEN(2, true, PPAV, ASV); else CONAN_GEN(2, false, PPAV, ASV); }                              \
+        else if (mode == 1) { if (kl) CONAN_GEN(1, true, PPAV, ASV); else CONAN_GEN(1, false, PPAV, ASV); }                         \
+        else { if (kl) CONAN_GEN(0, true, PPAV, ASV); else CONAN_GEN(0, false, PPAV, ASV); }                                        \
+    } while (0)
+            if (symmetric == 1) CONAN_MODES(true, false);                // (solver 1: PGD with symmetric = 1 takes the model path)
+            else if (solver == 1) CONAN_MODES(true, true);
+            else CONAN_MODES(false, true);
+#undef CONAN_MODES
+#undef CONAN_GEN
         }
         if (T_iter)
             (void)hipMemcpyAsync(T_iter + (size_t)outer * B * K * NN, T, (size_t)B * K * NN * sizeof(float), hipMemcpyDeviceToDevice, s);
@@ -1093,8 +1177,8 @@ static int fgw_fwd_solver(const float *Ys, const float *Cs, const float *ps, con
 static int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
                         const float *init_C, const float *init_Y, int B, int K, int N, int d,
                         const conan_fgw_params *params_in, float *Y, float *C, float *T, float *T_iter, int *info,
-                        float *errs, void *workspace, void *stream, FgwAdj adj, int solver = 0) {
-    if (solver < 0 || solver > 2) return CONAN_E_BADARG;
+                        float *errs, void *workspace, void *stream, FgwAdj adj, int solver = 0, int symmetric = 1) {
+    if (solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
     if (!Ys || (!Cs && !adj.rowptr) || !params_in || !Y || !C || !T || !info || !errs || !workspace || B <= 0 || K <= 0 || N <= 0 || d <= 0)
         return CONAN_E_BADARG;
     conan_fgw_params params_v = *params_in;
@@ -1120,12 +1204,14 @@ static int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const
     const bool small = conan_fgw_small_supported(N, d);
     const bool kl = params->loss_fun != 0;
     if (params->loss_fun != 0 && params->loss_fun != 1) return CONAN_E_BADARG;
+    // symmetric != 1: the asymmetric BAPG solve's own scratch (N > 64) sits behind the whole workspace (conan_fgw_workspace_bytes_sym / _ragged_sym)
+    char *asym_scratch = static_cast<char *>(workspace) + (adj.rowptr ? conan_fgw_workspace_bytes_ragged(B, K, N, d) : conan_fgw_workspace_bytes(B, K, N, d));
     if (adj.rowptr) {
         // ragged structure: the dense scratch sits behind the regular workspace (conan_fgw_workspace_bytes_ragged).  The kernels with a ragged
         // load stage are the square-loss ones of the model path (k_fgw_coupling_fast for N <= 64, k_fgw_coupling_big above); any other shape /
         // loss expands the graphs into the scratch once and continues on the dense path.
         adj.dense = reinterpret_cast<float *>(static_cast<char *>(workspace) + conan_fgw_workspace_bytes(B, K, N, d));
-        const bool ragged_ok = solver == 0 && !kl && (small ? conan_fgw_fast_supported(N, d, 1) : big_lds(N, true) <= LDS_LIMIT);
+        const bool ragged_ok = solver == 0 && symmetric == 1 && !kl && (small ? conan_fgw_fast_supported(N, d, 1) : big_lds(N, true) <= LDS_LIMIT);
         if (!ragged_ok) {
             k_adj_dense<<<B * K, 256, 0, s>>>(adj, N);
             Cs = adj.dense;
@@ -1133,8 +1219,9 @@ static int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const
         }
     }
 
-    if (solver != 0) return fgw_fwd_solver(Ys, Cs, ps, p, lambdas, init_C, init_Y, D, *params, Y, C, T, T_iter, info, errs, Cw, Yw, active, sc_c,
-                                           Ypart, Cpart, solver, s);
+    if (solver != 0 || symmetric != 1)
+        return fgw_fwd_solver(Ys, Cs, ps, p, lambdas, init_C, init_Y, D, *params, Y, C, T, T_iter, info, errs, Cw, Yw, active, sc_c, Ypart, Cpart,
+                              solver, s, symmetric, asym_scratch);
 
     // size-ordered dealing of the coupling workgroups (speed only): k_fgw_coupling_fast and k_fgw_coupling_big
     if (adj.rowptr && !kl && (B & 7) == 0 && B <= 4096 && (small || (CONAN_FGW_BIG_ORDER && big_lds(N, true) <= LDS_LIMIT))) adj.order = order_ws;
@@ -1242,6 +1329,36 @@ int conan_fgw_barycenter_fwd_ragged_solver(const float *Ys, const int *graph_ptr
     if (!graph_ptr || !rowptr || !col || !tgt) return CONAN_E_BADARG;
     return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
                         FgwAdj{graph_ptr, rowptr, col, tgt, nullptr}, solver);
+}
+
+long long conan_fgw_workspace_bytes_sym(int B, int K, int N, int d, int solver, int symmetric) {
+    const long long w = conan_fgw_workspace_bytes(B, K, N, d);
+    if (w <= 0 || solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return 0;
+    return w + (solver == 2 && symmetric != 1 ? (long long)al256(conan_fgw_bapg_asym_scratch_bytes(B, K, N)) : 0);
+}
+
+long long conan_fgw_workspace_bytes_ragged_sym(int B, int K, int N, int d, int solver, int symmetric) {
+    const long long w = conan_fgw_workspace_bytes_ragged(B, K, N, d);
+    if (w <= 0 || solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return 0;
+    return w + (solver == 2 && symmetric != 1 ? (long long)al256(conan_fgw_bapg_asym_scratch_bytes(B, K, N)) : 0);
+}
+
+int conan_fgw_barycenter_fwd_sym(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
+                                 const float *init_C, const float *init_Y, int B, int K, int N, int d,
+                                 const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
+                                 float *errs, void *workspace, void *stream, int solver, int symmetric) {
+    if (!Cs) return CONAN_E_BADARG;
+    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
+                        FgwAdj{nullptr, nullptr, nullptr, nullptr, nullptr}, solver, symmetric);
+}
+
+int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
+                                        const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
+                                        int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T,
+                                        float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver, int symmetric) {
+    if (!graph_ptr || !rowptr || !col || !tgt) return CONAN_E_BADARG;
+    return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
+                        FgwAdj{graph_ptr, rowptr, col, tgt, nullptr}, solver, symmetric);
 }
 
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,

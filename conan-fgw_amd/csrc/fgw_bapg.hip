@@ -15,6 +15,12 @@
 // Matrices (pitch P): T, A and Mb = (1 - alpha) M in fp64, the previous iterate Tp in fp32 (only read by the error check: its rounding moves
 // ||T - Tprev|| by ~1e-8 of ||T||, far below the tol).  28 bytes per entry: in LDS up to N = 64 (LDS = true), else in the coupling scratch
 // of the general kernel's global mode (L2-resident).  C1 (fp64) and C2 (fp32) are read from global memory by the products, as in k_fgw_coupling.
+//
+// ASYM: symmetric=False / None (bregman.py:199-222): df(T) = -alpha (hC1 T hC2^T + hC1^T T hC2) + (1 - alpha) M.  The second product needs the
+// iterate after the first is done, so G1 = A hC2^T waits in one more fp64 matrix G (36 bytes per entry: LDS up to N = 64, else a scratch of
+// its own behind the regular workspace, conan_fgw_workspace_bytes_sym); C1^T is read through the element-reader form of the product.  Bit 1
+// of y_zero selects symmetric=None: torch.allclose(C1, C1^T, atol=1e-10) and the same for C2 (bregman.py:199-200), per coupling solve, and the
+// symmetric form when both hold.
 #include "fgw_common.h"
 
 namespace {
@@ -23,7 +29,7 @@ constexpr int BAPG_NW = 8;
 
 __host__ __device__ inline size_t bapg_vec_bytes(int N, int NW = BAPG_NW) { return (size_t)((5 + NW) * N + 16) * 8; }
 
-template <bool LDS, bool KL, int NW>
+template <bool LDS, bool KL, int NW, bool ASYM = false>
 __global__ void __launch_bounds__(64 * NW) k_fgw_coupling_bapg(
     const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb,
     FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw,
@@ -31,6 +37,8 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling_bapg(
     fgw_part_t *__restrict__ Ypart, fgw_part_t *__restrict__ Cpart) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = 64 * NW;
+    [[maybe_unused]] int sym_auto = 0;
+    if constexpr (ASYM) { sym_auto = y_zero >> 1; y_zero &= 1; }
     const int cid = blockIdx.x;
     const int b = cid / D.K, s = cid % D.K;
     if (!fgw_active(active, D.B, b, outer)) return;
@@ -43,7 +51,8 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling_bapg(
     double *red = pa + 5 * N, *pm = red + 16;                  // pm[NW][N]: per-wavefront partial sums
     char *mats = LDS ? smem + bapg_vec_bytes(N, NW) : scratch + (size_t)cid * scratch_stride;
     double *T = reinterpret_cast<double *>(mats), *A = T + NP, *Mb = A + NP;
-    float *Tp = reinterpret_cast<float *>(Mb + NP);
+    [[maybe_unused]] double *G = Mb + NP;                      // ASYM only
+    float *Tp = reinterpret_cast<float *>(ASYM ? G + NP : Mb + NP);
 
     const float *Z = Ys + ((size_t)b * D.K + s) * N * d;
     const float *C2 = Cs + ((size_t)b * D.K + s) * NN;
@@ -72,6 +81,17 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling_bapg(
             if (i < N && sub == 0) { y2a[i] = y2; z2a[i] = z2; }
         }
     }
+    [[maybe_unused]] bool asym = false;
+    if constexpr (ASYM) {
+        int nonsym = 0;
+        if (sym_auto)
+            for (int t = tid; t < NN; t += NT) {
+                const int i = t / N, k = t - i * N;
+                const double c1 = C1[i * N + k], c1t = C1[k * N + i], c2 = (double)C2[i * N + k], c2t = (double)C2[k * N + i];
+                nonsym |= !(fabs(c1 - c1t) <= 1e-10 + 1e-5 * fabs(c1t)) || !(fabs(c2 - c2t) <= 1e-10 + 1e-5 * fabs(c2t));
+            }
+        asym = !sym_auto || __syncthreads_or(nonsym) != 0;              // (workgroup-uniform)
+    }
     __syncthreads();
     // ---- T0: warm start from the previous outer iteration, else outer(p, q)      (bregman.py:197-198)
     for (int t = tid; t < NN; t += NT) {
@@ -95,6 +115,29 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling_bapg(
     auto bregman_factor = [&]() {
         mm_f64_glb<NW, false>(N, N, N, C1, N, T, P, [&](int i, int j, double v) { A[i * P + j] = v; });      // A = C1 T
         __syncthreads();
+        if constexpr (ASYM) {
+            if (asym) {      // G = A hC2^T; A = C1^T T; T <- T exp(-(-alpha' (G + A hC2) + Mb) / eps)
+                if constexpr (KL)
+                    mm_f64<NW>(N, N, N, [&](int i, int k) { return A[i * P + k]; }, [&](int k, int j) { return log((double)C2[j * N + k] + 1e-15); },
+                               [&](int i, int j, double g) { G[i * P + j] = g; });
+                else
+                    mm_f64_glb<NW, true>(N, N, N, A, P, C2, N, [&](int i, int j, double g) { G[i * P + j] = g; });
+                __syncthreads();
+                mm_f64<NW>(N, N, N, [&](int i, int k) { return C1[k * N + i]; }, [&](int k, int j) { return T[k * P + j]; },
+                           [&](int i, int j, double v) { A[i * P + j] = v; });
+                __syncthreads();
+                auto upd2 = [&](int i, int j, double g) {      // square: hC2 = 2 C2 (factor 2 folded in)
+                    const double x = T[i * P + j] * exp(-(-(KL ? 1.0 : 2.0) * alpha * (G[i * P + j] + g) + Mb[i * P + j]) / eps);
+                    T[i * P + j] = (pa[i] > 0.0 && qb[j] > 0.0) ? x : 0.0;
+                };
+                if constexpr (KL)
+                    mm_f64<NW>(N, N, N, [&](int i, int k) { return A[i * P + k]; }, [&](int k, int j) { return log((double)C2[k * N + j] + 1e-15); }, upd2);
+                else
+                    mm_f64_glb<NW, false>(N, N, N, A, P, C2, N, upd2);
+                __syncthreads();
+                return;
+            }
+        }
         auto upd = [&](int i, int j, double g) {        // g = (A hC2^T)_ij / c with c = 2 (square: hC2 = 2 C2, folded into the factor) or 1
             const double x = T[i * P + j] * exp(-(-(KL ? 2.0 : 4.0) * alpha * g + Mb[i * P + j]) / eps);
             T[i * P + j] = (pa[i] > 0.0 && qb[j] > 0.0) ? x : 0.0;
@@ -180,25 +223,41 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_coupling_bapg(
 
 constexpr size_t BAPG_LDS_LIMIT = 160 * 1024;
 
+__host__ inline size_t bapg_asym_stride(size_t NP) { return (NP * 36 + 15) / 16 * 16; }
+
 }  // namespace
 
-size_t conan_fgw_bapg_lds(int N) { return bapg_vec_bytes(N) + (size_t)N * fgw_pitch(N) * 28; }
+size_t conan_fgw_bapg_lds(int N, bool asym) { return bapg_vec_bytes(N) + (size_t)N * fgw_pitch(N) * (asym ? 36 : 28); }
+
+size_t conan_fgw_bapg_asym_scratch_bytes(int B, int K, int N) {
+    return conan_fgw_bapg_lds(N, true) <= BAPG_LDS_LIMIT ? 0 : (size_t)B * K * bapg_asym_stride((size_t)N * fgw_pitch(N));
+}
 
 void conan_fgw_bapg_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer,
                              int y_zero, const double *Cw, const double *Yw, const int *active, float *Tw, int *info, char *scratch,
-                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s) {
-    const size_t full = conan_fgw_bapg_lds(D.N);
+                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s, int symmetric, char *asym_scratch) {
+    const bool asym = symmetric != 1;
+    const size_t full = conan_fgw_bapg_lds(D.N, asym);
     const bool lds = full <= BAPG_LDS_LIMIT;
     const size_t bytes = lds ? full : bapg_vec_bytes(D.N);
-#define BAPG_LAUNCH(L, KLV)                                                                                                          \
+    if (asym) {      // symmetric=None travels in bit 1 of y_zero; outside LDS the matrices sit in the asymmetric solve's own scratch
+        y_zero |= symmetric < 0 ? 2 : 0;
+        if (!lds) { scratch = asym_scratch; scratch_stride = bapg_asym_stride((size_t)D.N * D.P); }
+    }
+#define BAPG_LAUNCH(L, KLV, AS)                                                                                                      \
     do {                                                                                                                             \
         if (bytes > 64 * 1024)                                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling_bapg<L, KLV, BAPG_NW>),                         \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling_bapg<L, KLV, BAPG_NW, AS>),                     \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);                                       \
-        k_fgw_coupling_bapg<L, KLV, BAPG_NW><<<D.B * D.K, 64 * BAPG_NW, bytes, s>>>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, \
-                                                                                  Tw, info, scratch, scratch_stride, Ypart, Cpart);  \
+        k_fgw_coupling_bapg<L, KLV, BAPG_NW, AS><<<D.B * D.K, 64 * BAPG_NW, bytes, s>>>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, \
+                                                                                      Tw, info, scratch, scratch_stride, Ypart, Cpart); \
     } while (0)
-    if (lds) { if (prm.loss_fun) BAPG_LAUNCH(true, true); else BAPG_LAUNCH(true, false); }
-    else { if (prm.loss_fun) BAPG_LAUNCH(false, true); else BAPG_LAUNCH(false, false); }
+    if (asym) {
+        if (lds) { if (prm.loss_fun) BAPG_LAUNCH(true, true, true); else BAPG_LAUNCH(true, false, true); }
+        else { if (prm.loss_fun) BAPG_LAUNCH(false, true, true); else BAPG_LAUNCH(false, false, true); }
+    } else {
+        if (lds) { if (prm.loss_fun) BAPG_LAUNCH(true, true, false); else BAPG_LAUNCH(true, false, false); }
+        else { if (prm.loss_fun) BAPG_LAUNCH(false, true, false); else BAPG_LAUNCH(false, false, false); }
+    }
 #undef BAPG_LAUNCH
 }

@@ -1060,7 +1060,11 @@ void conan_fgw_small_update(const float *pb, const float *lambdas, FgwDims D, co
 int conan_fgw_update_chunk(int K, int N, int d, int B);
 // solver="BAPG" coupling solve (fgw_bapg.hip): one workgroup per (molecule, input graph), any N; `scratch` + cid * scratch_stride is the
 // coupling's slice of the global scratch (28 bytes per N x P entry), used when its matrices do not fit in LDS.
-size_t conan_fgw_bapg_lds(int N);
+// symmetric = 1 (True), 0 (False) or -1 (None, decided per coupling solve); symmetric != 1 outside LDS (N > 64) runs in `asym_scratch`,
+// conan_fgw_bapg_asym_scratch_bytes(B, K, N) bytes (36 bytes per N x P entry and coupling; 0 when the matrices fit in LDS).
+size_t conan_fgw_bapg_lds(int N, bool asym = false);
+size_t conan_fgw_bapg_asym_scratch_bytes(int B, int K, int N);
 void conan_fgw_bapg_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer,
                              int y_zero, const double *Cw, const double *Yw, const int *active, float *Tw, int *info, char *scratch,
-                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s);
+                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s, int symmetric = 1,
+                             char *asym_scratch = nullptr);

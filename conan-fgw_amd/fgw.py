@@ -6,10 +6,12 @@ barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (ut
 reference (bregman.py:8-67): `solver="PGD"` (every model), `"PPA"` (PGD with the proximal term -epsilon log(T), bregman.py:127-128) and
 `"BAPG"` (Bregman projections, fgw_bregman, bregman.py:170-279; the Sinkhorn keywords numItermax / stopThr / method are ignored, as in the
 reference).  BAPG's multiplicative iteration underflows where the reference's does (small epsilon, wide features): a zero row or column sum
-of an iterate gives NaN outputs, as the reference's, and the reference's warning.  Options that exist in the reference but are not reached by
-any caller (`symmetric=False`, `stop_criterion="loss"` — the latter is broken in the reference itself) raise
-`NotImplementedError`.  Input graphs of any size (n_s != N, ragged lists) are solved by embedding them in a square problem with massless
-nodes (below).  Runs on the GPU only (PPA / BAPG with CPU tensors: `NotImplementedError`).
+of an iterate gives NaN outputs, as the reference's, and the reference's warning.  `symmetric` as in the reference (bregman.py:98-128,
+:199-222), for all three solvers and both losses: True (every model), False (directed graphs, asymmetric structure or cost matrices: the
+gradient averages the problem and its transpose) or None (decided in every coupling solve by torch.allclose(C, C^T, atol=1e-10) on the
+current barycenter structure and the input graph).  `stop_criterion="loss"` exists in the reference but is broken there and
+raises `NotImplementedError`.  Input graphs of any size (n_s != N, ragged lists) are solved by embedding them in a square problem with
+massless nodes (below).  Runs on the GPU only (PPA / BAPG, or symmetric other than True, with CPU tensors: `NotImplementedError`).
 """
 from __future__ import annotations
 
@@ -35,8 +37,7 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
     if stop_criterion != "barycenter":
         raise NotImplementedError("only stop_criterion='barycenter' (the path every ConAN model takes, schnet_no_sum.py:281-306) is "
                                   "implemented on this backend")
-    if not symmetric:
-        raise NotImplementedError("symmetric=False is not reached by any ConAN model")
+    symmetric = None if symmetric is None else bool(symmetric)           # (bregman.py:103-106: None is decided per call, else truthiness)
     method = kwargs.pop("method", "sinkhorn_log")
     if solver != "BAPG" and str(method).lower() != "sinkhorn_log":      # (fgw_bregman takes no Sinkhorn keywords, bregman.py:52-67)
         raise NotImplementedError("only method='sinkhorn_log' is implemented")
@@ -48,8 +49,9 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
         raise ValueError("If Y is fixed it must be initialized")
 
     N = int(N)
-    if solver != "PGD" and not all(torch.is_tensor(y) and y.is_cuda for y in (Ys.unbind(0) if torch.is_tensor(Ys) else Ys)):
-        raise NotImplementedError(f"solver='{solver}' runs on the GPU only: pass CUDA (ROCm) tensors")
+    if (solver != "PGD" or symmetric is not True) and not all(torch.is_tensor(y) and y.is_cuda for y in (Ys.unbind(0) if torch.is_tensor(Ys) else Ys)):
+        what = f"solver='{solver}'" if symmetric is True else f"symmetric={symmetric}"
+        raise NotImplementedError(f"{what} runs on the GPU only: pass CUDA (ROCm) tensors")
     Ys_l = [y.to(torch.float32) for y in (Ys.unbind(0) if torch.is_tensor(Ys) else Ys)]
     Cs_l = [c.to(torch.float32) for c in (Cs.unbind(0) if torch.is_tensor(Cs) else Cs)]
     K, d = len(Ys_l), Ys_l[0].shape[1]
@@ -110,7 +112,7 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
         init_C=init_C.to(torch.float32).view(1, N, N), init_Y=None if init_Y is None else init_Y.to(torch.float32).view(1, N, d),
         alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, inner_tol=1e-4, num_iter_max=num_iter_max, stop_thr=stop_thr,
         fixed_structure=fixed_structure, fixed_features=fixed_features, warmstart=warmstartT, loss_fun=loss_fun, keep_iterates=bool(log),
-        cs_small_int=small_int, solver=solver)
+        cs_small_int=small_int, solver=solver, symmetric=symmetric)
     Y, C, T, info, errs = res[:5]
     if solver != "PGD" and int(info[0, 3].item()) & 4:
         # an iterate with a zero row / column sum: the reference's NaN case, where it only warns (bregman.py:159-162, :270-273)

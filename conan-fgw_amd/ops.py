@@ -884,6 +884,17 @@ PROD_FGW = dict(alpha=0.1, epsilon=0.1, max_iter=5, tol=1e-2, inner_tol=1e-4, nu
 FGW_SOLVERS = {"PGD": 0, "PPA": 1, "BAPG": 2}               # the `solver` codes of conan_fgw_barycenter_fwd_solver (bregman.py:8-67)
 
 
+def _symmetric_code(symmetric) -> int:
+    """The `symmetric` code of conan_fgw_barycenter_fwd_sym: True -> 1, False -> 0, None -> -1 (decided per coupling solve)."""
+    if symmetric is True:
+        return 1
+    if symmetric is False:
+        return 0
+    if symmetric is None:
+        return -1
+    raise ValueError(f"symmetric must be True, False or None, not {symmetric!r}")
+
+
 class _FgwBarycenterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Ys, Cs, ps, p, lambdas, init_C, init_Y, params):
@@ -906,7 +917,19 @@ class _FgwBarycenterFn(torch.autograd.Function):
         errs = torch.empty(B, 2, prm.max_iter, dtype=f32, device=dev)
         import ctypes
         solver = FGW_SOLVERS[params.get("solver", "PGD")]
-        if solver != 0:              # PPA / BAPG: the same argument lists plus the solver code (PGD keeps the original entry points)
+        symmetric = _symmetric_code(params.get("symmetric", True))
+        if symmetric != 1:           # symmetric=False / None: the `_solver` argument lists plus the solver and symmetric codes
+            if adj is None:
+                ws = torch.empty(int(lib().conan_fgw_workspace_bytes_sym(B, K, N, d, solver, symmetric)), dtype=torch.uint8, device=dev)
+                call("conan_fgw_barycenter_fwd_sym", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
+                     B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver,
+                     symmetric)
+            else:
+                ws = torch.empty(int(lib().conan_fgw_workspace_bytes_ragged_sym(B, K, N, d, solver, symmetric)), dtype=torch.uint8, device=dev)
+                call("conan_fgw_barycenter_fwd_ragged_sym", ptr(Ys, f32), ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32),
+                     ptr(adj.tgt, i32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C),
+                     ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver, symmetric)
+        elif solver != 0:            # PPA / BAPG: the same argument lists plus the solver code (PGD keeps the original entry points)
             if adj is None:
                 ws = torch.empty(int(lib().conan_fgw_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
                 call("conan_fgw_barycenter_fwd_solver", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
@@ -954,9 +977,13 @@ def fgw_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, 
     `adjacency=graph` (a RadiusGraph with B * K conformer graphs, Cs=None): the input structures are to_dense_adj of those graphs, read by the
     coupling kernels from the ragged neighbour lists — no [B,K,N,N] tensor exists (what the models do).
     `solver` = "PGD" (default: the models' solver), "PPA" or "BAPG" — the reference's three coupling solvers (bregman.py:8-67); info[:, 3] bit 2
-    is raised for a molecule whose BAPG / PPA iterate had a zero row or column sum (the reference's NaN case)."""
+    is raised for a molecule whose BAPG / PPA iterate had a zero row or column sum (the reference's NaN case).
+    `symmetric` = True (default: today's entry points), False (directed graphs / asymmetric structure matrices: the cost of bregman.py:98-128
+    averages the problem and its transpose) or None (decided per coupling solve by torch.allclose(C, C^T, atol=1e-10) on the barycenter
+    structure and the input graph, as the reference's every fgw() call does); False / None run the general kernels for every solver."""
     if params.get("solver", "PGD") not in FGW_SOLVERS:
         raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % params["solver"])
+    _symmetric_code(params.get("symmetric", True))
     prm = dict(PROD_FGW)
     prm.update(params)
     opt = lambda t: _c(t) if t is not None else None

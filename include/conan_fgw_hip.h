@@ -583,6 +583,27 @@ int conan_fgw_barycenter_fwd_ragged_solver(const float *Ys, const int *graph_ptr
                                            int B, int K, int N, int d, const conan_fgw_params *params /* (host) */, float *Y, float *C,
                                            float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver);
 
+/* The `_solver` pair with the reference's `symmetric` argument as well (fgw_barycenters(..., symmetric=S), barycenter.py:118-160 ->
+ * bregman.py:98-128 / :199-222): symmetric 1 = True (runs exactly what conan_fgw_barycenter_fwd_solver / _ragged_solver run), 0 = False (the
+ * cost is the mean of the gradients of the problem and of its transpose, init_matrix(C1^T, C2^T): for directed graphs and other asymmetric
+ * structure matrices), -1 = None (decided per coupling solve, as the reference's every fgw() call does: False unless the barycenter structure
+ * and the input graph both pass torch.allclose(X, X^T, atol=1e-10)).  symmetric != 1 runs the general kernels for every solver (PGD as well:
+ * no fast / big path, no padded-node merge, flags bits 0 / 1 as for solvers 1 / 2) and expands ragged input to the dense scratch first.
+ * Workspace: conan_fgw_workspace_bytes_sym / _ragged_sym with the same solver and symmetric (equal to conan_fgw_workspace_bytes / _ragged
+ * except for BAPG with symmetric != 1 at N > 64, whose solve needs a scratch of its own).  Returns CONAN_E_BADARG (size queries: 0) for a
+ * solver outside 0..2 or a symmetric outside -1..1. */
+long long conan_fgw_workspace_bytes_sym(int B, int K, int N, int d, int solver, int symmetric);
+long long conan_fgw_workspace_bytes_ragged_sym(int B, int K, int N, int d, int solver, int symmetric);
+int conan_fgw_barycenter_fwd_sym(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
+                                 const float *init_C, const float *init_Y, int B, int K, int N, int d,
+                                 const conan_fgw_params *params /* (host) */, float *Y, float *C, float *T, float *T_iter,
+                                 int *info, float *errs, void *workspace, void *stream, int solver, int symmetric);
+int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
+                                        const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
+                                        int B, int K, int N, int d, const conan_fgw_params *params /* (host) */, float *Y, float *C,
+                                        float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver,
+                                        int symmetric);
+
 /* dYs[b,s,j,:] = lambdas[s] * sum_i T[b,s,i,j] * (1/p[b,i]) * dY[b,i,:]  — the whole backward of the block given the
  * saved couplings (the reference solves them under torch.no_grad(), barycenter.py:120). */
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,

@@ -5,7 +5,10 @@ BACE-shaped batch (B=64, K=5, N=90), for kernel timing:
 
 Each configuration runs twice (a warm-up, then the timed solve); the per-kernel durations come from the kernel trace (k_fgw_coupling_fast /
 _big for PGD, k_fgw_coupling<..., PPA = true> for PPA, k_fgw_coupling_bapg for BAPG).  The script itself prints the wall time of the timed
-solve (torch.cuda events) and its iteration counts.  BAPG runs at epsilon = 2.0: at the models' 0.1 it is NaN, in the reference as here."""
+solve (torch.cuda events) and its iteration counts.  BAPG runs at epsilon = 2.0: at the models' 0.1 it is NaN, in the reference as here.
+Every solver runs with symmetric=True and then with symmetric=False (k_fgw_coupling<..., ASYM = true> for PGD / PPA,
+k_fgw_coupling_bapg<..., ASYM = true> for BAPG) on the same, symmetric, input: the cost of the second product and of the general kernel
+for PGD.  `--sym-only` runs the symmetric=False solves alone."""
 import os
 import sys
 
@@ -31,7 +34,11 @@ def batch(shape, B, K):
 def main():
     for shape, B, K in (("esol", 256, 5), ("bace", 64, 5)):
         Ys, g = batch(shape, B, K)
-        for solver, kw in (("PGD", {}), ("PPA", {}), ("BAPG", {"epsilon": 2.0})):      # (BAPG is NaN at the models' epsilon = 0.1)
+        runs = [(solver, kw, sym) for sym in (True, False) for solver, kw in (("PGD", {}), ("PPA", {}), ("BAPG", {"epsilon": 2.0}))]
+        for solver, kw, sym in runs:      # (BAPG is NaN at the models' epsilon = 0.1)
+            if sym and "--sym-only" in sys.argv:
+                continue
+            kw = dict(kw, symmetric=sym)
             ops.fgw_barycenter_batched(Ys, None, adjacency=g, solver=solver, **kw)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -40,7 +47,7 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             info = out[3]
-            print(f"{shape} B={B} K={K} N={Ys.shape[2]} {solver:5s} {e0.elapsed_time(e1):8.3f} ms  outer={int(info[:, 0].sum())} "
+            print(f"{shape} B={B} K={K} N={Ys.shape[2]} {solver:5s} symmetric={sym!s:5s} {e0.elapsed_time(e1):8.3f} ms  outer={int(info[:, 0].sum())} "
                   f"inner={int(info[:, 1].sum())} sinkhorn={int(info[:, 2].sum())} flags={int((info[:, 3] & 4).sum() // 4)} molecules with bit 2",
                   flush=True)
 
