@@ -11,7 +11,9 @@ of an iterate gives NaN outputs, as the reference's, and the reference's warning
 gradient averages the problem and its transpose) or None (decided in every coupling solve by torch.allclose(C, C^T, atol=1e-10) on the
 current barycenter structure and the input graph).  `stop_criterion="loss"` exists in the reference but is broken there and
 raises `NotImplementedError`.  Input graphs of any size (n_s != N, ragged lists) are solved by embedding them in a square problem with
-massless nodes (below).  Runs on the GPU only (PPA / BAPG, or symmetric other than True, with CPU tensors: `NotImplementedError`).
+massless nodes (below).  Differentiable like the reference, whose couplings are solved under torch.no_grad() (barycenter.py:120): Y and
+C carry gradients to Ys, Cs, p and lambdas (to init_Y / init_C instead under fixed_features / fixed_structure); ps gets none.  Runs on
+the GPU only (PPA / BAPG, or symmetric other than True, with CPU tensors: `NotImplementedError`).
 """
 from __future__ import annotations
 
@@ -104,7 +106,11 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
     p_t = p_embedded.view(1, N) if embedded else (p.to(torch.float32).view(1, N) if p is not None else None)
     lam = None
     if lambdas is not None:
-        lam = torch.as_tensor(lambdas, dtype=torch.float32, device=Ys_t.device)
+        if not torch.is_tensor(lambdas) and any(torch.is_tensor(l) for l in lambdas):
+            # a list of (0-d) tensors: stacked, so that a lambda that requires grad keeps its graph (torch.as_tensor would drop it)
+            lam = torch.stack([torch.as_tensor(l, dtype=torch.float32, device=Ys_t.device).reshape(()) for l in lambdas])
+        else:
+            lam = torch.as_tensor(lambdas, dtype=torch.float32, device=Ys_t.device)
     # adjacency-like inputs (integers in [0, 255]: what to_dense_adj produces) take the byte-wide LDS layout of the N <= 64 kernel
     small_int = bool(((Cs_t == Cs_t.round()) & (Cs_t >= 0) & (Cs_t <= 255)).all())
     res = ops.fgw_barycenter_batched(

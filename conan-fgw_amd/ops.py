@@ -948,24 +948,62 @@ class _FgwBarycenterFn(torch.autograd.Function):
             call("conan_fgw_barycenter_fwd_ragged", ptr(Ys, f32), ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32), ptr(adj.tgt, i32),
                  ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter),
                  ptr(info), ptr(errs), ptr(ws), stream_ptr())
-        ctx.save_for_backward(T, p, lambdas)
         ctx.dims = (B, K, N, d)
         ctx.set_materialize_grads(False)          # C, T, info, errs carry no gradient: without this autograd fills four zero tensors per backward
+        # Gradients beyond Ys (conan_fgw_barycenter_bwd_full): the last update steps are differentiable in Cs, p, lambdas (and init_C /
+        # init_Y under fixed_structure / fixed_features), as in the reference.  Every model asks for Ys only: that path saves and launches
+        # exactly what it always did, and C stays non-differentiable.
+        need = ctx.needs_input_grad
+        fs, ff = bool(params["fixed_structure"]), bool(params["fixed_features"])
+        want = dict(Ys=need[0] and not ff, Cs=need[1] and Cs is not None and not fs, p=need[3] and p is not None,
+                    lam=need[4] and lambdas is not None, init_C=need[5] and fs, init_Y=need[6] and ff)
+        ctx.full = any(want[k] for k in ("Cs", "p", "lam", "init_C", "init_Y")) or (need[0] and ff)
+        c_diff = want["init_C"] if fs else (want["Cs"] or want["p"] or want["lam"])
+        if not ctx.full:
+            ctx.save_for_backward(T, p, lambdas)
+        else:
+            kl = prm.loss_fun == 1
+            ctx.want, ctx.flags = want, (prm.loss_fun, int(fs), int(ff))
+            keep_Ys = want["lam"] and not ff
+            keep_Cs = (want["Cs"] or want["lam"]) and not fs
+            keep_Y = want["p"] and not ff
+            keep_C = not fs and (want["p"] or (kl and (want["Cs"] or want["lam"])))
+            ctx.save_for_backward(T, p, lambdas, Ys if keep_Ys else None, Cs if keep_Cs else None, Y if keep_Y else None,
+                                  C if keep_C else None)
+        nd = (T, info, errs) if c_diff else (C, T, info, errs)
         if T_iter is None:
-            ctx.mark_non_differentiable(C, T, info, errs)
+            ctx.mark_non_differentiable(*nd)
             return Y, C, T, info, errs
-        ctx.mark_non_differentiable(C, T, info, errs, T_iter)
+        ctx.mark_non_differentiable(*nd, T_iter)
         return Y, C, T, info, errs, T_iter
 
     @staticmethod
-    def backward(ctx, dY, *_):
-        if dY is None:
+    def backward(ctx, dY, dC=None, *_):
+        if not ctx.full:
+            if dY is None:
+                return (None,) * 8
+            T, p, lambdas = ctx.saved_tensors
+            B, K, N, d = ctx.dims
+            dYs = torch.empty(B, K, N, d, dtype=f32, device=dY.device)
+            call("conan_fgw_barycenter_bwd", ptr(T), ptr(_c(dY)), ptr(p), ptr(lambdas), B, K, N, d, ptr(dYs), stream_ptr())
+            return dYs, None, None, None, None, None, None, None
+        if dY is None and dC is None:
             return (None,) * 8
-        T, p, lambdas = ctx.saved_tensors
+        T, p, lambdas, Ys, Cs, Y, C = ctx.saved_tensors
         B, K, N, d = ctx.dims
-        dYs = torch.empty(B, K, N, d, dtype=f32, device=dY.device)
-        call("conan_fgw_barycenter_bwd", ptr(T), ptr(_c(dY)), ptr(p), ptr(lambdas), B, K, N, d, ptr(dYs), stream_ptr())
-        return dYs, None, None, None, None, None, None, None
+        w = ctx.want
+        loss, fs, ff = ctx.flags
+        dev = T.device
+        new = lambda want, *shape: torch.empty(*shape, dtype=f32, device=dev) if want else None
+        dYs, dCs = new(w["Ys"], B, K, N, d), new(w["Cs"], B, K, N, N)
+        dp = torch.empty_like(p) if w["p"] else None
+        dlam = torch.empty_like(lambdas) if w["lam"] else None
+        dinit_C, dinit_Y = new(w["init_C"], B, N, N), new(w["init_Y"], B, N, d)
+        ws = torch.empty(int(lib().conan_fgw_barycenter_bwd_full_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
+        opt = lambda t: ptr(_c(t)) if t is not None else None
+        call("conan_fgw_barycenter_bwd_full", ptr(T), ptr(Ys), ptr(Cs), ptr(Y), ptr(C), opt(dY), opt(dC), ptr(p), ptr(lambdas), B, K, N, d,
+             loss, fs, ff, ptr(dYs), ptr(dCs), ptr(dp), ptr(dlam), ptr(dinit_C), ptr(dinit_Y), ptr(ws), stream_ptr())
+        return dYs, dCs, None, dp, dlam, dinit_C, dinit_Y, None
 
 
 def fgw_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, p: Optional[Tensor] = None,
@@ -973,7 +1011,9 @@ def fgw_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, 
                            **params):
     """B independent FGW barycenters.  Ys [B,K,N,d], Cs [B,K,N,N] -> Y [B,N,d], C [B,N,N], T [B,K,N,N], info [B,4], errs [B,2,max_iter]
     (+ T_iter [max_iter,B,K,N,N] with keep_iterates=True: the couplings after every outer iteration, barycenter.py:196).
-    Gradient flows to Ys only (through the final couplings as constants), like the reference.
+    Gradients flow through the last update steps with the final couplings held constant, like the reference (barycenter.py:120): Y to Ys,
+    p and lambdas (to init_Y instead of Ys under fixed_features); C to Cs, p and lambdas (to init_C under fixed_structure).  ps gets none.
+    With only Ys requiring grad (every model) C is non-differentiable and the backward is conan_fgw_barycenter_bwd alone.
     `adjacency=graph` (a RadiusGraph with B * K conformer graphs, Cs=None): the input structures are to_dense_adj of those graphs, read by the
     coupling kernels from the ragged neighbour lists — no [B,K,N,N] tensor exists (what the models do).
     `solver` = "PGD" (default: the models' solver), "PPA" or "BAPG" — the reference's three coupling solvers (bregman.py:8-67); info[:, 3] bit 2

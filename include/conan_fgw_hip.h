@@ -609,6 +609,21 @@ int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, c
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,
                              int N, int d, float *dYs, void *stream);
 
+/* The full backward of the block (fgw_grad.hip): gradients of Y / C with respect to every input the reference's last update steps
+ * differentiate (update_feature_matrix / update_square_loss / update_kl_loss, utils.py:67-95; init_Y / init_C under fixed_features /
+ * fixed_structure, barycenter.py:56-80), the couplings T held constant.  Shapes as conan_fgw_barycenter_fwd: Ys / dYs [B,K,N,d],
+ * Cs / dCs / T [B,K,N,N], Y / dY / init_Y / dinit_Y [B,N,d], C / dC / init_C / dinit_C [B,N,N], p / dp [B,N], lambdas / dlambdas [K]
+ * (summed over the batch in a fixed order; no atomics).  loss_fun 0 = square, 1 = KL.  dY / dC may be NULL (zero); every output may be
+ * NULL (not wanted).  Needs: Cs for dCs, p for dp; Ys (feature term) and Cs (structure term) for dlambdas; Y / C for dp; C for the KL
+ * structure term.  dYs is refused under fixed_features, dCs under fixed_structure, dinit_Y / dinit_C without them (CONAN_E_BADARG, no
+ * launch).  With dYs the only output, the call is conan_fgw_barycenter_bwd (same launch, same bits).
+ * Workspace: conan_fgw_barycenter_bwd_full_workspace_bytes (needed for dlambdas, and for dCs / dlambdas above N = 112). */
+long long conan_fgw_barycenter_bwd_full_workspace_bytes(int B, int K, int N, int d);
+int conan_fgw_barycenter_bwd_full(const float *T, const float *Ys, const float *Cs, const float *Y, const float *C, const float *dY,
+                                  const float *dC, const float *p, const float *lambdas, int B, int K, int N, int d, int loss_fun,
+                                  int fixed_structure, int fixed_features, float *dYs, float *dCs, float *dp, float *dlambdas,
+                                  float *dinit_C, float *dinit_Y, void *workspace, void *stream);
+
 /* F_bary readout of _compute_barycenter: out[b*K + k, :] = sum_i post(Y[b])[i, :] for k < K
  * (schnet_no_sum.py:308-312).  mode 0 = SchNet (post = identity); mode 1 = ViSNet (NaN guard -> zeros, then column
  * L2 normalisation over the N rows, visnet.py:233-242). */
