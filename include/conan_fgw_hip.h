@@ -422,7 +422,10 @@ int conan_scale_channels_add(const float *v, const float *w, const float *add, l
 /* vec_dot[a,c] = sum_sp vp[a,sp,c] * vp[a,sp,H+c], vp = vec_proj(vec) [n,3,3H] (:605-607). */
 int conan_visnet_vecdot(const float *vp, int n, int H, float *out, void *stream);
 /* ViS_MP.message (scalar half) + aggregate (:632-645, :671): attn_h = SiLU(sum_{c in head} q_i k_j dk_e) * C(r_e);
- * vmsg[e,:] = v_j * dv_e * attn_h;  xagg[i,:] = sum_{e in row i} vmsg[e,:].  H <= 64 or H == 128.
+ * vmsg[e,:] = v_j * dv_e * attn_h;  xagg[i,:] = sum_{e in row i} vmsg[e,:].
+ * Shapes (the same rule in conan_visnet_attn_message_bwd): H % num_heads != 0 is CONAN_E_BADARG; with hd = H / num_heads, supported are H a multiple of 128 with
+ * hd a power of two in 4 .. 128, H == 128 with hd twice a power of two, and H <= 64 with hd a power of two; everything else returns CONAN_E_UNSUPPORTED and
+ * writes nothing.  n == 0 returns CONAN_OK and writes nothing.
  * pre_act != 0: dk / dv are the PRE-activations of dk_proj / dv_proj (:623-624) and act (SiLU) is applied as they are loaded — the
  * activated [E,H] tensors then never exist in HBM (the backward returns the gradients w.r.t. the pre-activations, likewise). */
 int conan_visnet_attn_message(const float *q, const float *k, const float *v, const float *dk, const float *dv,
