@@ -1107,258 +1107,213 @@ inline size_t big_lds(int N, bool c2_bytes) {
 }
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
+// Every region of the caller's workspace, in order (the table is in DESIGN.md, "FGW workspace"); total = 0 for a shape or a code that the
+// entry points refuse.  The size queries return `total`, the solve takes every pointer from the offsets: there is no second description.
+FgwWorkspace fgw_workspace(int B, int K, int N, int d, bool ragged, int solver, int symmetric) {
+    FgwWorkspace w{};
+    if (B <= 0 || K <= 0 || N <= 0 || d <= 0 || solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return w;
+    const size_t NN = (size_t)N * N, NP = (size_t)N * pitch_of(N), BK = (size_t)B * K;
+    size_t end = 0;
+    auto region = [&](size_t bytes) { const size_t at = end; end += bytes; return at; };
+    w.Cw = region(al256((size_t)B * NN * 8));                       // (the first five regions start 256-byte aligned)
+    w.Yw = region(al256((size_t)B * N * d * 8));
+    w.active = region(al256((size_t)B * 16));                       // [parity][features | structure][B] ints (fgw_active)
+    w.scratch = region(al256(BK * coupling_scratch_stride(NP)));    // coupling scratch (global mode)
+    w.order = region(al256((size_t)B * NP * 16));                   // [B] ints (FgwAdj.order), then unused padding: the queries' numbers are public
+    w.Ypart = region(BK * N * d * sizeof(fgw_part_t));
+    w.Cpart = region(BK * NN * sizeof(fgw_part_t));
+    end = (end + 15) & ~(size_t)15;
+    w.zvec = region(BK * 2 * N * 8);
+    w.yvec = region((size_t)B * 2 * N * 8);
+    w.redo = region(BK * 4 + 512);                                  // [B,K] ints, then 512 bytes of slack
+    w.dense = region(ragged ? al256(BK * NN * sizeof(float)) : 0);  // ragged input: [B,K,N,N] fp32 (FgwAdj.dense)
+    w.asym = region(solver == 2 && symmetric != 1 ? al256(conan_fgw_bapg_asym_scratch_bytes(B, K, N)) : 0);
+    w.total = end;
+    return w;
+}
+template <class T>
+inline T *ws_at(void *workspace, size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + offset); }
+
+// What one solve launches, decided once before the outer loop.
+enum class FgwPath {
+    Small,        // N <= 64, PGD, symmetric: the register-resident kernels of fgw_small.hip (they also initialise)
+    Big,          // N > 64, PGD, symmetric, square loss: k_fgw_coupling_big, then k_fgw_coupling<SECOND> for whatever it handed back
+    General,      // k_fgw_coupling<MODE, KL, GEN_NW, false, PPA, ASYM>: PGD / PPA, any symmetric code, any N
+    Bapg          // solver = 2: k_fgw_coupling_bapg (fgw_bapg.hip)
+};
+struct FgwPlan {
+    FgwPath path;
+    int mode;                   // k_fgw_coupling: the four matrices in LDS (2), only the Sinkhorn kernel matrix (1), all in the global scratch (0)
+    size_t lds_bytes;
+    bool kl, ppa, asym;
+    bool y_from_t;              // N <= 64: the update kernel forms the feature contributions T_s Z_s itself; the coupling kernels then skip that product
+    size_t big_bytes;           // k_fgw_coupling_big: its LDS, C2 as bytes, the 128-register build, size-ordered dealing
+    bool big_u8, big_wpc2, big_ordered;
+};
+
+template <int M>
+void launch_general(const FgwCall &c, const FgwPlan &pl, int outer, int y_zero, const int *only) {
+    auto go = [&](auto kernel, int blocks) {
+        launch_lds(kernel, blocks, 64 * GEN_NW, pl.lds_bytes, c.s, c.Ys, c.Cs, c.ps, c.p, c.D, c.prm, outer, y_zero | (c.symmetric < 0 ? 2 : 0), c.Cw,
+                   c.Yw, c.active, c.T, c.info, c.scratch, c.Ypart, c.Cpart, only, c.adj);      // (symmetric=None travels in bit 1 of y_zero)
+    };
+    // SECOND exists behind the big kernel only: square loss, PGD, symmetric
+    if (only) go(k_fgw_coupling<M, false, GEN_NW, true>, (c.D.B * c.D.K + 63) / 64);
+    else with_flags([&](auto KL, auto PPA, auto ASYM) { go(k_fgw_coupling<M, KL.value, GEN_NW, false, PPA.value, ASYM.value>, c.D.B * c.D.K); },
+                    pl.kl, pl.ppa, pl.asym);
+}
+
+// The one host driver of every forward entry point: PGD, PPA and BAPG, symmetric or not, dense or ragged, any N.
+int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
+                 const float *init_Y, int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter,
+                 int *info, float *errs, void *workspace, void *stream, FgwAdj adj, int solver = 0, int symmetric = 1) {
+    if (solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
+    if (!Ys || !(Cs || (adj.gptr && adj.rowptr && adj.col && adj.tgt)) || !params || !Y || !C || !T || !info || !errs || !workspace || B <= 0 || K <= 0 || N <= 0 || d <= 0)
+        return CONAN_E_BADARG;
+    if (params->max_iter <= 0 || params->num_iter_max <= 0) return CONAN_E_BADARG;
+    if (params->fixed_features && !init_Y) return CONAN_E_BADARG;      // barycenter.py:70-72
+    if (params->loss_fun != 0 && params->loss_fun != 1) return CONAN_E_BADARG;
+    const bool ragged = adj.rowptr != nullptr, small = conan_fgw_small_supported(N, d), kl = params->loss_fun != 0;
+    const bool model = solver == 0 && symmetric == 1;      // the models' solve; every other one runs the general kernels on dense structure
+    const FgwWorkspace w = fgw_workspace(B, K, N, d, ragged, solver, symmetric);
+    const size_t NN = (size_t)N * N, NP = (size_t)N * pitch_of(N);
+    FgwCall c{};
+    c.Ys = Ys; c.Cs = Cs; c.ps = ps; c.p = p; c.lambdas = lambdas; c.init_C = init_C; c.init_Y = init_Y;
+    c.D = FgwDims{B, K, N, d, pitch_of(N)};
+    c.prm = *params;
+    c.adj = adj;
+    c.symmetric = symmetric;
+    c.Y = Y; c.C = C; c.T = T; c.info = info; c.errs = errs;
+    c.Cw = ws_at<double>(workspace, w.Cw); c.Yw = ws_at<double>(workspace, w.Yw); c.active = ws_at<int>(workspace, w.active);
+    c.scratch = ws_at<char>(workspace, w.scratch); c.scratch_stride = coupling_scratch_stride(NP);
+    c.Ypart = ws_at<fgw_part_t>(workspace, w.Ypart); c.Cpart = ws_at<fgw_part_t>(workspace, w.Cpart);
+    c.redo = ws_at<int>(workspace, w.redo);
+    c.asym_scratch = ws_at<char>(workspace, w.asym);
+    c.s = as_stream(stream);
+    if (ragged) {
+        // The kernels with a ragged load stage are the square-loss ones of the model path (k_fgw_coupling_fast for N <= 64, k_fgw_coupling_big
+        // above); any other shape / loss / solver expands the graphs into the dense scratch once and continues on the dense path.
+        c.prm.cs_small_int = 1;                             // adjacency counts are small integers by construction
+        c.adj.dense = ws_at<float>(workspace, w.dense);
+        if (!(model && !kl && (small ? conan_fgw_fast_supported(N, d, 1) : big_lds(N, true) <= LDS_LIMIT))) {
+            k_adj_dense<<<B * K, 256, 0, c.s>>>(c.adj, N);
+            c.Cs = c.adj.dense;
+            c.adj.rowptr = nullptr;
+        }
+    }
+    if (!model) c.adj = FgwAdj{};
+    // size-ordered dealing of the coupling workgroups (speed only): k_fgw_coupling_fast and k_fgw_coupling_big
+    if (c.adj.rowptr && !kl && (B & 7) == 0 && B <= 4096 && (small || (CONAN_FGW_BIG_ORDER && big_lds(N, true) <= LDS_LIMIT)))
+        c.adj.order = ws_at<int>(workspace, w.order);
+
+    FgwPlan pl{};
+    pl.kl = kl; pl.ppa = solver == 1; pl.asym = symmetric != 1;
+    pl.big_u8 = c.prm.cs_small_int != 0;
+    pl.big_bytes = big_lds(N, pl.big_u8);
+    pl.path = solver == 2 ? FgwPath::Bapg : model && small ? FgwPath::Small : model && !kl && pl.big_bytes <= LDS_LIMIT ? FgwPath::Big : FgwPath::General;
+    const size_t lc = coupling_lds(N), vec_c = (size_t)((6 + 2 * GEN_NW) * N + 16) * 8, mr_bytes = NP * 8;
+    pl.mode = lc <= LDS_LIMIT ? 2 : (vec_c + mr_bytes <= LDS_LIMIT ? 1 : 0);
+    pl.lds_bytes = pl.mode == 2 ? lc : vec_c + (pl.mode == 1 ? mr_bytes : 0);
+    pl.big_wpc2 = BIG_WPC2 && (B * K <= CONAN_FGW_WPC2_MAX || (CONAN_FGW_WPC2_ORDERED && c.adj.order));      // the 128-register build (see WPC above)
+    pl.big_ordered = c.adj.order != nullptr && (B * K & 7) == 0 && pl.big_wpc2 && pl.big_u8;      // (an order implies the byte layout and the two-per-CU build)
+    pl.y_from_t = pl.path == FgwPath::Small && !c.prm.fixed_features && conan_fgw_update_chunk(K, N, d, B) > 0;
+    if (pl.path == FgwPath::Small) { c.zvec = ws_at<double>(workspace, w.zvec); c.yvec = ws_at<double>(workspace, w.yvec); }
+
+    if (pl.path == FgwPath::Small) conan_fgw_small_prepare(c);
+    else k_fgw_init<<<B, 256, 0, c.s>>>(c.Cs, init_C, init_Y, c.D, c.prm.max_iter, c.Cw, c.Yw, c.active, info, errs, Y, C, c.adj);
+    const FastConst fc = fast_const(c.prm, N);
+    for (int outer = 0; outer < c.prm.max_iter; ++outer) {
+        const int y_zero = (outer == 0 && !init_Y) ? 1 : 0;
+        const int *only = nullptr;
+        if (pl.path == FgwPath::Big) {
+            // the round-3 kernel first (fp32 kernel matrix in LDS), then k_fgw_coupling over the same grid for whatever it handed back
+            // (redo[b, s]; an early-exit launch otherwise).  ORD exists with U8 and two per CU only.
+            auto big = [&](auto kernel) {
+                launch_lds(kernel, B * K, 64 * GEN_NW, pl.big_bytes, c.s, c.Ys, c.Cs, c.ps, c.p, c.D, c.prm, fc, outer, y_zero, c.Cw, c.Yw, c.active, c.T,
+                           c.info, c.scratch, c.Ypart, c.Cpart, c.redo, c.adj);
+            };
+            if (pl.big_ordered) big(k_fgw_coupling_big<GEN_NW, true, 2, true>);
+            else if (pl.big_u8) { if (pl.big_wpc2) big(k_fgw_coupling_big<GEN_NW, true, 2, false>); else big(k_fgw_coupling_big<GEN_NW, true, 3, false>); }
+            else { if (pl.big_wpc2) big(k_fgw_coupling_big<GEN_NW, false, 2, false>); else big(k_fgw_coupling_big<GEN_NW, false, 3, false>); }
+            only = c.redo;
+        }
+        if (pl.path == FgwPath::Small) conan_fgw_small_coupling(c, outer, y_zero, pl.y_from_t ? nullptr : c.Ypart);
+        else if (pl.path == FgwPath::Bapg) conan_fgw_bapg_coupling(c, outer, y_zero);
+        else if (pl.mode == 2) launch_general<2>(c, pl, outer, y_zero, only);
+        else if (pl.mode == 1) launch_general<1>(c, pl, outer, y_zero, only);
+        else launch_general<0>(c, pl, outer, y_zero, only);
+        if (T_iter)      // log["Ts_iter"] (barycenter.py:196): a snapshot per outer iteration, only when the caller asks for the log
+            (void)hipMemcpyAsync(T_iter + (size_t)outer * B * K * NN, T, (size_t)B * K * NN * sizeof(float), hipMemcpyDeviceToDevice, c.s);
+        conan_fgw_small_update(c, outer, pl.y_from_t);
+    }
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+inline FgwAdj ragged_adj(const int *graph_ptr, const int *rowptr, const int *col, const int *tgt) {
+    return FgwAdj{graph_ptr, rowptr, col, tgt, nullptr, nullptr};
+}
+const FgwAdj DENSE_ADJ{};
+
 }  // namespace
 
 extern "C" {
 
-long long conan_fgw_workspace_bytes(int B, int K, int N, int d) {
-    if (B <= 0 || K <= 0 || N <= 0 || d <= 0) return 0;
-    const size_t NN = (size_t)N * N, NP = (size_t)N * pitch_of(N);
-    size_t bytes = 0;
-    bytes += al256((size_t)B * NN * 8);               // Cw          (every region starts 256-byte aligned)
-    bytes += al256((size_t)B * N * d * 8);            // Yw
-    bytes += al256((size_t)B * 16);                   // active: [parity][features | structure][B] (fgw_active)
-    bytes += al256((size_t)B * K * coupling_scratch_stride(NP));    // coupling scratch (global mode)
-    bytes += al256((size_t)B * NP * 16);              // update scratch (global mode)
-    bytes += conan_fgw_small_part_bytes(B, K, N, d);   // per-graph update contributions (register-resident path)
-    return (long long)bytes;
+// The four size queries: one layout (fgw_workspace), asked for its total.
+long long conan_fgw_workspace_bytes(int B, int K, int N, int d) { return (long long)fgw_workspace(B, K, N, d, false, 0, 1).total; }
+long long conan_fgw_workspace_bytes_ragged(int B, int K, int N, int d) { return (long long)fgw_workspace(B, K, N, d, true, 0, 1).total; }
+long long conan_fgw_workspace_bytes_sym(int B, int K, int N, int d, int solver, int symmetric) {
+    return (long long)fgw_workspace(B, K, N, d, false, solver, symmetric).total;
+}
+long long conan_fgw_workspace_bytes_ragged_sym(int B, int K, int N, int d, int solver, int symmetric) {
+    return (long long)fgw_workspace(B, K, N, d, true, solver, symmetric).total;
 }
 
-// solver = 1 (PPA) / 2 (BAPG), or symmetric != 1 (False = 0, None = -1) with any solver: the outer loop of fgw_fwd_impl with the general
-// initialisation and update kernels and the solver's coupling kernel — PGD / PPA: k_fgw_coupling<MODE, KL, GEN_NW, false, PPA, ASYM>; BAPG:
-// k_fgw_coupling_bapg (fgw_bapg.hip).  Dense structure only (the caller expands ragged input first); no fast / big / register-resident path,
-// no padded-node merge (flags bit 1 stays 0).  symmetric=None reaches the kernels as bit 1 of y_zero.
-static int fgw_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
-                          const float *init_Y, FgwDims D, const conan_fgw_params &prm, float *Y, float *C, float *T, float *T_iter, int *info,
-                          float *errs, double *Cw, double *Yw, int *active, char *sc_c, fgw_part_t *Ypart, fgw_part_t *Cpart, int solver,
-                          hipStream_t s, int symmetric = 1, char *asym_scratch = nullptr) {
-    const int B = D.B, K = D.K, N = D.N;
-    const size_t NN = (size_t)N * N, NP = (size_t)N * D.P;
-    const bool kl = prm.loss_fun != 0;
-    const FgwAdj none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    k_fgw_init<<<B, 256, 0, s>>>(Cs, init_C, init_Y, D, prm.max_iter, Cw, Yw, active, info, errs, Y, C, none);
-    const size_t lc = coupling_lds(N), vec_c = (size_t)((6 + 2 * GEN_NW) * N + 16) * 8, mr_bytes = NP * 8;
-    const int mode = lc <= LDS_LIMIT ? 2 : (vec_c + mr_bytes <= LDS_LIMIT ? 1 : 0);
-    const size_t lds_bytes = mode == 2 ? lc : vec_c + (mode == 1 ? mr_bytes : 0);
-    for (int outer = 0; outer < prm.max_iter; ++outer) {
-        const int y_zero = (outer == 0 && !init_Y) ? 1 : 0;
-        if (solver == 2) {
-            conan_fgw_bapg_coupling(Ys, Cs, ps, p, D, prm, outer, y_zero, Cw, Yw, active, T, info, sc_c, coupling_scratch_stride(NP), Ypart, Cpart, s,
-                                    symmetric, asym_scratch);
-        } else {
-#define CONAN_GEN(M, KLV, PPAV, ASV)                                                                                                \
-    do {                                                                                                                            \
-        if (lds_bytes > 64 * 1024)                                                                                                  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling<M, KLV, GEN_NW, false, PPAV, ASV>),            \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                                  \
-        k_fgw_coupling<M, KLV, GEN_NW, false, PPAV, ASV><<<B * K, 64 * GEN_NW, lds_bytes, s>>>(Ys, Cs, ps, p, D, prm, outer,            \
-            y_zero | (ASV && symmetric < 0 ? 2 : 0), Cw, Yw, active, T, info, sc_c, Ypart, Cpart, nullptr, none);                   \
-    } while (0)
-#define CONAN_MODES(PPAV, ASV)                                                                                                      \
-    do {                                                                                                                            \
-        if (mode == 2) { if (kl) CONAN_GEN(2, true, PPAV, ASV); else CONAN_GEN(2, false, PPAV, ASV); }                              \
-        else if (mode == 1) { if (kl) CONAN_GEN(1, true, PPAV, ASV); else CONAN_GEN(1, false, PPAV, ASV); }                         \
-        else { if (kl) CONAN_GEN(0, true, PPAV, ASV); else CONAN_GEN(0, false, PPAV, ASV); }                                        \
-    } while (0)
-            if (symmetric == 1) CONAN_MODES(true, false);                // (solver 1: PGD with symmetric = 1 takes the model path)
-            else if (solver == 1) CONAN_MODES(true, true);
-            else CONAN_MODES(false, true);
-#undef CONAN_MODES
-#undef CONAN_GEN
-        }
-        if (T_iter)
-            (void)hipMemcpyAsync(T_iter + (size_t)outer * B * K * NN, T, (size_t)B * K * NN * sizeof(float), hipMemcpyDeviceToDevice, s);
-        conan_fgw_small_update(p, lambdas, D, prm, outer, Ypart, Cpart, Cw, Yw, active, info, errs, Y, C, nullptr, nullptr, nullptr, s);
-    }
-    CONAN_LAUNCH_CHECK();
-    return CONAN_OK;
-}
-
-static int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
-                        const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                        const conan_fgw_params *params_in, float *Y, float *C, float *T, float *T_iter, int *info,
-                        float *errs, void *workspace, void *stream, FgwAdj adj, int solver = 0, int symmetric = 1) {
-    if (solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
-    if (!Ys || (!Cs && !adj.rowptr) || !params_in || !Y || !C || !T || !info || !errs || !workspace || B <= 0 || K <= 0 || N <= 0 || d <= 0)
-        return CONAN_E_BADARG;
-    conan_fgw_params params_v = *params_in;
-    if (adj.rowptr) params_v.cs_small_int = 1;                          // adjacency counts are small integers by construction
-    const conan_fgw_params *params = &params_v;
-    if (params->max_iter <= 0 || params->num_iter_max <= 0) return CONAN_E_BADARG;
-    if (params->fixed_features && !init_Y) return CONAN_E_BADARG;      // barycenter.py:70-72
-    hipStream_t s = as_stream(stream);
-    FgwDims D{B, K, N, d, pitch_of(N)};
-    const size_t NN = (size_t)N * N, NP = (size_t)N * D.P;
-    char *w = static_cast<char *>(workspace);
-    double *Cw = reinterpret_cast<double *>(w); w += al256((size_t)B * NN * 8);
-    double *Yw = reinterpret_cast<double *>(w); w += al256((size_t)B * N * d * 8);
-    int *active = reinterpret_cast<int *>(w); w += al256((size_t)B * 16);
-    char *sc_c = w; w += al256((size_t)B * K * coupling_scratch_stride(NP));
-    int *order_ws = reinterpret_cast<int *>(w);      // [B] ints at the head of the reserved region: FgwAdj.order
-    w += al256((size_t)B * NP * 16);        // (reserved)
-    fgw_part_t *Ypart = reinterpret_cast<fgw_part_t *>(w);
-    fgw_part_t *Cpart = Ypart + (size_t)B * K * N * d;
-    double *zvec = reinterpret_cast<double *>(w + conan_fgw_part_offset(B, K, N, d));      // [B,K,2N]  |z_j|^2, r2_j      (register-resident path)
-    double *yvec = zvec + (size_t)B * K * 2 * N;            // [B,2N]    |y_i|^2, r1_i
-    int *redo = reinterpret_cast<int *>(yvec + (size_t)B * 2 * N);      // [B,K]  couplings the round-3 kernel hands back to the exact path
-    const bool small = conan_fgw_small_supported(N, d);
-    const bool kl = params->loss_fun != 0;
-    if (params->loss_fun != 0 && params->loss_fun != 1) return CONAN_E_BADARG;
-    // symmetric != 1: the asymmetric BAPG solve's own scratch (N > 64) sits behind the whole workspace (conan_fgw_workspace_bytes_sym / _ragged_sym)
-    char *asym_scratch = static_cast<char *>(workspace) + (adj.rowptr ? conan_fgw_workspace_bytes_ragged(B, K, N, d) : conan_fgw_workspace_bytes(B, K, N, d));
-    if (adj.rowptr) {
-        // ragged structure: the dense scratch sits behind the regular workspace (conan_fgw_workspace_bytes_ragged).  The kernels with a ragged
-        // load stage are the square-loss ones of the model path (k_fgw_coupling_fast for N <= 64, k_fgw_coupling_big above); any other shape /
-        // loss expands the graphs into the scratch once and continues on the dense path.
-        adj.dense = reinterpret_cast<float *>(static_cast<char *>(workspace) + conan_fgw_workspace_bytes(B, K, N, d));
-        const bool ragged_ok = solver == 0 && symmetric == 1 && !kl && (small ? conan_fgw_fast_supported(N, d, 1) : big_lds(N, true) <= LDS_LIMIT);
-        if (!ragged_ok) {
-            k_adj_dense<<<B * K, 256, 0, s>>>(adj, N);
-            Cs = adj.dense;
-            adj.rowptr = nullptr;
-        }
-    }
-
-    if (solver != 0 || symmetric != 1)
-        return fgw_fwd_solver(Ys, Cs, ps, p, lambdas, init_C, init_Y, D, *params, Y, C, T, T_iter, info, errs, Cw, Yw, active, sc_c, Ypart, Cpart,
-                              solver, s, symmetric, asym_scratch);
-
-    // size-ordered dealing of the coupling workgroups (speed only): k_fgw_coupling_fast and k_fgw_coupling_big
-    if (adj.rowptr && !kl && (B & 7) == 0 && B <= 4096 && (small || (CONAN_FGW_BIG_ORDER && big_lds(N, true) <= LDS_LIMIT))) adj.order = order_ws;
-    if (small) conan_fgw_small_prepare(Ys, Cs, ps, p, D, *params, Cw, Yw, zvec, yvec, init_C, init_Y, active, info, errs, Y, C, adj, s);
-    else k_fgw_init<<<B, 256, 0, s>>>(Cs, init_C, init_Y, D, params->max_iter, Cw, Yw, active, info, errs, Y, C, adj);
-    const size_t lc = coupling_lds(N);
-    const bool c_lds = lc <= LDS_LIMIT;
-    const size_t vec_c = (size_t)((6 + 2 * GEN_NW) * N + 16) * 8;
-    const size_t mr_bytes = NP * 8;
-    const int mode = c_lds ? 2 : (vec_c + mr_bytes <= LDS_LIMIT ? 1 : 0);
-    const size_t lds_bytes = mode == 2 ? lc : vec_c + (mode == 1 ? mr_bytes : 0);
-#define CONAN_CPL_(M, KLV, SEC, GRID)                                                                                               \
-    do {                                                                                                                            \
-        if (lds_bytes > 64 * 1024)                                                                                                  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling<M, KLV, GEN_NW, SEC>),                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                                  \
-        k_fgw_coupling<M, KLV, GEN_NW, SEC><<<GRID, 64 * GEN_NW, lds_bytes, s>>>(Ys, Cs, ps, p, D, *params, outer, y_zero, Cw, Yw, active, T, \
-                                                                              info, sc_c, Ypart, Cpart, only, adj);                 \
-    } while (0)
-#define CONAN_CPL(M, KLV)                                                                                                           \
-    do {                                                                                                                            \
-        if (!KLV && only) CONAN_CPL_(M, false, true, (B * K + 63) / 64);                                                            \
-        else CONAN_CPL_(M, KLV, false, B * K);                                                                                      \
-    } while (0)
-    // N > 64, square loss: the round-3 kernel first (fp32 kernel matrix in LDS: three workgroups per CU), then k_fgw_coupling over the
-    // same grid for whatever it handed back (redo[b, s]; an early-exit launch otherwise)
-    const bool c2b = params->cs_small_int != 0;
-    const size_t lb = big_lds(N, c2b);
-    const bool big = !small && !kl && lb <= LDS_LIMIT;
-    const FastConst fc = fast_const(*params, N);
-    // N <= 64: the update kernel forms the feature contributions T_s Z_s itself (fgw_small.hip); the coupling kernels then skip that product
-    const bool y_from_t = small && !params->fixed_features && conan_fgw_update_chunk(K, N, d, B) > 0;
-    fgw_part_t *Ypart_c = y_from_t ? nullptr : Ypart;
-    for (int outer = 0; outer < params->max_iter; ++outer) {
-        const int y_zero = (outer == 0 && !init_Y) ? 1 : 0;
-        const int *only = nullptr;
-        if (big) {
-#define CONAN_BIG(U8, WPC, ORD)                                                                                                     \
-    do {                                                                                                                            \
-        if (lb > 64 * 1024)                                                                                                         \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling_big<GEN_NW, U8, WPC, ORD>),                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);                                         \
-        k_fgw_coupling_big<GEN_NW, U8, WPC, ORD><<<B * K, 64 * GEN_NW, lb, s>>>(Ys, Cs, ps, p, D, *params, fc, outer, y_zero, Cw, Yw, active, T, info, sc_c, \
-                                                                                 Ypart, Cpart, redo, adj);                           \
-    } while (0)
-            const bool two_per_cu = BIG_WPC2 && (B * K <= CONAN_FGW_WPC2_MAX || (CONAN_FGW_WPC2_ORDERED && adj.order));      // the 128-register build (see WPC above)
-            const bool ordered = adj.order != nullptr && (B * K & 7) == 0 && two_per_cu && c2b;      // (an order implies the byte layout and the two-per-CU build)
-            if (ordered) CONAN_BIG(true, 2, true);
-            else if (c2b) { if (two_per_cu) CONAN_BIG(true, 2, false); else CONAN_BIG(true, 3, false); }
-            else { if (two_per_cu) CONAN_BIG(false, 2, false); else CONAN_BIG(false, 3, false); }
-#undef CONAN_BIG
-            only = redo;
-        }
-        if (small)
-            conan_fgw_small_coupling(Ys, Cs, ps, p, D, *params, outer, y_zero, Cw, Yw, active, T, info, Ypart_c, Cpart, zvec, yvec, redo, adj, s);
-        else if (mode == 2) { if (kl) CONAN_CPL(2, true); else CONAN_CPL(2, false); }
-        else if (mode == 1) { if (kl) CONAN_CPL(1, true); else CONAN_CPL(1, false); }
-        else { if (kl) CONAN_CPL(0, true); else CONAN_CPL(0, false); }
-        if (T_iter)      // log["Ts_iter"] (barycenter.py:196): a snapshot per outer iteration, only when the caller asks for the log
-            (void)hipMemcpyAsync(T_iter + (size_t)outer * B * K * NN, T, (size_t)B * K * NN * sizeof(float), hipMemcpyDeviceToDevice, s);
-        conan_fgw_small_update(p, lambdas, D, *params, outer, Ypart, Cpart, Cw, Yw, active, info, errs, Y, C, small ? yvec : nullptr, y_from_t ? T : nullptr, y_from_t ? Ys : nullptr, s);
-    }
-#undef CONAN_CPL
-#undef CONAN_CPL_
-    CONAN_LAUNCH_CHECK();
-    return CONAN_OK;
-}
-
+// The six forward entry points: fgw_fwd_impl with dense (Cs) or ragged (the four lists) structure; it refuses a null among them.
 int conan_fgw_barycenter_fwd(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
                              const float *init_C, const float *init_Y, int B, int K, int N, int d,
                              const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
                              float *errs, void *workspace, void *stream) {
-    if (!Cs) return CONAN_E_BADARG;
-    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        FgwAdj{nullptr, nullptr, nullptr, nullptr, nullptr});
-}
-
-long long conan_fgw_workspace_bytes_ragged(int B, int K, int N, int d) {
-    const long long w = conan_fgw_workspace_bytes(B, K, N, d);
-    return w <= 0 ? 0 : w + (long long)al256((size_t)B * K * N * N * sizeof(float));
+    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream, DENSE_ADJ);
 }
 
 int conan_fgw_barycenter_fwd_ragged(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt, const float *ps,
                                     const float *p, const float *lambdas, const float *init_C, const float *init_Y, int B, int K, int N, int d,
                                     const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info, float *errs,
                                     void *workspace, void *stream) {
-    if (!graph_ptr || !rowptr || !col || !tgt) return CONAN_E_BADARG;
     return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        FgwAdj{graph_ptr, rowptr, col, tgt, nullptr});
+                        ragged_adj(graph_ptr, rowptr, col, tgt));
 }
 
 int conan_fgw_barycenter_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
                                     const float *init_C, const float *init_Y, int B, int K, int N, int d,
                                     const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
                                     float *errs, void *workspace, void *stream, int solver) {
-    if (!Cs) return CONAN_E_BADARG;
-    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        FgwAdj{nullptr, nullptr, nullptr, nullptr, nullptr}, solver);
+    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream, DENSE_ADJ, solver);
 }
 
 int conan_fgw_barycenter_fwd_ragged_solver(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
                                            const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
                                            int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T,
                                            float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver) {
-    if (!graph_ptr || !rowptr || !col || !tgt) return CONAN_E_BADARG;
     return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        FgwAdj{graph_ptr, rowptr, col, tgt, nullptr}, solver);
-}
-
-long long conan_fgw_workspace_bytes_sym(int B, int K, int N, int d, int solver, int symmetric) {
-    const long long w = conan_fgw_workspace_bytes(B, K, N, d);
-    if (w <= 0 || solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return 0;
-    return w + (solver == 2 && symmetric != 1 ? (long long)al256(conan_fgw_bapg_asym_scratch_bytes(B, K, N)) : 0);
-}
-
-long long conan_fgw_workspace_bytes_ragged_sym(int B, int K, int N, int d, int solver, int symmetric) {
-    const long long w = conan_fgw_workspace_bytes_ragged(B, K, N, d);
-    if (w <= 0 || solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return 0;
-    return w + (solver == 2 && symmetric != 1 ? (long long)al256(conan_fgw_bapg_asym_scratch_bytes(B, K, N)) : 0);
+                        ragged_adj(graph_ptr, rowptr, col, tgt), solver);
 }
 
 int conan_fgw_barycenter_fwd_sym(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
                                  const float *init_C, const float *init_Y, int B, int K, int N, int d,
                                  const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
                                  float *errs, void *workspace, void *stream, int solver, int symmetric) {
-    if (!Cs) return CONAN_E_BADARG;
-    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        FgwAdj{nullptr, nullptr, nullptr, nullptr, nullptr}, solver, symmetric);
+    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream, DENSE_ADJ, solver,
+                        symmetric);
 }
 
 int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
                                         const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
                                         int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T,
                                         float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver, int symmetric) {
-    if (!graph_ptr || !rowptr || !col || !tgt) return CONAN_E_BADARG;
     return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        FgwAdj{graph_ptr, rowptr, col, tgt, nullptr}, solver, symmetric);
+                        ragged_adj(graph_ptr, rowptr, col, tgt), solver, symmetric);
 }
 
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,

@@ -233,31 +233,20 @@ size_t conan_fgw_bapg_asym_scratch_bytes(int B, int K, int N) {
     return conan_fgw_bapg_lds(N, true) <= BAPG_LDS_LIMIT ? 0 : (size_t)B * K * bapg_asym_stride((size_t)N * fgw_pitch(N));
 }
 
-void conan_fgw_bapg_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer,
-                             int y_zero, const double *Cw, const double *Yw, const int *active, float *Tw, int *info, char *scratch,
-                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s, int symmetric, char *asym_scratch) {
-    const bool asym = symmetric != 1;
+void conan_fgw_bapg_coupling(const FgwCall &c, int outer, int y_zero) {
+    const FgwDims &D = c.D;
+    const bool asym = c.symmetric != 1;
     const size_t full = conan_fgw_bapg_lds(D.N, asym);
     const bool lds = full <= BAPG_LDS_LIMIT;
     const size_t bytes = lds ? full : bapg_vec_bytes(D.N);
+    char *scratch = c.scratch;
+    size_t scratch_stride = c.scratch_stride;
     if (asym) {      // symmetric=None travels in bit 1 of y_zero; outside LDS the matrices sit in the asymmetric solve's own scratch
-        y_zero |= symmetric < 0 ? 2 : 0;
-        if (!lds) { scratch = asym_scratch; scratch_stride = bapg_asym_stride((size_t)D.N * D.P); }
+        y_zero |= c.symmetric < 0 ? 2 : 0;
+        if (!lds) { scratch = c.asym_scratch; scratch_stride = bapg_asym_stride((size_t)D.N * D.P); }
     }
-#define BAPG_LAUNCH(L, KLV, AS)                                                                                                      \
-    do {                                                                                                                             \
-        if (bytes > 64 * 1024)                                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling_bapg<L, KLV, BAPG_NW, AS>),                     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);                                       \
-        k_fgw_coupling_bapg<L, KLV, BAPG_NW, AS><<<D.B * D.K, 64 * BAPG_NW, bytes, s>>>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, \
-                                                                                      Tw, info, scratch, scratch_stride, Ypart, Cpart); \
-    } while (0)
-    if (asym) {
-        if (lds) { if (prm.loss_fun) BAPG_LAUNCH(true, true, true); else BAPG_LAUNCH(true, false, true); }
-        else { if (prm.loss_fun) BAPG_LAUNCH(false, true, true); else BAPG_LAUNCH(false, false, true); }
-    } else {
-        if (lds) { if (prm.loss_fun) BAPG_LAUNCH(true, true, false); else BAPG_LAUNCH(true, false, false); }
-        else { if (prm.loss_fun) BAPG_LAUNCH(false, true, false); else BAPG_LAUNCH(false, false, false); }
-    }
-#undef BAPG_LAUNCH
+    with_flags([&](auto L, auto KL, auto AS) {
+        launch_lds(k_fgw_coupling_bapg<L.value, KL.value, BAPG_NW, AS.value>, D.B * D.K, 64 * BAPG_NW, bytes, c.s, c.Ys, c.Cs, c.ps, c.p, D, c.prm,
+                   outer, y_zero, c.Cw, c.Yw, c.active, c.T, c.info, scratch, scratch_stride, c.Ypart, c.Cpart);
+    }, lds, c.prm.loss_fun != 0, asym);
 }

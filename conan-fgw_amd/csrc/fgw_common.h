@@ -1,5 +1,6 @@
 // Shared device helpers of the FGW barycenter kernels (fgw.hip: generic path, fgw_small.hip: register-resident path).
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 // Phase timing of the coupling kernels (tools/fgw_phase_profile.py builds a private library with -DCONAN_FGW_PROFILE; the product
@@ -1040,31 +1041,65 @@ __device__ __forceinline__ void mm_lds2(int M, int Nn, int Kd, const TX *__restr
         if (b_on[p]) st(b_i[p], b_j[p], bval[p]);
 }
 
+// ---- host side of the solve: fgw.hip drives (fgw_fwd_impl), fgw_small.hip and fgw_bapg.hip launch their own kernels --------------------------
+
+// Byte offsets of the regions of the caller's workspace, in this order, and the total the size queries return (fgw_workspace in fgw.hip fills
+// it, once per query and once per solve; the table is in DESIGN.md, "FGW workspace").
+struct FgwWorkspace {
+    size_t Cw, Yw, active, scratch, order, Ypart, Cpart, zvec, yvec, redo, dense, asym, total;
+};
+
+// One solve's inputs, outputs, parameters, workspace pointers and stream.  The launchers below take it by const reference plus the few values
+// that change per outer iteration, and unpack it into the kernels' argument lists at the launch site only.
+struct FgwCall {
+    const float *Ys, *Cs, *ps, *p, *lambdas, *init_C, *init_Y;
+    FgwDims D;
+    conan_fgw_params prm;
+    FgwAdj adj;
+    int symmetric;                  // 1 (True), 0 (False) or -1 (None, decided per coupling solve)
+    float *Y, *C, *T;
+    int *info;
+    float *errs;
+    double *Cw, *Yw;                // [B,N,N], [B,N,d]: the barycenter's fp64 state
+    int *active;
+    char *scratch;                  // coupling scratch (global mode): scratch_stride bytes per coupling, 28 per N x P entry
+    size_t scratch_stride;
+    fgw_part_t *Ypart, *Cpart;      // [B,K,N,d], [B,K,N,N]: per-graph update contributions
+    double *zvec, *yvec;            // [B,K,2N] |z_j|^2, r2_j and [B,2N] |y_i|^2, r1_i (register-resident path; null on every other: the update then refreshes none)
+    int *redo;                      // [B,K]: couplings the round-3 kernels hand back to the exact path
+    char *asym_scratch;             // asymmetric BAPG outside LDS: 36 bytes per N x P entry and coupling
+    hipStream_t s;
+};
+
+// kernel<<<grid, block, lds, s>>>(args...), raising the kernel's dynamic LDS limit first when the launch needs more than the default 64 KiB
+template <class... KA, class... A>
+inline void launch_lds(void (*kernel)(KA...), int grid, int block, size_t lds, hipStream_t s, A &&...args) {
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    kernel<<<grid, block, lds, s>>>(static_cast<KA>(args)...);
+}
+// run-time booleans to template flags: with_flags(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}).  Instantiates f for EVERY
+// combination: only for ladders that are complete.
+template <class F>
+inline void with_flags(F &&f) { f(); }
+template <class F, class... B>
+inline void with_flags(F &&f, bool b, B... rest) {
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
 // Launchers of the register-resident path (fgw_small.hip), N <= 64.
 bool conan_fgw_small_supported(int N, int d);
 bool conan_fgw_fast_supported(int N, int d, int small_int);
-size_t conan_fgw_small_part_bytes(int B, int K, int N, int d);
-size_t conan_fgw_part_offset(int B, int K, int N, int d);      // bytes of Ypart + Cpart (16-byte aligned): where the fp64 vectors start
 // (also initialises the molecules: the N <= 64 path launches no k_fgw_init)
-void conan_fgw_small_prepare(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm,
-                             double *Cw, double *Yw, double *zvec, double *yvec, const float *init_C, const float *init_Y, int *active, int *info,
-                             float *errs, float *Yout, float *Cout, FgwAdj adj, hipStream_t s);
-void conan_fgw_small_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D,
-                              conan_fgw_params prm, int outer, int y_zero, const double *Cw, const double *Yw,
-                              const int *active, float *Tw, int *info, fgw_part_t *Ypart, fgw_part_t *Cpart, const double *zvec,
-                              const double *yvec, int *redo, FgwAdj adj, hipStream_t s);
-// yvec (nullable): the register-resident path's per-molecule vectors, refreshed after every update
-void conan_fgw_small_update(const float *pb, const float *lambdas, FgwDims D, conan_fgw_params prm, int outer,
-                            const fgw_part_t *Ypart, const fgw_part_t *Cpart, double *Cw, double *Yw, int *active, int *info,
-                            float *errs, float *Yout, float *Cout, double *yvec, const float *Tw, const float *Ys, hipStream_t s);
+void conan_fgw_small_prepare(const FgwCall &c);
+// Ypart (nullable): null when the update kernel forms the feature contributions from the couplings itself (y_from_t)
+void conan_fgw_small_coupling(const FgwCall &c, int outer, int y_zero, fgw_part_t *Ypart);
+// the update of every path.  y_from_t: form T_s Z_s here from the couplings (conan_fgw_update_chunk > 0)
+void conan_fgw_small_update(const FgwCall &c, int outer, bool y_from_t);
 int conan_fgw_update_chunk(int K, int N, int d, int B);
-// solver="BAPG" coupling solve (fgw_bapg.hip): one workgroup per (molecule, input graph), any N; `scratch` + cid * scratch_stride is the
-// coupling's slice of the global scratch (28 bytes per N x P entry), used when its matrices do not fit in LDS.
-// symmetric = 1 (True), 0 (False) or -1 (None, decided per coupling solve); symmetric != 1 outside LDS (N > 64) runs in `asym_scratch`,
-// conan_fgw_bapg_asym_scratch_bytes(B, K, N) bytes (36 bytes per N x P entry and coupling; 0 when the matrices fit in LDS).
+// solver="BAPG" coupling solve (fgw_bapg.hip): one workgroup per (molecule, input graph), any N; the coupling's slice of c.scratch is used
+// when its matrices do not fit in LDS.  c.symmetric != 1 outside LDS (N > 64) runs in c.asym_scratch, conan_fgw_bapg_asym_scratch_bytes(B, K, N)
+// bytes (0 when the matrices fit in LDS).
 size_t conan_fgw_bapg_lds(int N, bool asym = false);
 size_t conan_fgw_bapg_asym_scratch_bytes(int B, int K, int N);
-void conan_fgw_bapg_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer,
-                             int y_zero, const double *Cw, const double *Yw, const int *active, float *Tw, int *info, char *scratch,
-                             size_t scratch_stride, fgw_part_t *Ypart, fgw_part_t *Cpart, hipStream_t s, int symmetric = 1,
-                             char *asym_scratch = nullptr);
+void conan_fgw_bapg_coupling(const FgwCall &c, int outer, int y_zero);

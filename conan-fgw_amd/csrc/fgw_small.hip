@@ -1240,43 +1240,32 @@ inline size_t small_lds(int N, int d) {
 
 bool conan_fgw_small_supported(int N, int d) { return N <= 64 && small_lds(N, d) <= 160 * 1024; }
 
-size_t conan_fgw_part_offset(int B, int K, int N, int d) {
-    return (((size_t)B * K * N * d + (size_t)B * K * N * N) * sizeof(fgw_part_t) + 15) & ~(size_t)15;
-}
-size_t conan_fgw_small_part_bytes(int B, int K, int N, int d) {
-    // Ypart [B,K,N,d] + Cpart [B,K,N,N] (fgw_part_t); zvec [B,K,2N] + yvec [B,2N], fp64; redo [B,K] int32
-    return conan_fgw_part_offset(B, K, N, d) + ((size_t)B * K * 2 * N + (size_t)B * 2 * N) * 8 + (size_t)B * K * 4 + 512;
+void conan_fgw_small_prepare(const FgwCall &c) {
+    k_fgw_small_vectors<<<c.D.B * c.D.K, 256, 0, c.s>>>(c.Ys, c.Cs, c.ps, c.p, c.D, c.prm.loss_fun, c.Cw, c.Yw, c.zvec, c.yvec, c.init_C, c.init_Y,
+                                                       c.prm.max_iter, c.active, c.info, c.errs, c.Y, c.C, c.adj);
 }
 
-void conan_fgw_small_prepare(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm,
-                             double *Cw, double *Yw, double *zvec, double *yvec, const float *init_C, const float *init_Y, int *active, int *info,
-                             float *errs, float *Yout, float *Cout, FgwAdj adj, hipStream_t s) {
-    k_fgw_small_vectors<<<D.B * D.K, 256, 0, s>>>(Ys, Cs, ps, pb, D, prm.loss_fun, Cw, Yw, zvec, yvec, init_C, init_Y, prm.max_iter, active, info,
-                                                 errs, Yout, Cout, adj);
+// rows per lane quad -> the build that covers them: f(std::integral_constant<int, 6 | 9 | 12 | 16>{})
+template <class F>
+static void with_rows(int R, F &&f) {
+    if (R <= 6) f(std::integral_constant<int, 6>{});
+    else if (R <= 9) f(std::integral_constant<int, 9>{});
+    else if (R <= 12) f(std::integral_constant<int, 12>{});
+    else f(std::integral_constant<int, 16>{});
 }
 
-template <int R, int MAXT, typename C2T>
-static void launch_fast_t(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer, int y_zero,
-                        const double *Cw, const double *Yw, const int *active, float *Tw, int *info, fgw_part_t *Ypart, fgw_part_t *Cpart,
-                        const double *zvec, const double *yvec, int *redo, FgwAdj adj, hipStream_t s) {
-    const size_t lds = fast_lds<C2T>(D.N).bytes;
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling_fast<R, MAXT, C2T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-    const FastConst fc = fast_const(prm, D.N);
-    k_fgw_coupling_fast<R, MAXT, C2T><<<D.B * D.K, FGW_THREADS, lds, s>>>(Ys, Cs, ps, pb, D, prm, fc, outer, y_zero, Cw, Yw, active, Tw, info, Ypart,
-                                                                          Cpart, zvec, yvec, redo, adj);
-}
+// the round-3 kernel; MAXT (product tiles per wavefront) is the smallest of the builds R has that covers N
 template <int R, typename C2T>
-static void launch_fast(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D, conan_fgw_params prm, int outer, int y_zero,
-                        const double *Cw, const double *Yw, const int *active, float *Tw, int *info, fgw_part_t *Ypart, fgw_part_t *Cpart,
-                        const double *zvec, const double *yvec, int *redo, FgwAdj adj, hipStream_t s) {
+static void launch_fast(const FgwCall &c, int outer, int y_zero, fgw_part_t *Ypart) {
+    const FgwDims &D = c.D;
     const int tpw = fast_tiles_per_wave(D.N);                          // <= ceil(ceil(4R / 16)^2 / 4)
-#define ARGS Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, Tw, info, Ypart, Cpart, zvec, yvec, redo, adj, s
-    if constexpr (R <= 6) launch_fast_t<R, 1, C2T>(ARGS);
-    else if constexpr (R <= 12) { if (tpw <= 1) launch_fast_t<R, 1, C2T>(ARGS); else launch_fast_t<R, 3, C2T>(ARGS); }
-    else { if (tpw <= 1) launch_fast_t<R, 1, C2T>(ARGS); else if (tpw <= 3) launch_fast_t<R, 3, C2T>(ARGS); else launch_fast_t<R, 4, C2T>(ARGS); }
-#undef ARGS
+    auto go = [&](auto kernel) {
+        launch_lds(kernel, D.B * D.K, FGW_THREADS, fast_lds<C2T>(D.N).bytes, c.s, c.Ys, c.Cs, c.ps, c.p, D, c.prm, fast_const(c.prm, D.N), outer,
+                   y_zero, c.Cw, c.Yw, c.active, c.T, c.info, Ypart, c.Cpart, c.zvec, c.yvec, c.redo, c.adj);
+    };
+    if constexpr (R <= 6) go(k_fgw_coupling_fast<R, 1, C2T>);
+    else if constexpr (R <= 12) { if (tpw <= 1) go(k_fgw_coupling_fast<R, 1, C2T>); else go(k_fgw_coupling_fast<R, 3, C2T>); }
+    else { if (tpw <= 1) go(k_fgw_coupling_fast<R, 1, C2T>); else if (tpw <= 3) go(k_fgw_coupling_fast<R, 3, C2T>); else go(k_fgw_coupling_fast<R, 4, C2T>); }
 }
 
 bool conan_fgw_fast_supported(int N, int d, int small_int) {
@@ -1285,74 +1274,41 @@ bool conan_fgw_fast_supported(int N, int d, int small_int) {
     return lds <= 160 * 1024 && d >= 1;
 }
 
-void conan_fgw_small_coupling(const float *Ys, const float *Cs, const float *ps, const float *pb, FgwDims D,
-                              conan_fgw_params prm, int outer, int y_zero, const double *Cw, const double *Yw,
-                              const int *active, float *Tw, int *info, fgw_part_t *Ypart, fgw_part_t *Cpart, const double *zvec,
-                              const double *yvec, int *redo, FgwAdj adj, hipStream_t s) {
+void conan_fgw_small_coupling(const FgwCall &c, int outer, int y_zero, fgw_part_t *Ypart) {
+    const FgwDims &D = c.D;
     const size_t lds = small_lds(D.N, D.d);
-    const int R = (D.N + 3) / 4;
     const int grid = D.B * D.K;
-    // Square loss: the round-3 kernel first; whatever it hands back (redo[b, s] = 1: a Sinkhorn sum left the fp64-safe range) is solved
-    // by the kernel with the exact log-domain path, launched over the same grid with an early exit for everything else.
-    const int *only = nullptr;
-    if (!prm.loss_fun && redo && conan_fgw_fast_supported(D.N, D.d, prm.cs_small_int)) {
-#define FAST(RR)                                                                                                                     \
-    do {                                                                                                                             \
-        if (prm.cs_small_int) launch_fast<RR, unsigned char>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, Tw, info, Ypart, Cpart, zvec, yvec, redo, adj, s); \
-        else launch_fast<RR, float>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, Tw, info, Ypart, Cpart, zvec, yvec, redo, adj, s);     \
-    } while (0)
-        if (R <= 6) FAST(6);
-        else if (R <= 9) FAST(9);
-        else if (R <= 12) FAST(12);
-        else FAST(16);
-#undef FAST
-        only = redo;
-    }
-#define LAUNCH_(RR, SEC, GRID)                                                                                                  \
-    do {                                                                                                                        \
-        if (lds > 64 * 1024)                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_coupling_small<RR, KLV, SEC>),                     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-        k_fgw_coupling_small<RR, KLV, SEC><<<GRID, FGW_THREADS, lds, s>>>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, Tw, \
-                                                                info, Ypart, Cpart, zvec, yvec, only, adj);                     \
-    } while (0)
-#define LAUNCH(RR)                                                                                                              \
-    do {                                                                                                                        \
-        if constexpr (KLV) LAUNCH_(RR, false, grid);                                                                            \
-        else if (only) LAUNCH_(RR, true, (grid + 63) / 64);                                                                     \
-        else LAUNCH_(RR, false, grid);                                                                                          \
-    } while (0)
-    if (prm.loss_fun) {
-        constexpr bool KLV = true;
-        if (R <= 6) LAUNCH(6);
-        else if (R <= 9) LAUNCH(9);
-        else if (R <= 12) LAUNCH(12);
-        else LAUNCH(16);
-    } else {
-        constexpr bool KLV = false;
-        if (R <= 6) LAUNCH(6);
-        else if (R <= 9) LAUNCH(9);
-        else if (R <= 12) LAUNCH(12);
-        else LAUNCH(16);
-    }
-#undef LAUNCH
-#undef LAUNCH_
+    const bool kl = c.prm.loss_fun != 0;
+    with_rows((D.N + 3) / 4, [&](auto R) {
+        // Square loss: the round-3 kernel first; whatever it hands back (redo[b, s] = 1: a Sinkhorn sum left the fp64-safe range) is solved
+        // by the kernel with the exact log-domain path, launched over the same grid with an early exit for everything else.
+        const int *only = nullptr;
+        if (!kl && conan_fgw_fast_supported(D.N, D.d, c.prm.cs_small_int)) {
+            if (c.prm.cs_small_int) launch_fast<R.value, unsigned char>(c, outer, y_zero, Ypart);
+            else launch_fast<R.value, float>(c, outer, y_zero, Ypart);
+            only = c.redo;
+        }
+        auto exact = [&](auto kernel, int blocks) {
+            launch_lds(kernel, blocks, FGW_THREADS, lds, c.s, c.Ys, c.Cs, c.ps, c.p, D, c.prm, outer, y_zero, c.Cw, c.Yw, c.active, c.T, c.info, Ypart,
+                       c.Cpart, c.zvec, c.yvec, only, c.adj);
+        };
+        if (kl) exact(k_fgw_coupling_small<R.value, true, false>, grid);                      // (no SECOND build with the KL loss: it has no round-3 kernel)
+        else if (only) exact(k_fgw_coupling_small<R.value, false, true>, (grid + 63) / 64);
+        else exact(k_fgw_coupling_small<R.value, false, false>, grid);
+    });
 }
 
-void conan_fgw_small_update(const float *pb, const float *lambdas, FgwDims D, conan_fgw_params prm, int outer,
-                            const fgw_part_t *Ypart, const fgw_part_t *Cpart, double *Cw, double *Yw, int *active, int *info,
-                            float *errs, float *Yout, float *Cout, double *yvec, const float *Tw, const float *Ys, hipStream_t s) {
-    // Tw / Ys given: the feature contributions are formed in this kernel from the couplings (conan_fgw_update_chunk > 0; the coupling kernels were
+void conan_fgw_small_update(const FgwCall &c, int outer, bool y_from_t) {
+    const FgwDims &D = c.D;
+    // y_from_t: the feature contributions are formed in this kernel from the couplings (conan_fgw_update_chunk > 0; the coupling kernels were
     // then launched with Ypart = nullptr)
-    const int chunk = Tw ? conan_fgw_update_chunk(D.K, D.N, D.d, D.B) : 0;
-    if (chunk > 0) {
-        const size_t lds = (size_t)chunk * ((size_t)D.N * D.N + (size_t)D.N * D.d) * 4;
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgw_update_parts<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        k_fgw_update_parts<true><<<2 * D.B, UPD_THREADS, lds, s>>>(pb, lambdas, D, prm, outer, nullptr, Cpart, Cw, Yw, active, info, errs, Yout, Cout, yvec, Tw, Ys, chunk);
-    } else {
-        k_fgw_update_parts<false><<<2 * D.B, UPD_THREADS, 0, s>>>(pb, lambdas, D, prm, outer, Ypart, Cpart, Cw, Yw, active, info, errs, Yout, Cout, yvec, nullptr, nullptr, 0);
-    }
+    const int chunk = y_from_t ? conan_fgw_update_chunk(D.K, D.N, D.d, D.B) : 0;
+    if (chunk > 0)
+        launch_lds(k_fgw_update_parts<true>, 2 * D.B, UPD_THREADS, (size_t)chunk * ((size_t)D.N * D.N + (size_t)D.N * D.d) * 4, c.s, c.p, c.lambdas, D,
+                   c.prm, outer, nullptr, c.Cpart, c.Cw, c.Yw, c.active, c.info, c.errs, c.Y, c.C, c.yvec, c.T, c.Ys, chunk);
+    else
+        k_fgw_update_parts<false><<<2 * D.B, UPD_THREADS, 0, c.s>>>(c.p, c.lambdas, D, c.prm, outer, c.Ypart, c.Cpart, c.Cw, c.Yw, c.active, c.info, c.errs,
+                                                                     c.Y, c.C, c.yvec, nullptr, nullptr, 0);
 }
 
 // graphs per LDS stage of the update kernel's own T_s Z_s products (0: not on that path — N > 64, or one graph does not fit)

@@ -918,36 +918,20 @@ class _FgwBarycenterFn(torch.autograd.Function):
         import ctypes
         solver = FGW_SOLVERS[params.get("solver", "PGD")]
         symmetric = _symmetric_code(params.get("symmetric", True))
-        if symmetric != 1:           # symmetric=False / None: the `_solver` argument lists plus the solver and symmetric codes
-            if adj is None:
-                ws = torch.empty(int(lib().conan_fgw_workspace_bytes_sym(B, K, N, d, solver, symmetric)), dtype=torch.uint8, device=dev)
-                call("conan_fgw_barycenter_fwd_sym", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
-                     B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver,
-                     symmetric)
-            else:
-                ws = torch.empty(int(lib().conan_fgw_workspace_bytes_ragged_sym(B, K, N, d, solver, symmetric)), dtype=torch.uint8, device=dev)
-                call("conan_fgw_barycenter_fwd_ragged_sym", ptr(Ys, f32), ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32),
-                     ptr(adj.tgt, i32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C),
-                     ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver, symmetric)
-        elif solver != 0:            # PPA / BAPG: the same argument lists plus the solver code (PGD keeps the original entry points)
-            if adj is None:
-                ws = torch.empty(int(lib().conan_fgw_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
-                call("conan_fgw_barycenter_fwd_solver", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
-                     B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver)
-            else:
-                ws = torch.empty(int(lib().conan_fgw_workspace_bytes_ragged(B, K, N, d)), dtype=torch.uint8, device=dev)
-                call("conan_fgw_barycenter_fwd_ragged_solver", ptr(Ys, f32), ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32),
-                     ptr(adj.tgt, i32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C),
-                     ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), solver)
-        elif adj is None:
-            ws = torch.empty(int(lib().conan_fgw_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
-            call("conan_fgw_barycenter_fwd", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
-                 B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+        # One call: symmetric=False / None takes the `_sym` pair (trailing solver and symmetric codes), PPA / BAPG the `_solver` pair (trailing
+        # solver code), PGD the original pair; a RadiusGraph the `_ragged` twin of each, with its four lists in place of Cs.
+        if symmetric != 1:
+            suffix, query, tail = "_sym", "_sym", (solver, symmetric)
+        elif solver != 0:
+            suffix, query, tail = "_solver", "", (solver,)
         else:
-            ws = torch.empty(int(lib().conan_fgw_workspace_bytes_ragged(B, K, N, d)), dtype=torch.uint8, device=dev)
-            call("conan_fgw_barycenter_fwd_ragged", ptr(Ys, f32), ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32), ptr(adj.tgt, i32),
-                 ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter),
-                 ptr(info), ptr(errs), ptr(ws), stream_ptr())
+            suffix, query, tail = "", "", ()
+        ragged = "" if adj is None else "_ragged"
+        ws_bytes = getattr(lib(), "conan_fgw_workspace_bytes" + ragged + query)(B, K, N, d, *(tail if query else ()))
+        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+        structure = (ptr(Cs, f32),) if adj is None else (ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32), ptr(adj.tgt, i32))
+        call("conan_fgw_barycenter_fwd" + ragged + suffix, ptr(Ys, f32), *structure, ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
+             B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), *tail)
         ctx.dims = (B, K, N, d)
         ctx.set_materialize_grads(False)          # C, T, info, errs carry no gradient: without this autograd fills four zero tensors per backward
         # Gradients beyond Ys (conan_fgw_barycenter_bwd_full): the last update steps are differentiable in Cs, p, lambdas (and init_C /

@@ -528,7 +528,7 @@ typedef struct conan_fgw_params {
                              * workgroups per CU at N = 33).  0 = arbitrary floats (fgw_barycenters called with general matrices). */
 } conan_fgw_params;
 
-/* Workspace size in BYTES for conan_fgw_barycenter_fwd. */
+/* Workspace size in BYTES for conan_fgw_barycenter_fwd (the regions of all four size queries: DESIGN.md, "FGW workspace"). */
 long long conan_fgw_workspace_bytes(int B, int K, int N, int d);
 
 /* Batched fgw_barycenters (barycenter.py:7-225 -> bregman.py:70-167 -> sinkhorn.py:318-450 -> utils.py), one
