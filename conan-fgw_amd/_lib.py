@@ -163,6 +163,9 @@ SIGNATURES = {
                                              _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int]),
     "conan_fgw_barycenter_fwd_ragged_sym": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
                                                     ctypes.POINTER(FgwParams), _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int]),
+    "conan_fgw_pair_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "conan_fgw_pair_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(FgwParams), c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "conan_fgw_pair_dist": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P]),
     "conan_fgw_barycenter_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "conan_fgw_barycenter_bwd_full_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "conan_fgw_barycenter_bwd_full": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

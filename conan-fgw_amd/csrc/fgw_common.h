@@ -81,6 +81,14 @@ struct FgwDims {
     int B, K, N, d, P;      // P = row pitch of the LDS/scratch matrices (odd => conflict-free column access)
 };
 
+// What the pair form of the general coupling kernels (PAIR: k_fgw_coupling_pair, k_fgw_coupling_bapg_pair) takes beyond the barycenter form's arguments:
+// the caller's cost M [B,N,N] and the error list errs [B,nerr], nerr = ceil(max_iter / 10), one entry per check of ||T - Tprev||.
+struct FgwPair {
+    const float *M;
+    float *errs;
+    int nerr;
+};
+
 // "Molecule b still moves" flags of the outer loop (barycenter.py:112): [parity of the outer iteration][features | structure][B] ints.  The update
 // kernel of iteration o writes the flags of parity o & 1 — one from each of the molecule's two workgroups — and everything that runs in iteration
 // o (coupling kernels, the update itself) reads the flags of iteration o - 1, i.e. parity (o + 1) & 1; the init kernels raise parity 1.
@@ -1048,6 +1056,24 @@ __device__ __forceinline__ void mm_lds2(int M, int Nn, int Kd, const TX *__restr
 struct FgwWorkspace {
     size_t Cw, Yw, active, scratch, order, Ypart, Cpart, zvec, yvec, redo, dense, asym, total;
 };
+// The same for conan_fgw_pair_fwd (fgw_pair_workspace in fgw.hip): C1 widened to fp64 [B,N,N], then `stride` bytes of coupling scratch per pair.
+struct FgwPairWorkspace {
+    size_t C1w, scratch, total, stride;
+};
+// One pair solve (conan_fgw_pair_fwd), as FgwCall is one barycenter solve.  T holds G0 when `warm`.
+struct FgwPairCall {
+    const float *M, *C2, *p, *q;
+    const double *C1w;
+    FgwDims D;                      // {B, 1, N, 0, P}
+    conan_fgw_params prm;           // max_iter / inner_tol: the solve's own max_iter / tol
+    int symmetric, warm;
+    float *T;
+    int *info;
+    FgwPair pr;
+    char *scratch;
+    size_t scratch_stride;
+    hipStream_t s;
+};
 
 // One solve's inputs, outputs, parameters, workspace pointers and stream.  The launchers below take it by const reference plus the few values
 // that change per outer iteration, and unpack it into the kernels' argument lists at the launch site only.
@@ -1087,6 +1113,30 @@ inline void with_flags(F &&f, bool b, B... rest) {
     else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
+// ---- shared by fgw.hip (the barycenter driver) and fgw_pair.hip (the pair solve): the general coupling kernels' scratch, LDS budget and mode
+namespace {
+// bytes of global scratch per coupling workgroup (Mr, A, base fp64 + T fp32 = 28 B per matrix entry), rounded to 16 B so that every
+// workgroup's fp64 region is aligned whatever the parity of N*P
+__host__ __device__ inline size_t coupling_scratch_stride(size_t NP) { return (NP * 28 + 15) / 16 * 16; }
+inline int pitch_of(int N) { return fgw_pitch(N); }
+inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
+constexpr int GEN_NW = 8;                   // wavefronts per workgroup of the large-N coupling kernel (16 measured no faster: 453 vs 443 us per workgroup and launch)
+inline size_t coupling_lds(int N) { return (size_t)((6 + 2 * GEN_NW) * N + 16) * 8 + (size_t)N * pitch_of(N) * 28; }
+constexpr size_t LDS_LIMIT = 160 * 1024;
+// k_fgw_coupling's LDS mode at N and the dynamic LDS it then takes
+inline int general_mode(int N, size_t *lds_bytes) {
+    const size_t lc = coupling_lds(N), vec_c = (size_t)((6 + 2 * GEN_NW) * N + 16) * 8, mr_bytes = (size_t)N * pitch_of(N) * 8;
+    const int mode = lc <= LDS_LIMIT ? 2 : (vec_c + mr_bytes <= LDS_LIMIT ? 1 : 0);
+    *lds_bytes = mode == 2 ? lc : vec_c + (mode == 1 ? mr_bytes : 0);
+    return mode;
+}
+template <class T>
+inline T *ws_at(void *workspace, size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + offset); }
+}  // namespace
+#ifndef CONAN_FGW_ASYM_C1T
+#define CONAN_FGW_ASYM_C1T 1        // (A/B switch) ASYM, modes 1 / 2: B = C1^T T from a transposed fp64 copy of C1 (the coupling's free scratch) instead of the element-reader form
+#endif
+
 // Launchers of the register-resident path (fgw_small.hip), N <= 64.
 bool conan_fgw_small_supported(int N, int d);
 bool conan_fgw_fast_supported(int N, int d, int small_int);
@@ -1103,3 +1153,6 @@ int conan_fgw_update_chunk(int K, int N, int d, int B);
 size_t conan_fgw_bapg_lds(int N, bool asym = false);
 size_t conan_fgw_bapg_asym_scratch_bytes(int B, int K, int N);
 void conan_fgw_bapg_coupling(const FgwCall &c, int outer, int y_zero);
+// the pair form of the same kernel; conan_fgw_bapg_pair_stride: bytes of scratch per pair it needs outside LDS (0 inside)
+size_t conan_fgw_bapg_pair_stride(int N, bool asym);
+void conan_fgw_bapg_pair(const FgwPairCall &c);

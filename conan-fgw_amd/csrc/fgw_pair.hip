@@ -1,0 +1,188 @@
+// The pair solve for gfx950: the reference's fgw(M, C1, C2, p, q, ...) (bregman.py:8-67 -> fgw_projected :70-167 / fgw_bregman :170-279) for B pairs of
+// attributed graphs at once, one workgroup per pair, with the reference's log: the error list and fgw_dist (bregman.py:149-150, :163-164).
+//
+//   k_fgw_pair_init              C1 widened to fp64, errs <- NaN, info <- 0
+//   k_fgw_coupling_pair          PGD / PPA: the body of k_fgw_coupling (fgw_coupling_body.inc) compiled with PAIR = true        (here)
+//   k_fgw_coupling_bapg_pair     BAPG: the body of k_fgw_coupling_bapg (fgw_bapg_body.inc) compiled with PAIR = true           (fgw_bapg.hip)
+//   k_fgw_pair_dist              fgw_dist of the returned plan; also exported on its own (conan_fgw_pair_dist)
+//
+// What PAIR changes is described in front of k_fgw_coupling (fgw.hip); DESIGN.md 3.3, "Pair form".
+#include "fgw_common.h"
+
+namespace {
+
+// The pair form.  Same arguments, of which it reads: Ys = M and Cs = C2 [B,N,N], ps = q and pb = p [B,N] (nullable: uniform), Cw = the widened C1, Tw = T
+// (in: G0 when outer = 1 and prm.warmstart), D = {B, 1, N, 0, P}, y_zero = 1 | (symmetric=None) << 1; Yw, active, Ypart, Cpart, only are unused (null).
+template <int MODE, bool KL, int NW, bool PPA, bool ASYM>
+__global__ void __launch_bounds__(64 * NW) k_fgw_coupling_pair(
+    const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb,
+    FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw,
+    const int *__restrict__ active, float *__restrict__ Tw, int *__restrict__ info, char *__restrict__ scratch,
+    fgw_part_t *__restrict__ Ypart, fgw_part_t *__restrict__ Cpart, const int *__restrict__ only, FgwAdj adj, FgwPair pr) {
+    constexpr bool PAIR = true, SECOND = false;
+#include "fgw_coupling_body.inc"
+}
+
+// conan_fgw_pair_fwd's first launch: C1 widened to fp64 (the operand type of the coupling kernels' products), errs filled with NaN, info zeroed
+__global__ void __launch_bounds__(256) k_fgw_pair_init(const float *__restrict__ C1, double *__restrict__ C1w, int NN, float *__restrict__ errs, int nerr,
+                                                       int *__restrict__ info) {
+    const int b = blockIdx.x;
+    for (int t = threadIdx.x; t < NN; t += 256) C1w[(size_t)b * NN + t] = (double)C1[(size_t)b * NN + t];
+    for (int t = threadIdx.x; t < nerr; t += 256) errs[(size_t)b * nerr + t] = __builtin_nanf("");
+    if (threadIdx.x < 4) info[b * 4 + threadIdx.x] = 0;
+}
+
+// fgw_dist of the reference's log (bregman.py:163-164, :272 with utils.py:4-64), one workgroup per pair:
+//     (1 - alpha) sum_ij M_ij T_ij + alpha sum_ij (constC_ij - (h1(C1) T h2(C2)^T)_ij) T_ij,     constC_ij = sum_k f1(C1_ik) p_k + sum_k q_k f2(C2_jk)
+// always from the problem itself, not its transpose (the reference does so after an asymmetric solve too).  The two products run on fp64 MFMA over
+// blocks of R rows of A = C1 T held in LDS (R = N when the matrix fits).  Every sum is fp64, per thread in index order, then over the lanes and the
+// wavefronts in a fixed order: no atomics, the same bits on every run and for every batch the pair is part of.
+template <bool KL, int NW>
+__global__ void __launch_bounds__(64 * NW) k_fgw_pair_dist(const float *__restrict__ M, const float *__restrict__ C1, const float *__restrict__ C2,
+                                                           const float *__restrict__ p, const float *__restrict__ q, const float *__restrict__ T, int N,
+                                                           int R, float alpha_f, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NT = 64 * NW;
+    const int b = blockIdx.x, P = fgw_pitch(N), NN = N * N;
+    const int tid = threadIdx.x;
+    double *pa = reinterpret_cast<double *>(smem), *qb = pa + N, *cc = pa + 2 * N, *rc = pa + 3 * N, *red = pa + 4 * N, *A = red + 16;      // A [R,P]
+    M += (size_t)b * NN; C1 += (size_t)b * NN; C2 += (size_t)b * NN; T += (size_t)b * NN;
+    const double alpha = (double)alpha_f;
+    for (int i = tid; i < N; i += NT) {
+        pa[i] = p ? (double)p[(size_t)b * N + i] : 1.0 / (double)N;
+        qb[i] = q ? (double)q[(size_t)b * N + i] : 1.0 / (double)N;
+    }
+    __syncthreads();
+    {   // init_matrix (utils.py:39-41): 8 lanes per index, as in the coupling kernels
+        constexpr int LPI = 8;
+        for (int i0 = 0; i0 < N; i0 += NT / LPI) {
+            const int i = i0 + tid / LPI, sub = tid % LPI;
+            double r1 = 0.0, r2 = 0.0;
+            if (i < N)
+                for (int k = sub; k < N; k += LPI) {
+                    const double c1 = (double)C1[i * N + k], c2 = (double)C2[i * N + k];
+                    r1 += (KL ? c1 * log(c1 + 1e-15) - c1 : c1 * c1) * pa[k];
+                    r2 += qb[k] * (KL ? c2 : c2 * c2);
+                }
+#pragma unroll
+            for (int o = 1; o < LPI; o <<= 1) { r1 += __shfl_xor(r1, o, 64); r2 += __shfl_xor(r2, o, 64); }
+            if (i < N && sub == 0) { cc[i] = r1; rc[i] = r2; }
+        }
+    }
+    __syncthreads();
+    double lin = 0.0, quad = 0.0;                                         // sum M T ; sum (constC - G) T
+    for (int t = tid; t < NN; t += NT) {
+        const int i = t / N, j = t - i * N;
+        const double tv = (double)T[t];
+        lin += (double)M[t] * tv;
+        quad += (cc[i] + rc[j]) * tv;
+    }
+    for (int r0 = 0; r0 < N; r0 += R) {
+        const int rows = min(R, N - r0);
+        mm_f64_glb<NW, false>(rows, N, N, C1 + (size_t)r0 * N, N, T, N, [&](int i, int j, double v) { A[i * P + j] = v; });      // A = h1(C1) T
+        __syncthreads();
+        auto take = [&](int i, int j, double g) { quad -= (KL ? 1.0 : 2.0) * g * (double)T[(r0 + i) * N + j]; };               // h2 = 2 C2: the 2 here
+        if constexpr (KL)
+            mm_f64<NW>(rows, N, N, [&](int i, int k) { return A[i * P + k]; }, [&](int k, int j) { return log((double)C2[j * N + k] + 1e-15); }, take);
+        else
+            mm_f64_glb<NW, true>(rows, N, N, A, P, C2, N, take);
+        __syncthreads();
+    }
+    const double total = block_sum_d<NW>((1.0 - alpha) * lin + alpha * quad, red);
+    if (tid == 0) out[b] = (float)total;
+}
+
+// The workspace of conan_fgw_pair_fwd, described once like fgw_workspace; total = 0 for what the entry point refuses.
+FgwPairWorkspace fgw_pair_workspace(int B, int N, int solver, int symmetric) {
+    FgwPairWorkspace w{};
+    if (B <= 0 || N <= 0 || solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return w;
+    const size_t NN = (size_t)N * N, NP = (size_t)N * pitch_of(N);
+    w.stride = solver == 2 ? conan_fgw_bapg_pair_stride(N, symmetric != 1) : coupling_scratch_stride(NP);
+    size_t end = 0;
+    auto region = [&](size_t bytes) { const size_t at = end; end += bytes; return at; };
+    w.C1w = region(al256((size_t)B * NN * 8));
+    w.scratch = region(al256((size_t)B * w.stride));
+    w.total = end;
+    return w;
+}
+// rows of A = C1 T that k_fgw_pair_dist holds in LDS at a time (0: not even 16 fit), and its dynamic LDS
+inline int pair_dist_rows(int N, size_t *lds_bytes) {
+    const size_t vec = (size_t)(4 * N + 16) * 8, row = (size_t)pitch_of(N) * 8;
+    if (vec + 16 * row > LDS_LIMIT && vec + (size_t)N * row > LDS_LIMIT) return 0;
+    const size_t fit = (LDS_LIMIT - vec) / row;
+    const int R = fit >= (size_t)N ? N : (int)(fit / 16 * 16);
+    *lds_bytes = vec + (size_t)R * row;
+    return R;
+}
+int fgw_pair_dist_launch(const float *M, const float *C1, const float *C2, const float *p, const float *q, const float *T, int B, int N, float alpha,
+                         int loss_fun, float *out, hipStream_t s) {
+    size_t bytes = 0;
+    const int R = pair_dist_rows(N, &bytes);
+    if (R <= 0) return CONAN_E_UNSUPPORTED;
+    if (loss_fun) launch_lds(k_fgw_pair_dist<true, GEN_NW>, B, 64 * GEN_NW, bytes, s, M, C1, C2, p, q, T, N, R, alpha, out);
+    else launch_lds(k_fgw_pair_dist<false, GEN_NW>, B, 64 * GEN_NW, bytes, s, M, C1, C2, p, q, T, N, R, alpha, out);
+    return CONAN_OK;
+}
+template <int MD>
+void launch_pair(const FgwPairCall &c, size_t lds_bytes, int solver) {
+    with_flags([&](auto KL, auto PPA, auto ASYM) {
+        launch_lds(k_fgw_coupling_pair<MD, KL.value, GEN_NW, PPA.value, ASYM.value>, c.D.B, 64 * GEN_NW, lds_bytes, c.s, c.M, c.C2, c.q, c.p, c.D, c.prm,
+                   c.warm, 1 | (c.symmetric < 0 ? 2 : 0), c.C1w, nullptr, nullptr, c.T, c.info, c.scratch, nullptr, nullptr, nullptr, FgwAdj{}, c.pr);
+    }, c.prm.loss_fun != 0, solver == 1, c.symmetric != 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the pair solve: fgw(M, C1, C2, p, q) of bregman.py:8-279 for B pairs at once
+long long conan_fgw_pair_workspace_bytes(int B, int N, int solver, int symmetric) { return (long long)fgw_pair_workspace(B, N, solver, symmetric).total; }
+
+int conan_fgw_pair_dist(const float *M, const float *C1, const float *C2, const float *p, const float *q, const float *T, int B, int N, float alpha,
+                        int loss_fun, float *out, void *stream) {
+    if (!M || !C1 || !C2 || !T || !out || B <= 0 || N <= 0 || (loss_fun != 0 && loss_fun != 1)) return CONAN_E_BADARG;
+    const int rc = fgw_pair_dist_launch(M, C1, C2, p, q, T, B, N, alpha, loss_fun, out, as_stream(stream));
+    if (rc != CONAN_OK) return rc;
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+int conan_fgw_pair_fwd(const float *M, const float *C1, const float *C2, const float *p, const float *q, const float *G0, int B, int N,
+                       const conan_fgw_params *params, int solver, int symmetric, float *T, float *fgw_dist, int *info, float *errs, void *workspace,
+                       void *stream) {
+    if (solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
+    if (!M || !C1 || !C2 || !params || !T || !info || !errs || !workspace || B <= 0 || N <= 0) return CONAN_E_BADARG;
+    if (params->max_iter <= 0 || (solver != 2 && params->num_iter_max <= 0) || (params->loss_fun != 0 && params->loss_fun != 1)) return CONAN_E_BADARG;
+    size_t dist_lds = 0;
+    if (fgw_dist && pair_dist_rows(N, &dist_lds) <= 0) return CONAN_E_UNSUPPORTED;
+    const FgwPairWorkspace w = fgw_pair_workspace(B, N, solver, symmetric);
+    const size_t NN = (size_t)N * N;
+    FgwPairCall c{};
+    c.M = M; c.C2 = C2; c.p = p; c.q = q;
+    c.C1w = ws_at<double>(workspace, w.C1w);
+    c.D = FgwDims{B, 1, N, 0, pitch_of(N)};
+    c.prm = *params;
+    c.prm.inner_tol = params->tol;                              // the kernels' loop tests inner_tol: here the solve's own tol
+    c.prm.warmstart = G0 ? 1 : 0;
+    c.prm.fixed_structure = c.prm.fixed_features = 1;
+    c.symmetric = symmetric; c.warm = G0 ? 1 : 0;
+    c.T = T; c.info = info;
+    c.pr = FgwPair{M, errs, (params->max_iter + 9) / 10};
+    c.scratch = ws_at<char>(workspace, w.scratch); c.scratch_stride = w.stride;
+    c.s = as_stream(stream);
+    k_fgw_pair_init<<<B, 256, 0, c.s>>>(C1, ws_at<double>(workspace, w.C1w), (int)NN, errs, c.pr.nerr, info);
+    if (G0) (void)hipMemcpyAsync(T, G0, (size_t)B * NN * sizeof(float), hipMemcpyDeviceToDevice, c.s);      // T0 = G0 through the warm-start branch
+    if (solver == 2) conan_fgw_bapg_pair(c);
+    else {
+        size_t lds_bytes = 0;
+        const int mode = general_mode(N, &lds_bytes);
+        if (mode == 2) launch_pair<2>(c, lds_bytes, solver);
+        else if (mode == 1) launch_pair<1>(c, lds_bytes, solver);
+        else launch_pair<0>(c, lds_bytes, solver);
+    }
+    if (fgw_dist) (void)fgw_pair_dist_launch(M, C1, C2, p, q, T, B, N, params->alpha, params->loss_fun, fgw_dist, c.s);
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 """Functional boundary of the FGW solver, mirroring the reference's signature
-(conan_fgw/src/model/fgw/barycenter.py:7-31 `fgw_barycenters`, :393-399 `normalize_tensor`).
+(conan_fgw/src/model/fgw/barycenter.py:7-31 `fgw_barycenters`, :393-399 `normalize_tensor`; bregman.py:8-279 `fgw`, `fgw_projected`,
+`fgw_bregman` — the coupling solve between two attributed graphs on its own, with `fgw_pairwise_distances` over an ensemble on top).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
 barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
@@ -142,6 +143,113 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
             "Ms": Ms,
             "n_outer": outer, "n_pgd": int(info[0, 1].item()), "n_sinkhorn": int(info[0, 2].item())}
     return Y[0], C[0], log_
+
+
+_FAILED = "Solver failed to produce a transport plan. You might want to increase the regularization parameter `epsilon`."
+
+
+def _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, log, num_iter_max=100, stop_thr=1e-5):
+    """One pair through ops.fgw_pair_batched (B = 1); the reference's return value."""
+    for name, t in (("M", M), ("C1", C1), ("C2", C2), ("p", p), ("q", q), ("G0", G0)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"fgw runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    one = lambda t: None if t is None else t.unsqueeze(0)
+    T, dist, info, errs = ops.fgw_pair_batched(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter,
+                                               tol=tol, num_iter_max=num_iter_max, stop_thr=stop_thr, loss_fun=loss_fun, solver=solver,
+                                               symmetric=symmetric, with_dist=bool(log))
+    T = T[0]
+    # bregman.py:159-162 (PGD / PPA: the plan's total mass) and :267-270 (BAPG: a NaN), one host synchronisation as in the reference
+    failed = bool(torch.isnan(T).any()) if solver == "BAPG" else bool(abs(T.sum() - 1) > 1e-5)
+    if failed:
+        warnings.warn(_FAILED)
+    if not log:
+        return T
+    n_iter, n_sk = int(info[0, 0].item()), int(info[0, 1].item())
+    return T, {"err": [errs[0, i] for i in range((n_iter + 9) // 10)], "fgw_dist": dist[0], "n_iter": n_iter, "n_sinkhorn": n_sk}
+
+
+def fgw_projected(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=100, tol=1e-5,
+                  solver="PGD", method="sinkhorn_log", warmstart=False, verbose=False, log=False, **kwargs):
+    """The reference's fgw_projected (bregman.py:70-167): the entropic FGW coupling between two attributed graphs by projected gradient
+    ("PGD") or proximal point ("PPA") iterations with a log-domain Sinkhorn inside, on the GPU.  M [n1,n2] feature cost, C1 [n1,n1], C2 [n2,n2]
+    structures, p / q marginals, G0 start plan; keywords numItermax (100) / stopThr (1e-5) go to the Sinkhorn.  Returns T [n1,n2]; with log=True
+    (T, {"err": [||T - Tprev|| at every 10th iteration], "fgw_dist": 0-d tensor, "n_iter": int, "n_sinkhorn": int}).  Same ValueErrors and the
+    same "Solver failed" warning (|sum(T) - 1| > 1e-5) as the reference.  Deviations: p=None / q=None mean uniform marginals (the reference's own
+    default crashes in torch.outer(None, None)); warmstart=True raises NotImplementedError (the reference's branch calls torch.log on a Python
+    int and raises TypeError); a method other than "sinkhorn_log", CPU tensors ("GPU only") and verbose printing are not implemented
+    (NotImplementedError for the first two, verbose is ignored); the outputs carry NO gradient (the reference would back-propagate through the
+    unrolled iterations; not built here)."""
+    if solver not in ["PGD", "PPA"]:
+        raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA']." % solver)
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    if warmstart:
+        raise NotImplementedError("warmstart=True is broken in the reference (torch.log of a Python int, bregman.py:113) and not implemented here")
+    if str(method).lower() != "sinkhorn_log":
+        raise NotImplementedError("only method='sinkhorn_log' is implemented")
+    num_iter_max = int(kwargs.pop("numItermax", 100))          # sinkhorn.py:12
+    stop_thr = float(kwargs.pop("stopThr", 1e-5))              # sinkhorn.py:13
+    return _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, log, num_iter_max, stop_thr)
+
+
+def fgw_bregman(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=1000, tol=1e-9,
+                marginal_loss=False, verbose=False, log=False):
+    """The reference's fgw_bregman (bregman.py:170-279): the same coupling by alternating Bregman projections (BAPG), on the GPU.  Arguments and
+    return value as fgw_projected (n_sinkhorn is 0; the reference's log["loss"] is not formed); the warning is the reference's, for a NaN plan.
+    Deviations: as fgw_projected, and marginal_loss=True raises NotImplementedError (no caller of the reference sets it)."""
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    if marginal_loss:
+        raise NotImplementedError("marginal_loss=True is not implemented")
+    return _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, "BAPG", log)
+
+
+def fgw(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=100, tol=1e-5, solver="PGD",
+        method="sinkhorn_log", warmstart=False, verbose=False, log=False, **kwargs):
+    """The reference's fgw (bregman.py:8-67): fgw_projected for solver "PGD" / "PPA", fgw_bregman for "BAPG" (which, as in the reference, takes
+    no Sinkhorn keywords, no method and no warmstart).  See fgw_projected for the return value and the deviations."""
+    if solver in ["PGD", "PPA"]:
+        return fgw_projected(M, C1, C2, p=p, q=q, loss_fun=loss_fun, epsilon=epsilon, symmetric=symmetric, alpha=alpha, G0=G0, max_iter=max_iter,
+                             tol=tol, solver=solver, method=method, warmstart=warmstart, verbose=verbose, log=log, **kwargs)
+    elif solver == "BAPG":
+        return fgw_bregman(M, C1, C2, p=p, q=q, loss_fun=loss_fun, epsilon=epsilon, symmetric=symmetric, alpha=alpha, G0=G0, max_iter=max_iter,
+                           tol=tol, verbose=verbose, log=log)
+    raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % solver)
+
+
+def feature_cost(Y: Tensor, Z: Tensor) -> Tensor:
+    """dist(Y, Z) of the reference (utils.py:154-171): the squared Euclidean distances of the feature rows, clamped at 0 -> [n1,n2]."""
+    return torch.clamp((Y * Y).sum(1)[:, None] + (Z * Z).sum(1)[None, :] - 2.0 * (Y @ Z.T), min=0)
+
+
+def fgw_pairwise_distances(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, alpha=0.5, epsilon=0.1, loss_fun="square_loss", symmetric=None,
+                           max_iter=100, tol=1e-5, solver="PGD", numItermax=100, stopThr=1e-5) -> Tensor:
+    """The FGW distance matrix of G attributed graphs (the conformers of an ensemble): Ys[g] [n_g,d] features, Cs[g] [n_g,n_g] structures, ps[g]
+    node weights or None (uniform) -> [G,G], symmetric with a zero diagonal.  The G (G - 1) / 2 pairs a < b are solved in ONE
+    ops.fgw_pair_batched call (the list form when the sizes differ) with M = feature_cost(Ys[a], Ys[b]), formed by torch per pair ahead of
+    the call; entry (a, b) is fgw(M, Cs[a], Cs[b], ps[a], ps[b], ..., log=True)'s log["fgw_dist"], bit for bit.  No gradient."""
+    G = len(Ys)
+    if len(Cs) != G or (ps is not None and len(ps) != G):
+        raise ValueError("Ys, Cs (and ps) must have one entry per graph")
+    if not all(torch.is_tensor(t) and t.is_cuda for t in list(Ys) + list(Cs)):
+        raise NotImplementedError("fgw_pairwise_distances runs on the GPU only: pass CUDA (ROCm) tensors")
+    Ys = [y.detach().to(torch.float32) for y in Ys]
+    out = torch.zeros(G, G, dtype=torch.float32, device=Ys[0].device)
+    ia, ib = torch.triu_indices(G, G, 1).tolist() if G > 1 else ([], [])
+    if not ia:
+        return out
+    kw = dict(alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, num_iter_max=numItermax, stop_thr=stopThr, loss_fun=loss_fun, solver=solver,
+              symmetric=symmetric)
+    Ms = [feature_cost(Ys[a], Ys[b]) for a, b in zip(ia, ib)]
+    pick = lambda ts, idx: None if ts is None else [ts[i] for i in idx]
+    if len({int(y.shape[0]) for y in Ys}) == 1:
+        st = lambda ts: None if ts is None else torch.stack([t.detach().to(torch.float32) for t in ts])
+        dist = ops.fgw_pair_batched(torch.stack(Ms), st(pick(Cs, ia)), st(pick(Cs, ib)), st(pick(ps, ia)), st(pick(ps, ib)), **kw)[1]
+    else:
+        dist = ops.fgw_pair_list(Ms, pick(Cs, ia), pick(Cs, ib), pick(ps, ia), pick(ps, ib), **kw)[1]
+    out[ia, ib] = dist
+    out[ib, ia] = dist
+    return out
 
 
 def normalize_tensor(tensor: Tensor, a: float, b: float) -> Tensor:

@@ -1014,6 +1014,114 @@ def fgw_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, 
     return _FgwBarycenterFn.apply(Ys, Cs, opt(ps), opt(p), opt(lambdas), opt(init_C), opt(init_Y), prm)
 
 
+def _pair_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric):
+    if solver not in FGW_SOLVERS:
+        raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % solver)
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    # conan_fgw_pair_fwd reads alpha, epsilon, max_iter, tol, num_iter_max, stop_thr and loss_fun; the other fields are ignored
+    prm = FgwParams(float(alpha), float(epsilon), int(max_iter), float(tol), float(tol), int(num_iter_max), float(stop_thr), 1, 1, 0,
+                    {"square_loss": 0, "kl_loss": 1}[loss_fun], 0)
+    return prm, FGW_SOLVERS[solver], _symmetric_code(None if symmetric is None else bool(symmetric))
+
+
+def _pair_tensor(t, name, *shape):
+    if not t.is_cuda:
+        raise NotImplementedError(f"the pairwise FGW solve runs on the GPU only: {name} is a CPU tensor")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have shape {list(shape)}, not {list(t.shape)}")
+    return _c(t.detach().to(f32))
+
+
+def fgw_pair_batched(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, G0: Optional[Tensor] = None, *,
+                     alpha: float = 0.5, epsilon: float = 0.1, max_iter: int = 100, tol: float = 1e-5, num_iter_max: int = 100,
+                     stop_thr: float = 1e-5, loss_fun: str = "square_loss", solver: str = "PGD", symmetric=None, with_dist: bool = True):
+    """B independent entropic FGW coupling solves, the reference's fgw(M, C1, C2, p, q, ...) (bregman.py:8-279), in one launch of the pair form of
+    the general coupling kernels (one workgroup per pair).  M [B,n1,n2] (any cost matrix, used as given), C1 [B,n1,n1], C2 [B,n2,n2], p [B,n1] /
+    q [B,n2] or None (uniform), G0 [B,n1,n2] or None (outer(p, q)) -> T [B,n1,n2], fgw_dist [B] (None with with_dist=False), info [B,4] int32 =
+    {PGD / PPA / BAPG iterations, Sinkhorn iterations, flags (bit 2: a node with mass had a zero row / column sum), symmetric decision taken},
+    errs [B, ceil(max_iter / 10)] = ||T - Tprev|| at every 10th iteration (NaN where not executed).
+    max_iter / tol are the solve's own; num_iter_max / stop_thr the Sinkhorn keywords numItermax / stopThr; solver "PGD", "PPA" or "BAPG";
+    symmetric True, False or None (decided per pair by torch.allclose(C, C^T, atol=1e-10) on C1 and C2, inside the kernel).  n1 != n2 is solved
+    embedded in a square problem of max(n1, n2) nodes whose extra nodes carry no mass (zero rows / columns of M, C1, C2, zero weights): the
+    leading block is the reference's rectangular problem.  Non-contiguous inputs are copied.  The outputs carry no gradient."""
+    prm, solver_code, sym_code = _pair_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric)
+    if M.dim() != 3:
+        raise ValueError(f"M must be [B,n1,n2], not {list(M.shape)}")
+    B, n1, n2 = M.shape
+    M, C1, C2 = _pair_tensor(M, "M", B, n1, n2), _pair_tensor(C1, "C1", B, n1, n1), _pair_tensor(C2, "C2", B, n2, n2)
+    p = None if p is None else _pair_tensor(p, "p", B, n1)
+    q = None if q is None else _pair_tensor(q, "q", B, n2)
+    G0 = None if G0 is None else _pair_tensor(G0, "G0", B, n1, n2)
+    dev, N = M.device, max(n1, n2)
+    if n1 != n2:
+        def pad(t, *shape):
+            out = torch.zeros(B, *shape, dtype=f32, device=dev)
+            out[(slice(None),) + tuple(slice(0, k) for k in t.shape[1:])] = t
+            return out
+        p = pad(torch.full((B, n1), 1.0 / n1, dtype=f32, device=dev) if p is None else p, N)
+        q = pad(torch.full((B, n2), 1.0 / n2, dtype=f32, device=dev) if q is None else q, N)
+        M, C1, C2 = pad(M, N, N), pad(C1, N, N), pad(C2, N, N)
+        G0 = None if G0 is None else pad(G0, N, N)
+    T = torch.empty(B, N, N, dtype=f32, device=dev)
+    dist = torch.empty(B, dtype=f32, device=dev) if with_dist else None
+    info = torch.empty(B, 4, dtype=i32, device=dev)
+    errs = torch.empty(B, (prm.max_iter + 9) // 10, dtype=f32, device=dev)
+    import ctypes
+    ws = torch.empty(int(lib().conan_fgw_pair_workspace_bytes(B, N, solver_code, sym_code)), dtype=torch.uint8, device=dev)
+    call("conan_fgw_pair_fwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, ctypes.byref(prm), solver_code, sym_code,
+         ptr(T), ptr(dist), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+    return (T if n1 == n2 else T[:, :n1, :n2]), dist, info, errs
+
+
+def fgw_pair_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
+    """fgw_pair_batched for pairs of different sizes: Ms[b] [n1_b,n2_b], C1s[b], C2s[b], ps[b] / qs[b] / G0s[b] (the lists, or single entries,
+    may be None).  Every pair is embedded in the common Np = max over all n1_b, n2_b with massless nodes and the batch is ONE launch.
+    Returns ([T_b [n1_b,n2_b]], fgw_dist [B], info [B,4], errs)."""
+    B = len(Ms)
+    if B == 0 or len(C1s) != B or len(C2s) != B:
+        raise ValueError("Ms, C1s and C2s must be non-empty lists of the same length")
+    for t in list(Ms) + list(C1s) + list(C2s):
+        if not t.is_cuda:
+            raise NotImplementedError("the pairwise FGW solve runs on the GPU only: got a CPU tensor")
+    dev = Ms[0].device
+    sizes = [tuple(int(k) for k in m.shape) for m in Ms]
+    Np = max(max(s) for s in sizes)
+
+    def stack(ts, cols, default=None):
+        out = torch.zeros(B, *([Np] * cols), dtype=f32, device=dev)
+        for b in range(B):
+            t = ts[b] if ts is not None and ts[b] is not None else default(b)
+            out[(b,) + tuple(slice(0, k) for k in t.shape)] = t.detach().to(f32)
+        return out
+
+    G0 = None
+    if G0s is not None and any(g is not None for g in G0s):
+        if any(g is None for g in G0s):
+            raise ValueError("G0s must hold a start plan for every pair or for none")
+        G0 = stack(G0s, 2)
+    T, dist, info, errs = fgw_pair_batched(
+        stack(Ms, 2), stack(C1s, 2), stack(C2s, 2), stack(ps, 1, lambda b: torch.full((sizes[b][0],), 1.0 / sizes[b][0], device=dev)),
+        stack(qs, 1, lambda b: torch.full((sizes[b][1],), 1.0 / sizes[b][1], device=dev)), G0, **params)
+    return [T[b, :sizes[b][0], :sizes[b][1]] for b in range(B)], dist, info, errs
+
+
+def fgw_pair_dist(M: Tensor, C1: Tensor, C2: Tensor, T: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, *, alpha: float = 0.5,
+                  loss_fun: str = "square_loss") -> Tensor:
+    """The reference's log["fgw_dist"] of the plans T [B,N,N] (conan_fgw_pair_dist; square problems: embed rectangular ones as fgw_pair_batched
+    does): (1 - alpha) sum(M * T) + alpha * gwloss(init_matrix(C1, C2, p, q, loss_fun), T), bregman.py:163-164 -> [B]."""
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    B, N, _ = M.shape
+    M, C1, C2, T = (_pair_tensor(t, n, B, N, N) for t, n in ((M, "M"), (C1, "C1"), (C2, "C2"), (T, "T")))
+    p = None if p is None else _pair_tensor(p, "p", B, N)
+    q = None if q is None else _pair_tensor(q, "q", B, N)
+    out = torch.empty(B, dtype=f32, device=M.device)
+    call("conan_fgw_pair_dist", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(T, f32), B, N, float(alpha),
+         {"square_loss": 0, "kl_loss": 1}[loss_fun], ptr(out), stream_ptr())
+    return out
+
+
 class _MseLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target):

@@ -607,6 +607,33 @@ int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, c
                                         float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver,
                                         int symmetric);
 
+/* The coupling solve on its own, B pairs of attributed graphs at once: the reference's fgw(M, C1, C2, p, q, ...) (bregman.py:8-67 -> fgw_projected
+ * :70-167 / fgw_bregman :170-279), one workgroup per pair on the pair form of the general coupling kernels.
+ * M[B,N,N] the feature cost (any matrix: used as given, not clamped), C1[B,N,N] / C2[B,N,N] the two structures, p[B,N] / q[B,N] the marginals or NULL
+ * (uniform), G0[B,N,N] the start plan or NULL (outer(p, q)); all fp32.  Entries of p / q may be ZERO (a node without mass): a rectangular pair
+ * n1 x n2 is passed embedded in N = max(n1, n2) with zero rows / columns of M, C1, C2 and zero weights, and its plan comes out in the leading
+ * n1 x n2 block, every other entry exactly zero.
+ * params: alpha, epsilon, loss_fun as everywhere; max_iter and tol are the SOLVE's cap and tolerance on ||T - Tprev|| (checked at every 10th
+ * iteration, bregman.py:119,144-147 / :238,252-255); num_iter_max / stop_thr the Sinkhorn keywords numItermax / stopThr (unused by solver 2);
+ * inner_tol, fixed_*, warmstart and cs_small_int are ignored.  solver 0 / 1 / 2 = PGD / PPA / BAPG, symmetric 1 / 0 / -1 = True / False / None as in
+ * conan_fgw_barycenter_fwd_sym.
+ * Outputs: T[B,N,N]; fgw_dist[B] or NULL (not wanted): conan_fgw_pair_dist of the returned T, same bits; info[B,4] int32 = {PGD / PPA / BAPG
+ * iterations, Sinkhorn iterations (0 for BAPG), flags, symmetric decision taken (1 / 0)}, flags bit 2: an iterate had a zero row or column sum
+ * at a node WITH mass (the reference's NaN case); errs[B, ceil(max_iter / 10)] fp32: ||T - Tprev||_F of every check (the reference's
+ * log["err"]), formed in fp64 and rounded once, NaN where not executed.
+ * Workspace: conan_fgw_pair_workspace_bytes with the same B, N, solver and symmetric (0 for what the solve refuses).  CONAN_E_BADARG, before any
+ * launch, for a null required pointer, B <= 0, N <= 0, max_iter <= 0, a solver outside 0..2, a symmetric outside -1..1 or an unknown loss_fun. */
+long long conan_fgw_pair_workspace_bytes(int B, int N, int solver, int symmetric);
+int conan_fgw_pair_fwd(const float *M, const float *C1, const float *C2, const float *p, const float *q, const float *G0, int B, int N,
+                       const conan_fgw_params *params /* (host) */, int solver, int symmetric, float *T, float *fgw_dist, int *info,
+                       float *errs, void *workspace, void *stream);
+/* out[b] = (1 - alpha) sum(M * T) + alpha sum((constC - h1(C1) T h2(C2)^T) * T) with constC, h1, h2 = init_matrix(C1, C2, p, q, loss_fun)
+ * (bregman.py:163-164, utils.py:4-64): the reference's log["fgw_dist"] of any plan T[B,N,N], also after an asymmetric solve (it uses the
+ * problem itself, never its transpose).  loss_fun 0 = square, 1 = KL; p / q NULL = uniform.  fp64 sums in a fixed order, no atomics: the same
+ * bits on every run and in every batch.  CONAN_E_UNSUPPORTED above N ~ 1000 (16 rows of C1 T no longer fit in LDS). */
+int conan_fgw_pair_dist(const float *M, const float *C1, const float *C2, const float *p, const float *q, const float *T, int B, int N,
+                        float alpha, int loss_fun, float *out, void *stream);
+
 /* dYs[b,s,j,:] = lambdas[s] * sum_i T[b,s,i,j] * (1/p[b,i]) * dY[b,i,:]  — the whole backward of the block given the
  * saved couplings (the reference solves them under torch.no_grad(), barycenter.py:120). */
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,

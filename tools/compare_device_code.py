@@ -1,11 +1,14 @@
 """Are the gfx950 kernels of two builds of an object file the same machine code?
 
-    python tools/compare_device_code.py OLD_DIR NEW_DIR [name.o ...]        (default: fgw.o fgw_small.o fgw_bapg.o fgw_grad.o)
+    python tools/compare_device_code.py [--allow-new] OLD_DIR NEW_DIR [name.o ...]        (default: fgw.o fgw_small.o fgw_bapg.o fgw_grad.o)
 
 For every object file, built with the Makefile's flags in both directories, the gfx950 code object is extracted (llvm-objdump --offloading)
 and three things are compared per kernel symbol, whatever the order of the kernels in the file: the set of kernel names, each kernel's
 metadata (llvm-readelf --notes: VGPRs, SGPRs, LDS, scratch, kernarg size) and each kernel's disassembly with addresses stripped.  A change
 that touches host code only must leave all three identical: that is the proof that no kernel and no set of template instantiations moved.
+--allow-new: a change that ADDS kernels (new instantiations, new templates) — symbols that only the new build has are counted, not reported as
+differences; every symbol of the old build must still be there with the same metadata and code.  The padding behind the last instruction of a
+symbol (s_nop up to the next alignment boundary, or the end of the section) belongs to the layout of the file, not to the symbol, and is dropped.
 Prints one line per object file and exits 1 on any difference.  Needs no GPU."""
 import os
 import re
@@ -73,16 +76,22 @@ def disassembly(co):
             out[name] = []
         elif name is not None:
             out[name].append(re.sub(r"// [0-9A-F]+: ", "// ", line.rstrip()))          # (every line carries its own address in a comment)
+    for v in out.values():
+        while v and (not v[-1].strip() or v[-1].strip() == "..." or re.match(r"^\ts_nop 0\s", v[-1])):
+            v.pop()
     return {k: "\n".join(v) for k, v in out.items()}
 
 
-def compare(old, new):
-    """List of differences between two object files (empty: identical device code)."""
+def compare(old, new, allow_new=False):
+    """List of differences between two object files (empty: identical device code), the number of kernels of the old one and of symbols only the
+    new one has (counted instead of listed with allow_new)."""
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         ca, cb = code_object(old, ta), code_object(new, tb)
         ma, mb, da, db = metadata(ca), metadata(cb), disassembly(ca), disassembly(cb)
-    diffs = [f"kernel only in old: {k}" for k in sorted(set(ma) - set(mb))] + [f"kernel only in new: {k}" for k in sorted(set(mb) - set(ma))]
-    diffs += [f"symbol only in old: {k}" for k in sorted(set(da) - set(db))] + [f"symbol only in new: {k}" for k in sorted(set(db) - set(da))]
+    diffs = [f"kernel only in old: {k}" for k in sorted(set(ma) - set(mb))] + [f"symbol only in old: {k}" for k in sorted(set(da) - set(db))]
+    added = [f"kernel only in new: {k}" for k in sorted(set(mb) - set(ma))] + [f"symbol only in new: {k}" for k in sorted(set(db) - set(da))]
+    if not allow_new:
+        diffs += added
     for k in sorted(set(ma) & set(mb)):
         if ma[k] != mb[k]:
             diffs.append(f"metadata differs: {k}: {ma[k]} -> {mb[k]}")
@@ -91,16 +100,19 @@ def compare(old, new):
             diffs.append(f"disassembly differs: {k}")
     missing = sorted(set(ma) - set(da))
     assert not missing, f"kernels without disassembly: {missing}"
-    return diffs, len(ma)
+    return diffs, len(ma), (len(set(mb) - set(ma)), len(set(db) - set(da)))
 
 
 def main(argv):
+    allow_new = "--allow-new" in argv
+    argv = [a for a in argv if a != "--allow-new"]
     old_dir, new_dir = argv[1], argv[2]
     names = argv[3:] or ["fgw.o", "fgw_small.o", "fgw_bapg.o", "fgw_grad.o"]
     bad = 0
     for n in names:
-        diffs, count = compare(os.path.join(old_dir, n), os.path.join(new_dir, n))
-        print(f"{n}: {count} kernels, " + ("names, metadata and disassembly identical" if not diffs else f"{len(diffs)} DIFFERENCES"))
+        diffs, count, (new_k, new_s) = compare(os.path.join(old_dir, n), os.path.join(new_dir, n), allow_new)
+        plus = f" (+ {new_k} new kernels, {new_s} new symbols)" if allow_new and new_s else ""
+        print(f"{n}: {count} kernels, " + ("names, metadata and disassembly identical" if not diffs else f"{len(diffs)} DIFFERENCES") + plus)
         for d in diffs:
             print("   ", d)
         bad += bool(diffs)
