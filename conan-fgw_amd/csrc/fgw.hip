@@ -16,7 +16,7 @@
 // 5-iteration scheme amplifies rounding; computing on-chip in fp64 puts this kernel on the fp64
 // side of that yard-stick at negligible cost (the per-molecule matrices are tiny and MI355X runs fp64 FMA at half the
 // fp32 rate).  exp() is evaluated as 2^n * v_exp_f32(frac) with the range reduction done in fp64 (1 ulp of fp32).
-#include "fgw_common.h"
+#include "fgw_coupling.h"
 #ifdef CONAN_FGW_PROFILE
 FGW_PROF_ACCESSOR(conan_debug_fgw_prof_large)
 FGW_PROF_TRACE_ACCESSOR(conan_debug_fgw_trace_large)
@@ -77,19 +77,15 @@ __global__ void k_fgw_init(const float *__restrict__ Cs, const float *__restrict
 // PAIR: the pair form (conan_fgw_pair_fwd: the reference's fgw(M, C1, C2, p, q), bregman.py:8-167, one workgroup per pair b, K = 1, d = 0).  The cost M is the
 // caller's [B,N,N] tensor (pr.M) instead of dist(Y, Z); C1 is the caller's structure, widened once into Cw by k_fgw_pair_init; the start plan is outer(p, q),
 // or the caller's G0, which the launcher copies into T and reads through the warm-start branch (outer = 1); prm.max_iter / prm.inner_tol are the solve's own
-// max_iter / tol; ||T - Tprev|| is written to pr.errs at every check; info[b] = {iterations, Sinkhorn iterations, flags, symmetric decision taken} by plain
-// stores; no update contributions.  The flag is a constant of the kernel, not a template parameter: a new parameter, defaulted or not, is part of
-// every instantiation's mangled name.  So the body is ONE text (fgw_coupling_body.inc) compiled into two kernel templates, k_fgw_coupling with PAIR = false —
-// its symbols, template arguments included, its registers and its code stay what they were — and k_fgw_coupling_pair with PAIR = true.
+// max_iter / tol; ||T - Tprev|| goes to pr.errs at every check; info[b] = {iterations, Sinkhorn iterations, flags, symmetric decision taken}; no update contributions.
+// The solve is fgw_coupling_solve (fgw_coupling.h): this kernel is its PAIR = false instantiations, k_fgw_coupling_pair (fgw_pair.hip) the PAIR = true ones.
 template <int MODE, bool KL, int NW, bool SECOND = false, bool PPA = false, bool ASYM = false>      // KL: loss_fun = "kl_loss"; SECOND: the pass behind k_fgw_coupling_big (see fgw_small.hip)
 __global__ void __launch_bounds__(64 * NW) k_fgw_coupling(
     const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb,
     FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw,
     const int *__restrict__ active, float *__restrict__ Tw, int *__restrict__ info, char *__restrict__ scratch,
     fgw_part_t *__restrict__ Ypart, fgw_part_t *__restrict__ Cpart, const int *__restrict__ only, FgwAdj adj) {
-    constexpr bool PAIR = false;
-    [[maybe_unused]] const FgwPair pr{};
-#include "fgw_coupling_body.inc"
+    fgw_coupling_solve<MODE, KL, NW, SECOND, PPA, ASYM, false>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, Yw, active, Tw, info, scratch, Ypart, Cpart, only, adj, FgwPair{});
 }
 
 // ------------------------------------------------------------------------------------------------ round-3 coupling kernel, N > 64

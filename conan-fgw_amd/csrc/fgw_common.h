@@ -81,7 +81,7 @@ struct FgwDims {
     int B, K, N, d, P;      // P = row pitch of the LDS/scratch matrices (odd => conflict-free column access)
 };
 
-// What the pair form of the general coupling kernels (PAIR: k_fgw_coupling_pair, k_fgw_coupling_bapg_pair) takes beyond the barycenter form's arguments:
+// What only the pair form of the general coupling solves reads (PAIR: k_fgw_coupling_pair, k_fgw_coupling_bapg_pair; the barycenter kernels pass it empty):
 // the caller's cost M [B,N,N] and the error list errs [B,nerr], nerr = ceil(max_iter / 10), one entry per check of ||T - Tprev||.
 struct FgwPair {
     const float *M;

@@ -1,5 +1,14 @@
-// Body of k_fgw_coupling and k_fgw_coupling_pair (fgw.hip), compiled once into each: the kernel's arguments by name, the template parameters MODE, KL, NW,
-// PPA, ASYM, and the constants SECOND, PAIR and `FgwPair pr` that the including kernel defines.  Not a translation unit of its own.
+#pragma once
+#include "fgw_common.h"
+namespace {
+// The general coupling solve, one per workgroup (SECOND: one per flagged coupling of the workgroup's 64): k_fgw_coupling (fgw.hip) and k_fgw_coupling_pair (fgw_pair.hip)
+// are this function.  Parameters and arguments are k_fgw_coupling's (described there), then PAIR and `pr` (by reference: by value measured slower); with PAIR, Yw, active, Ypart, Cpart, only and adj.rowptr are null.
+template <int MODE, bool KL, int NW, bool SECOND, bool PPA, bool ASYM, bool PAIR>
+__device__ __forceinline__ void fgw_coupling_solve(
+    const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb, FgwDims D, conan_fgw_params prm,
+    int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw, const int *__restrict__ active, float *__restrict__ Tw,
+    int *__restrict__ info, char *__restrict__ scratch, fgw_part_t *__restrict__ Ypart, fgw_part_t *__restrict__ Cpart, const int *__restrict__ only,
+    FgwAdj adj, const FgwPair &pr) {
     constexpr bool LDS_MODE = MODE == 2, MR_LDS = MODE >= 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = 64 * NW;
@@ -377,9 +386,7 @@
     if constexpr (PAIR) {
         int zero = 0;
         if constexpr (PPA) zero = __syncthreads_or(ppa_zero);
-        int sym_taken = 1;
-        if constexpr (ASYM) sym_taken = asym ? 0 : 1;
-        if (tid == 0) { info[b * 4 + 0] = cpt; info[b * 4 + 1] = sk_total; info[b * 4 + 2] = zero ? 4 : 0; info[b * 4 + 3] = sym_taken; }
+        if (tid == 0) { info[b * 4 + 0] = cpt; info[b * 4 + 1] = sk_total; info[b * 4 + 2] = zero ? 4 : 0; info[b * 4 + 3] = asym ? 0 : 1; }      // (asym: false without ASYM)
         return;
     }
     if constexpr (PPA) { if (__syncthreads_or(ppa_zero) && tid == 0) atomicOr(&info[b * 4 + 3], 4); }
@@ -416,3 +423,5 @@
             __syncthreads();                                            // LDS is re-staged by the next trip
         }
     }
+}
+}  // namespace

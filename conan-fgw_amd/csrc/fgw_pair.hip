@@ -1,28 +1,20 @@
 // The pair solve for gfx950: the reference's fgw(M, C1, C2, p, q, ...) (bregman.py:8-67 -> fgw_projected :70-167 / fgw_bregman :170-279) for B pairs of
 // attributed graphs at once, one workgroup per pair, with the reference's log: the error list and fgw_dist (bregman.py:149-150, :163-164).
-//
 //   k_fgw_pair_init              C1 widened to fp64, errs <- NaN, info <- 0
-//   k_fgw_coupling_pair          PGD / PPA: the body of k_fgw_coupling (fgw_coupling_body.inc) compiled with PAIR = true        (here)
-//   k_fgw_coupling_bapg_pair     BAPG: the body of k_fgw_coupling_bapg (fgw_bapg_body.inc) compiled with PAIR = true           (fgw_bapg.hip)
+//   k_fgw_coupling_pair          PGD / PPA: fgw_coupling_solve (fgw_coupling.h), the solve of k_fgw_coupling, with PAIR = true            (here)
+//   k_fgw_coupling_bapg_pair     BAPG: the body of k_fgw_coupling_bapg (fgw_bapg_body.inc) compiled with PAIR = true                    (fgw_bapg.hip)
 //   k_fgw_pair_dist              fgw_dist of the returned plan; also exported on its own (conan_fgw_pair_dist)
-//
-// What PAIR changes is described in front of k_fgw_coupling (fgw.hip); DESIGN.md 3.3, "Pair form".
-#include "fgw_common.h"
-
+#include "fgw_coupling.h"
 namespace {
-
-// The pair form.  Same arguments, of which it reads: Ys = M and Cs = C2 [B,N,N], ps = q and pb = p [B,N] (nullable: uniform), Cw = the widened C1, Tw = T
-// (in: G0 when outer = 1 and prm.warmstart), D = {B, 1, N, 0, P}, y_zero = 1 | (symmetric=None) << 1; Yw, active, Ypart, Cpart, only are unused (null).
+// The pair form (what PAIR changes: in front of k_fgw_coupling, fgw.hip; DESIGN.md 3.3, "Pair form"), under the barycenter form's names: Ys = M and Cs = C2 [B,N,N], ps = q and pb = p [B,N] (nullable: uniform), Cw = the widened C1, Tw = T (in: G0
+// when outer = 1 and prm.warmstart), D = {B, 1, N, 0, P}, y_zero = 1 | (symmetric=None) << 1.  What it has none of (Yw, active, Ypart, Cpart, only, adj) goes to the solve as constants.
 template <int MODE, bool KL, int NW, bool PPA, bool ASYM>
 __global__ void __launch_bounds__(64 * NW) k_fgw_coupling_pair(
     const float *__restrict__ Ys, const float *__restrict__ Cs, const float *__restrict__ ps, const float *__restrict__ pb,
-    FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, const double *__restrict__ Yw,
-    const int *__restrict__ active, float *__restrict__ Tw, int *__restrict__ info, char *__restrict__ scratch,
-    fgw_part_t *__restrict__ Ypart, fgw_part_t *__restrict__ Cpart, const int *__restrict__ only, FgwAdj adj, FgwPair pr) {
-    constexpr bool PAIR = true, SECOND = false;
-#include "fgw_coupling_body.inc"
+    FgwDims D, conan_fgw_params prm, int outer, int y_zero, const double *__restrict__ Cw, float *__restrict__ Tw, int *__restrict__ info,
+    char *__restrict__ scratch, FgwPair pr) {
+    fgw_coupling_solve<MODE, KL, NW, false, PPA, ASYM, true>(Ys, Cs, ps, pb, D, prm, outer, y_zero, Cw, nullptr, nullptr, Tw, info, scratch, nullptr, nullptr, nullptr, FgwAdj{}, pr);
 }
-
 // conan_fgw_pair_fwd's first launch: C1 widened to fp64 (the operand type of the coupling kernels' products), errs filled with NaN, info zeroed
 __global__ void __launch_bounds__(256) k_fgw_pair_init(const float *__restrict__ C1, double *__restrict__ C1w, int NN, float *__restrict__ errs, int nerr,
                                                        int *__restrict__ info) {
@@ -127,7 +119,7 @@ template <int MD>
 void launch_pair(const FgwPairCall &c, size_t lds_bytes, int solver) {
     with_flags([&](auto KL, auto PPA, auto ASYM) {
         launch_lds(k_fgw_coupling_pair<MD, KL.value, GEN_NW, PPA.value, ASYM.value>, c.D.B, 64 * GEN_NW, lds_bytes, c.s, c.M, c.C2, c.q, c.p, c.D, c.prm,
-                   c.warm, 1 | (c.symmetric < 0 ? 2 : 0), c.C1w, nullptr, nullptr, c.T, c.info, c.scratch, nullptr, nullptr, nullptr, FgwAdj{}, c.pr);
+                   c.warm, 1 | (c.symmetric < 0 ? 2 : 0), c.C1w, c.T, c.info, c.scratch, c.pr);
     }, c.prm.loss_fun != 0, solver == 1, c.symmetric != 1);
 }
 

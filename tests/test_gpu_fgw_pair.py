@@ -7,6 +7,7 @@ calls bit for bit, symmetric=None, G0, the barycenter path on the same couplings
 import ctypes
 import math
 import os
+import re
 import warnings
 
 import numpy as np
@@ -222,18 +223,9 @@ def _structure(rng, n, dens):
     return (a | a.T).astype(np.float32)
 
 
-@pytest.mark.parametrize("solver,symmetric,eps", [("PGD", True, 0.1), ("PPA", True, 0.1), ("BAPG", True, 1.0), ("PGD", False, 0.1)])
-@pytest.mark.parametrize("N", [12, 33, 80])
-def test_same_couplings_as_the_barycenter_path(N, solver, symmetric, eps):
-    """One input graph, structure and features of the barycenter held fixed: the first outer iteration of fgw_barycenters IS one coupling solve
-    with M = dist(Y0, Z), max_iter = m and tol = 1e-4.  At N <= 64 the PGD / symmetric barycenter runs the register-resident kernels.
-    m = 12 puts a second check of ||T - Tprev|| (iteration 10) inside the solve.  Not at N = 80 with PGD / symmetric: there the barycenter runs
-    k_fgw_coupling_big, which forms the error against Tprev only at iteration 0 (its later checks compare with zero, so it never stops early
-    after the first: built for the models' max_iter = 5, DESIGN.md 3.3 "Pair form") — on this problem the reference's own fp64 run stops at 11
-    iterations (error 6.9e-10 at the second check) and so does the pair form, the big kernel runs all 12.  The two paths are the same loop up to
-    the first ten iterations, so that case is compared at m = 10."""
+def _same_couplings(N, solver, symmetric, eps, m):
     rng = np.random.RandomState(100 + N)
-    m, d = (10 if N > 64 and solver == "PGD" and symmetric else 12), 4
+    d = 4
     Y0, Z = t(rng.uniform(0.1, 1.0, size=(N, d))), t(rng.uniform(0.1, 1.0, size=(N, d)))
     C1, C2 = t(_structure(rng, N, 0.3)), t(_structure(rng, N, 0.3))
     _, _, log = pfgw.fgw_barycenters(N, [Z], [C2], init_C=C1, init_Y=Y0, fixed_structure=True, fixed_features=True, max_iter=m, log=True,
@@ -244,6 +236,41 @@ def test_same_couplings_as_the_barycenter_path(N, solver, symmetric, eps):
     print(f"N {N} {solver}: iterations {plog['n_iter']} / {n_b}, rel {rel(T.cpu().numpy(), T_b.cpu().numpy()):.2e}")
     assert plog["n_iter"] == n_b
     assert rel(T.cpu().numpy(), T_b.cpu().numpy()) <= 1e-4
+
+
+@pytest.mark.parametrize("solver,symmetric,eps", [("PGD", True, 0.1), ("PPA", True, 0.1), ("BAPG", True, 1.0), ("PGD", False, 0.1)])
+@pytest.mark.parametrize("N", [12, 33, 80])
+def test_same_couplings_as_the_barycenter_path(N, solver, symmetric, eps):
+    """One input graph, structure and features of the barycenter held fixed: the first outer iteration of fgw_barycenters IS one coupling solve
+    with M = dist(Y0, Z), max_iter = m and tol = 1e-4.  At N <= 64 the PGD / symmetric barycenter runs the register-resident kernels.
+    m = 12 puts a second check of ||T - Tprev|| (iteration 10) inside the solve.  Not at N = 80 with PGD / symmetric: there the barycenter runs
+    k_fgw_coupling_big, which forms the error against Tprev only at iteration 0 (its later checks compare with zero, so it never stops early
+    after the first: built for the models' max_iter = 5, DESIGN.md 3.3 "Pair form") — on this problem the reference's own fp64 run stops at 11
+    iterations (error 6.9e-10 at the second check) and so does the pair form, the big kernel runs all 12.  The two paths are the same loop up to
+    the first ten iterations, so that case is compared at m = 10."""
+    _same_couplings(N, solver, symmetric, eps, 10 if N > 64 and solver == "PGD" and symmetric else 12)
+
+
+def _smallest_n_with_no_matrix_in_lds():
+    """The smallest N at which general_mode (fgw_common.h) returns 0: the vectors, (6 + 2 GEN_NW) N + 16 doubles, and one N x (N | 1) fp64
+    matrix pass LDS_LIMIT.  The two constants are read from the header; the lines of the rule are demanded as they stand, so that a change
+    of the rule fails here instead of leaving mode 0 untested."""
+    with open(os.path.join(os.path.dirname(pfgw.__file__), "csrc", "fgw_common.h")) as f:
+        src = f.read()
+    nw = int(re.search(r"constexpr int GEN_NW = (\d+);", src).group(1))
+    limit = int(re.search(r"constexpr size_t LDS_LIMIT = (\d+) \* 1024;", src).group(1)) * 1024
+    for line in ("int fgw_pitch(int N) { return N | 1; }", "vec_c = (size_t)((6 + 2 * GEN_NW) * N + 16) * 8, mr_bytes = (size_t)N * pitch_of(N) * 8;",
+                 "mode = lc <= LDS_LIMIT ? 2 : (vec_c + mr_bytes <= LDS_LIMIT ? 1 : 0);"):
+        assert line in src, line
+    return next(N for N in range(2, 1024) if ((6 + 2 * nw) * N + 16) * 8 + N * (N | 1) * 8 > limit)
+
+
+@pytest.mark.parametrize("solver,symmetric", [("PPA", True), ("PGD", False)], ids=["ppa", "pgd_asym"])
+def test_same_couplings_with_every_matrix_in_the_global_scratch(solver, symmetric):
+    """At the smallest size at which the general coupling kernel keeps no matrix in LDS (133 with 8 wavefronts and 160 KiB), in the barycenter
+    form and in the pair form: PPA and symmetric=False take that kernel in both (the goldens of the pair form at N = 140 pin PGD / symmetric
+    there against the reference)."""
+    _same_couplings(_smallest_n_with_no_matrix_in_lds(), solver, symmetric, 0.1, 10)
 
 
 def _conformers(G=6, n=14, moved=None):

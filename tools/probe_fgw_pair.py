@@ -11,8 +11,8 @@ after warm-up, median of --runs (>= 20) runs:
 
 Beside each, the SAME couplings through the entry point that existed before the pair form: ops.fgw_barycenter_batched with K = 1, init_C = C1,
 init_Y = Y0, fixed_structure and fixed_features, max_iter 5 — its first outer iteration is the coupling solve with M = dist(Y0, Z); the update
-finds nothing moved and the other four iterations' launches exit at once.  Those kernels are byte-identical to the parent commit's
-(tools/compare_device_code.py), so this column is the parent's number; at N <= 64 it is the register-resident path.  The plans of the two
+finds nothing moved and the other four iterations' launches exit at once.  At N <= 64 it is the register-resident path, at N = 83
+k_fgw_coupling_big; neither contains the general solve the pair form runs.  The plans of the two
 columns are compared (relative Frobenius error, printed) so that the timings are known to be of the same problem."""
 import argparse
 import json
