@@ -166,6 +166,7 @@ SIGNATURES = {
     "conan_fgw_pair_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "conan_fgw_pair_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(FgwParams), c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "conan_fgw_pair_dist": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P]),
+    "conan_fgw_pair_dist_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P]),
     "conan_fgw_barycenter_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "conan_fgw_barycenter_bwd_full_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "conan_fgw_barycenter_bwd_full": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

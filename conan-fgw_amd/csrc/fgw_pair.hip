@@ -4,6 +4,7 @@
 //   k_fgw_coupling_pair          PGD / PPA: fgw_coupling_solve (fgw_coupling.h), the solve of k_fgw_coupling, with PAIR = true            (here)
 //   k_fgw_coupling_bapg_pair     BAPG: the body of k_fgw_coupling_bapg (fgw_bapg_body.inc) compiled with PAIR = true                    (fgw_bapg.hip)
 //   k_fgw_pair_dist              fgw_dist of the returned plan; also exported on its own (conan_fgw_pair_dist)
+//   k_fgw_pair_dist_bwd          its gradient in M, C1, C2, p, q at a fixed plan (conan_fgw_pair_dist_bwd)
 #include "fgw_coupling.h"
 namespace {
 // The pair form (what PAIR changes: in front of k_fgw_coupling, fgw.hip; DESIGN.md 3.3, "Pair form"), under the barycenter form's names: Ys = M and Cs = C2 [B,N,N], ps = q and pb = p [B,N] (nullable: uniform), Cw = the widened C1, Tw = T (in: G0
@@ -84,6 +85,107 @@ __global__ void __launch_bounds__(64 * NW) k_fgw_pair_dist(const float *__restri
     if (tid == 0) out[b] = (float)total;
 }
 
+// The gradient of k_fgw_pair_dist's value at a FIXED plan T (the couplings are constants of the backward, as in fgw_grad.hip; DESIGN.md 3.3, "Pair
+// form: backward"), one workgroup per pair, g = gout[b], r = T 1, c = T^T 1:
+//     dM  = (1 - alpha) g T
+//     dC1 = alpha g (f1'(C1) o (r p^T) - T h2(C2) T^T)        dp_k = alpha g sum_i f1(C1_ik) r_i
+//     dC2 = alpha g (f2'(C2) o (c q^T) - (T^T C1 T) o h2'(C2))  dq_k = alpha g sum_j f2(C2_jk) c_j
+// with f1, f2, h2 of init_matrix (utils.py:20-32): square a^2, b^2, 2b; KL a log(a + 1e-15) - a, b, log(b + 1e-15).  No symmetry of C1 / C2 is assumed.
+// Each triple product is two fp64 MFMA products over blocks of R rows of the intermediate (T h2(C2) resp. T^T C1) held in LDS, the LDS layout of
+// k_fgw_pair_dist; the elementwise terms ride in the second product's epilogue.  A null output is skipped with its products.  Every sum is fp64 in a
+// fixed order, no atomics, nothing shared between workgroups: the same bits on every run and for every batch the pair is part of.
+template <bool KL, int NW>
+__global__ void __launch_bounds__(64 * NW) k_fgw_pair_dist_bwd(const float *__restrict__ C1, const float *__restrict__ C2, const float *__restrict__ p,
+                                                               const float *__restrict__ q, const float *__restrict__ T, const float *__restrict__ gout,
+                                                               int N, int R, float alpha_f, float *__restrict__ dM, float *__restrict__ dC1,
+                                                               float *__restrict__ dC2, float *__restrict__ dp, float *__restrict__ dq) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NT = 64 * NW;
+    const int b = blockIdx.x, P = fgw_pitch(N), NN = N * N;
+    const int tid = threadIdx.x;
+    double *pa = reinterpret_cast<double *>(smem), *qb = pa + N, *rs = pa + 2 * N, *cs = pa + 3 * N, *A = pa + 4 * N + 16;      // A [R,P]
+    C1 += (size_t)b * NN; C2 += (size_t)b * NN; T += (size_t)b * NN;
+    const double g = (double)gout[b], ag = (double)alpha_f * g;
+    for (int i = tid; i < N; i += NT) {
+        pa[i] = p ? (double)p[(size_t)b * N + i] : 1.0 / (double)N;
+        qb[i] = q ? (double)q[(size_t)b * N + i] : 1.0 / (double)N;
+    }
+    if (dC1 || dp) {                                                       // r = T 1: 8 lanes per row
+        constexpr int LPI = 8;
+        for (int i0 = 0; i0 < N; i0 += NT / LPI) {
+            const int i = i0 + tid / LPI, sub = tid % LPI;
+            double r = 0.0;
+            if (i < N)
+                for (int k = sub; k < N; k += LPI) r += (double)T[i * N + k];
+#pragma unroll
+            for (int o = 1; o < LPI; o <<= 1) r += __shfl_xor(r, o, 64);
+            if (i < N && sub == 0) rs[i] = r;
+        }
+    }
+    if (dC2 || dq)                                                         // c = T^T 1: one thread per column
+        for (int j = tid; j < N; j += NT) {
+            double c = 0.0;
+            for (int i = 0; i < N; ++i) c += (double)T[i * N + j];
+            cs[j] = c;
+        }
+    __syncthreads();
+    if (dM) {
+        const double s = (1.0 - (double)alpha_f) * g;
+        for (int t = tid; t < NN; t += NT) dM[(size_t)b * NN + t] = (float)(s * (double)T[t]);
+    }
+    if (dp)
+        for (int k = tid; k < N; k += NT) {
+            double s = 0.0;
+            for (int i = 0; i < N; ++i) {
+                const double a = (double)C1[i * N + k];
+                s += (KL ? a * log(a + 1e-15) - a : a * a) * rs[i];
+            }
+            dp[(size_t)b * N + k] = (float)(ag * s);
+        }
+    if (dq)
+        for (int k = tid; k < N; k += NT) {
+            double s = 0.0;
+            for (int j = 0; j < N; ++j) {
+                const double c2 = (double)C2[j * N + k];
+                s += (KL ? c2 : c2 * c2) * cs[j];
+            }
+            dq[(size_t)b * N + k] = (float)(ag * s);
+        }
+    if (dC1) {
+        dC1 += (size_t)b * NN;
+        for (int r0 = 0; r0 < N; r0 += R) {
+            const int rows = min(R, N - r0);
+            auto keep = [&](int i, int j, double v) { A[i * P + j] = v; };                                                      // A = T C2 (h2's 2: in the epilogue) / T log(C2 + 1e-15)
+            if constexpr (KL)
+                mm_f64<NW>(rows, N, N, [&](int i, int k) { return (double)T[(r0 + i) * N + k]; }, [&](int k, int j) { return log((double)C2[k * N + j] + 1e-15); }, keep);
+            else
+                mm_f64_glb<NW, false>(rows, N, N, T + (size_t)r0 * N, N, C2, N, keep);
+            __syncthreads();
+            mm_f64_glb<NW, true>(rows, N, N, A, P, T, N, [&](int i, int j, double v) {
+                const int at = (r0 + i) * N + j;
+                const double a = (double)C1[at], w = rs[r0 + i] * pa[j];
+                dC1[at] = (float)(ag * (KL ? (log(a + 1e-15) + a / (a + 1e-15) - 1.0) * w - v : 2.0 * (a * w - v)));
+            });
+            __syncthreads();
+        }
+    }
+    if (dC2) {
+        dC2 += (size_t)b * NN;
+        for (int r0 = 0; r0 < N; r0 += R) {
+            const int rows = min(R, N - r0);
+            mm_f64<NW>(rows, N, N, [&](int j, int i) { return (double)T[i * N + r0 + j]; }, [&](int i, int k) { return (double)C1[i * N + k]; },
+                       [&](int j, int k, double v) { A[j * P + k] = v; });                                                        // A = T^T C1
+            __syncthreads();
+            mm_f64_glb<NW, false>(rows, N, N, A, P, T, N, [&](int j, int l, double v) {
+                const int at = (r0 + j) * N + l;
+                const double c2 = (double)C2[at], w = cs[r0 + j] * qb[l];
+                dC2[at] = (float)(ag * (KL ? w - v / (c2 + 1e-15) : 2.0 * (c2 * w - v)));
+            });
+            __syncthreads();
+        }
+    }
+}
+
 // The workspace of conan_fgw_pair_fwd, described once like fgw_workspace; total = 0 for what the entry point refuses.
 FgwPairWorkspace fgw_pair_workspace(int B, int N, int solver, int symmetric) {
     FgwPairWorkspace w{};
@@ -115,6 +217,16 @@ int fgw_pair_dist_launch(const float *M, const float *C1, const float *C2, const
     else launch_lds(k_fgw_pair_dist<false, GEN_NW>, B, 64 * GEN_NW, bytes, s, M, C1, C2, p, q, T, N, R, alpha, out);
     return CONAN_OK;
 }
+// the backward shares k_fgw_pair_dist's LDS layout (four fp64 vectors and R rows of an intermediate product), so also its R
+int fgw_pair_dist_bwd_launch(const float *C1, const float *C2, const float *p, const float *q, const float *T, const float *gout, int B, int N, float alpha,
+                             int loss_fun, float *dM, float *dC1, float *dC2, float *dp, float *dq, hipStream_t s) {
+    size_t bytes = 0;
+    const int R = pair_dist_rows(N, &bytes);
+    if (R <= 0) return CONAN_E_UNSUPPORTED;
+    if (loss_fun) launch_lds(k_fgw_pair_dist_bwd<true, GEN_NW>, B, 64 * GEN_NW, bytes, s, C1, C2, p, q, T, gout, N, R, alpha, dM, dC1, dC2, dp, dq);
+    else launch_lds(k_fgw_pair_dist_bwd<false, GEN_NW>, B, 64 * GEN_NW, bytes, s, C1, C2, p, q, T, gout, N, R, alpha, dM, dC1, dC2, dp, dq);
+    return CONAN_OK;
+}
 template <int MD>
 void launch_pair(const FgwPairCall &c, size_t lds_bytes, int solver) {
     with_flags([&](auto KL, auto PPA, auto ASYM) {
@@ -134,6 +246,16 @@ int conan_fgw_pair_dist(const float *M, const float *C1, const float *C2, const 
                         int loss_fun, float *out, void *stream) {
     if (!M || !C1 || !C2 || !T || !out || B <= 0 || N <= 0 || (loss_fun != 0 && loss_fun != 1)) return CONAN_E_BADARG;
     const int rc = fgw_pair_dist_launch(M, C1, C2, p, q, T, B, N, alpha, loss_fun, out, as_stream(stream));
+    if (rc != CONAN_OK) return rc;
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+int conan_fgw_pair_dist_bwd(const float *C1, const float *C2, const float *p, const float *q, const float *T, const float *gout, int B, int N,
+                            float alpha, int loss_fun, float *dM, float *dC1, float *dC2, float *dp, float *dq, void *stream) {
+    if (!C1 || !C2 || !T || !gout || B <= 0 || N <= 0 || (loss_fun != 0 && loss_fun != 1)) return CONAN_E_BADARG;
+    if ((!dM && !dC1 && !dC2 && !dp && !dq) || (dp && !p) || (dq && !q)) return CONAN_E_BADARG;
+    const int rc = fgw_pair_dist_bwd_launch(C1, C2, p, q, T, gout, B, N, alpha, loss_fun, dM, dC1, dC2, dp, dq, as_stream(stream));
     if (rc != CONAN_OK) return rc;
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;

@@ -1,6 +1,7 @@
 """Functional boundary of the FGW solver, mirroring the reference's signature
 (conan_fgw/src/model/fgw/barycenter.py:7-31 `fgw_barycenters`, :393-399 `normalize_tensor`; bregman.py:8-279 `fgw`, `fgw_projected`,
-`fgw_bregman` — the coupling solve between two attributed graphs on its own, with `fgw_pairwise_distances` over an ensemble on top).
+`fgw_bregman` — the coupling solve between two attributed graphs on its own, with `fgw_distance`, its differentiable distance, and
+`fgw_pairwise_distances` over an ensemble on top).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
 barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
@@ -148,24 +149,44 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
 _FAILED = "Solver failed to produce a transport plan. You might want to increase the regularization parameter `epsilon`."
 
 
-def _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, log, num_iter_max=100, stop_thr=1e-5):
-    """One pair through ops.fgw_pair_batched (B = 1); the reference's return value."""
+def _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, log, num_iter_max=100, stop_thr=1e-5, distance=False):
+    """One pair through ops.fgw_pair_batched (B = 1); the reference's return value.  distance: through ops.fgw_pair_distance, fgw_distance's."""
     for name, t in (("M", M), ("C1", C1), ("C2", C2), ("p", p), ("q", q), ("G0", G0)):
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"fgw runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
     one = lambda t: None if t is None else t.unsqueeze(0)
-    T, dist, info, errs = ops.fgw_pair_batched(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter,
-                                               tol=tol, num_iter_max=num_iter_max, stop_thr=stop_thr, loss_fun=loss_fun, solver=solver,
-                                               symmetric=symmetric, with_dist=bool(log))
+    kw = dict(alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, num_iter_max=num_iter_max, stop_thr=stop_thr, loss_fun=loss_fun, solver=solver,
+              symmetric=symmetric)
+    if distance:
+        dist, T, info, errs = ops.fgw_pair_distance(one(M), one(C1), one(C2), one(p), one(q), one(G0), return_plan=True, **kw)
+    else:
+        T, dist, info, errs = ops.fgw_pair_batched(one(M), one(C1), one(C2), one(p), one(q), one(G0), with_dist=bool(log), **kw)
     T = T[0]
     # bregman.py:159-162 (PGD / PPA: the plan's total mass) and :267-270 (BAPG: a NaN), one host synchronisation as in the reference
     failed = bool(torch.isnan(T).any()) if solver == "BAPG" else bool(abs(T.sum() - 1) > 1e-5)
     if failed:
         warnings.warn(_FAILED)
     if not log:
-        return T
+        return dist[0] if distance else T
     n_iter, n_sk = int(info[0, 0].item()), int(info[0, 1].item())
-    return T, {"err": [errs[0, i] for i in range((n_iter + 9) // 10)], "fgw_dist": dist[0], "n_iter": n_iter, "n_sinkhorn": n_sk}
+    log_ = {"err": [errs[0, i] for i in range((n_iter + 9) // 10)], "fgw_dist": dist[0].detach() if distance else dist[0], "n_iter": n_iter, "n_sinkhorn": n_sk}
+    if distance:
+        log_["T"] = T
+        return dist[0], log_
+    return T, log_
+
+
+def _check_projected(loss_fun, solver, method, warmstart, kwargs):
+    """fgw_projected's refusals, in its order -> the Sinkhorn keywords (numItermax, stopThr)."""
+    if solver not in ["PGD", "PPA"]:
+        raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA']." % solver)
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    if warmstart:
+        raise NotImplementedError("warmstart=True is broken in the reference (torch.log of a Python int, bregman.py:113) and not implemented here")
+    if str(method).lower() != "sinkhorn_log":
+        raise NotImplementedError("only method='sinkhorn_log' is implemented")
+    return int(kwargs.pop("numItermax", 100)), float(kwargs.pop("stopThr", 1e-5))          # sinkhorn.py:12-13
 
 
 def fgw_projected(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=100, tol=1e-5,
@@ -178,17 +199,9 @@ def fgw_projected(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1
     default crashes in torch.outer(None, None)); warmstart=True raises NotImplementedError (the reference's branch calls torch.log on a Python
     int and raises TypeError); a method other than "sinkhorn_log", CPU tensors ("GPU only") and verbose printing are not implemented
     (NotImplementedError for the first two, verbose is ignored); the outputs carry NO gradient (the reference would back-propagate through the
-    unrolled iterations; not built here)."""
-    if solver not in ["PGD", "PPA"]:
-        raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA']." % solver)
-    if loss_fun not in ("square_loss", "kl_loss"):
-        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
-    if warmstart:
-        raise NotImplementedError("warmstart=True is broken in the reference (torch.log of a Python int, bregman.py:113) and not implemented here")
-    if str(method).lower() != "sinkhorn_log":
-        raise NotImplementedError("only method='sinkhorn_log' is implemented")
-    num_iter_max = int(kwargs.pop("numItermax", 100))          # sinkhorn.py:12
-    stop_thr = float(kwargs.pop("stopThr", 1e-5))              # sinkhorn.py:13
+    unrolled iterations; not built here).  To train through the distance use fgw_distance (one pair) or fgw_pairwise_distances (an ensemble):
+    the gradient of fgw_dist at the returned plan."""
+    num_iter_max, stop_thr = _check_projected(loss_fun, solver, method, warmstart, kwargs)
     return _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, log, num_iter_max, stop_thr)
 
 
@@ -217,6 +230,25 @@ def fgw(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetri
     raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % solver)
 
 
+def fgw_distance(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=100, tol=1e-5,
+                 solver="PGD", method="sinkhorn_log", warmstart=False, verbose=False, log=False, **kwargs):
+    """The FGW distance of two attributed graphs as a differentiable value: fgw's arguments, defaults, errors and warning, and the value of its
+    log["fgw_dist"] bit for bit, as a 0-d tensor that carries gradients to M, C1, C2, p and q.  The gradient is that of
+    (1 - alpha) sum(M * T) + alpha gwloss(init_matrix(C1, C2, p, q, loss_fun), T) at the solve's plan T, held constant — the treatment the
+    barycenter gives its couplings (barycenter.py:120) — and NOT what the reference's log["fgw_dist"].backward() gives, which unrolls every Sinkhorn
+    sweep into the graph.  T and G0 get no gradient; there is no double backward.  A finite difference of this function moves the plan, so it does
+    not check this gradient.  log=True: (dist, {"T": the plan (no gradient), "err", "fgw_dist", "n_iter", "n_sinkhorn"})."""
+    if solver in ["PGD", "PPA"]:
+        num_iter_max, stop_thr = _check_projected(loss_fun, solver, method, warmstart, kwargs)
+    elif solver == "BAPG":
+        if loss_fun not in ("square_loss", "kl_loss"):
+            raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+        num_iter_max, stop_thr = 100, 1e-5
+    else:
+        raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % solver)
+    return _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, log, num_iter_max, stop_thr, distance=True)
+
+
 def feature_cost(Y: Tensor, Z: Tensor) -> Tensor:
     """dist(Y, Z) of the reference (utils.py:154-171): the squared Euclidean distances of the feature rows, clamped at 0 -> [n1,n2]."""
     return torch.clamp((Y * Y).sum(1)[:, None] + (Z * Z).sum(1)[None, :] - 2.0 * (Y @ Z.T), min=0)
@@ -227,13 +259,19 @@ def fgw_pairwise_distances(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, 
     """The FGW distance matrix of G attributed graphs (the conformers of an ensemble): Ys[g] [n_g,d] features, Cs[g] [n_g,n_g] structures, ps[g]
     node weights or None (uniform) -> [G,G], symmetric with a zero diagonal.  The G (G - 1) / 2 pairs a < b are solved in ONE
     ops.fgw_pair_batched call (the list form when the sizes differ) with M = feature_cost(Ys[a], Ys[b]), formed by torch per pair ahead of
-    the call; entry (a, b) is fgw(M, Cs[a], Cs[b], ps[a], ps[b], ..., log=True)'s log["fgw_dist"], bit for bit.  No gradient."""
+    the call; entry (a, b) is fgw(M, Cs[a], Cs[b], ps[a], ps[b], ..., log=True)'s log["fgw_dist"], bit for bit.
+    When any of Ys, Cs, ps requires grad the result carries gradients to them (earlier versions silently returned none): every entry is
+    fgw_distance's value with its gradient at the solved plan (ops.fgw_pair_distance); feature_cost, the stacking of the pairs and the scatter into
+    the matrix stay in torch and are differentiated by torch.  The values are the same bits either way; with no input requiring grad the calls issued
+    are the same as before."""
     G = len(Ys)
     if len(Cs) != G or (ps is not None and len(ps) != G):
         raise ValueError("Ys, Cs (and ps) must have one entry per graph")
     if not all(torch.is_tensor(t) and t.is_cuda for t in list(Ys) + list(Cs)):
         raise NotImplementedError("fgw_pairwise_distances runs on the GPU only: pass CUDA (ROCm) tensors")
-    Ys = [y.detach().to(torch.float32) for y in Ys]
+    grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in list(Ys) + list(Cs) + list(ps or []))
+    keep = (lambda t: t) if grad else (lambda t: t.detach())
+    Ys = [keep(y).to(torch.float32) for y in Ys]
     out = torch.zeros(G, G, dtype=torch.float32, device=Ys[0].device)
     ia, ib = torch.triu_indices(G, G, 1).tolist() if G > 1 else ([], [])
     if not ia:
@@ -243,10 +281,12 @@ def fgw_pairwise_distances(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, 
     Ms = [feature_cost(Ys[a], Ys[b]) for a, b in zip(ia, ib)]
     pick = lambda ts, idx: None if ts is None else [ts[i] for i in idx]
     if len({int(y.shape[0]) for y in Ys}) == 1:
-        st = lambda ts: None if ts is None else torch.stack([t.detach().to(torch.float32) for t in ts])
-        dist = ops.fgw_pair_batched(torch.stack(Ms), st(pick(Cs, ia)), st(pick(Cs, ib)), st(pick(ps, ia)), st(pick(ps, ib)), **kw)[1]
+        st = lambda ts: None if ts is None else torch.stack([keep(t).to(torch.float32) for t in ts])
+        args = (torch.stack(Ms), st(pick(Cs, ia)), st(pick(Cs, ib)), st(pick(ps, ia)), st(pick(ps, ib)))
+        dist = ops.fgw_pair_distance(*args, **kw) if grad else ops.fgw_pair_batched(*args, **kw)[1]
     else:
-        dist = ops.fgw_pair_list(Ms, pick(Cs, ia), pick(Cs, ib), pick(ps, ia), pick(ps, ib), **kw)[1]
+        args = (Ms, pick(Cs, ia), pick(Cs, ib), pick(ps, ia), pick(ps, ib))
+        dist = ops.fgw_pair_distance_list(*args, **kw) if grad else ops.fgw_pair_list(*args, **kw)[1]
     out[ia, ib] = dist
     out[ib, ia] = dist
     return out

@@ -1025,12 +1025,50 @@ def _pair_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun
     return prm, FGW_SOLVERS[solver], _symmetric_code(None if symmetric is None else bool(symmetric))
 
 
-def _pair_tensor(t, name, *shape):
+def _pair_tensor(t, name, *shape, keep_graph=False):
     if not t.is_cuda:
         raise NotImplementedError(f"the pairwise FGW solve runs on the GPU only: {name} is a CPU tensor")
     if tuple(t.shape) != shape:
         raise ValueError(f"{name} must have shape {list(shape)}, not {list(t.shape)}")
-    return _c(t.detach().to(f32))
+    return _c((t if keep_graph else t.detach()).to(f32))
+
+
+def _pair_prepare(M, C1, C2, p, q, G0, keep_graph=False):
+    """The checked, contiguous fp32 operands of conan_fgw_pair_fwd, n1 != n2 embedded in N = max(n1, n2) with massless nodes -> (M, C1, C2, p, q, G0,
+    (B, N, n1, n2)).  keep_graph: the inputs are not detached, so that torch differentiates the conversion and the embedding (G0 never is)."""
+    if M.dim() != 3:
+        raise ValueError(f"M must be [B,n1,n2], not {list(M.shape)}")
+    B, n1, n2 = M.shape
+    kg = dict(keep_graph=keep_graph)
+    M, C1, C2 = _pair_tensor(M, "M", B, n1, n2, **kg), _pair_tensor(C1, "C1", B, n1, n1, **kg), _pair_tensor(C2, "C2", B, n2, n2, **kg)
+    p = None if p is None else _pair_tensor(p, "p", B, n1, **kg)
+    q = None if q is None else _pair_tensor(q, "q", B, n2, **kg)
+    G0 = None if G0 is None else _pair_tensor(G0, "G0", B, n1, n2)
+    dev, N = M.device, max(n1, n2)
+    if n1 != n2:
+        def pad(t, *shape):
+            out = torch.zeros(B, *shape, dtype=f32, device=dev)
+            out[(slice(None),) + tuple(slice(0, k) for k in t.shape[1:])] = t
+            return out
+        p = pad(torch.full((B, n1), 1.0 / n1, dtype=f32, device=dev) if p is None else p, N)
+        q = pad(torch.full((B, n2), 1.0 / n2, dtype=f32, device=dev) if q is None else q, N)
+        M, C1, C2 = pad(M, N, N), pad(C1, N, N), pad(C2, N, N)
+        G0 = None if G0 is None else pad(G0, N, N)
+    return M, C1, C2, p, q, G0, (B, N, n1, n2)
+
+
+def _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, solver_code, sym_code, with_dist):
+    """conan_fgw_pair_fwd on prepared operands -> T [B,N,N], fgw_dist [B] or None, info, errs."""
+    dev = M.device
+    T = torch.empty(B, N, N, dtype=f32, device=dev)
+    dist = torch.empty(B, dtype=f32, device=dev) if with_dist else None
+    info = torch.empty(B, 4, dtype=i32, device=dev)
+    errs = torch.empty(B, (prm.max_iter + 9) // 10, dtype=f32, device=dev)
+    import ctypes
+    ws = torch.empty(int(lib().conan_fgw_pair_workspace_bytes(B, N, solver_code, sym_code)), dtype=torch.uint8, device=dev)
+    call("conan_fgw_pair_fwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, ctypes.byref(prm), solver_code, sym_code,
+         ptr(T), ptr(dist), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+    return T, dist, info, errs
 
 
 def fgw_pair_batched(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, G0: Optional[Tensor] = None, *,
@@ -1044,40 +1082,16 @@ def fgw_pair_batched(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = No
     max_iter / tol are the solve's own; num_iter_max / stop_thr the Sinkhorn keywords numItermax / stopThr; solver "PGD", "PPA" or "BAPG";
     symmetric True, False or None (decided per pair by torch.allclose(C, C^T, atol=1e-10) on C1 and C2, inside the kernel).  n1 != n2 is solved
     embedded in a square problem of max(n1, n2) nodes whose extra nodes carry no mass (zero rows / columns of M, C1, C2, zero weights): the
-    leading block is the reference's rectangular problem.  Non-contiguous inputs are copied.  The outputs carry no gradient."""
+    leading block is the reference's rectangular problem.  Non-contiguous inputs are copied.  The outputs carry no gradient: fgw_pair_distance is
+    the same solve with a differentiable fgw_dist (the gradient at the returned plan)."""
     prm, solver_code, sym_code = _pair_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric)
-    if M.dim() != 3:
-        raise ValueError(f"M must be [B,n1,n2], not {list(M.shape)}")
-    B, n1, n2 = M.shape
-    M, C1, C2 = _pair_tensor(M, "M", B, n1, n2), _pair_tensor(C1, "C1", B, n1, n1), _pair_tensor(C2, "C2", B, n2, n2)
-    p = None if p is None else _pair_tensor(p, "p", B, n1)
-    q = None if q is None else _pair_tensor(q, "q", B, n2)
-    G0 = None if G0 is None else _pair_tensor(G0, "G0", B, n1, n2)
-    dev, N = M.device, max(n1, n2)
-    if n1 != n2:
-        def pad(t, *shape):
-            out = torch.zeros(B, *shape, dtype=f32, device=dev)
-            out[(slice(None),) + tuple(slice(0, k) for k in t.shape[1:])] = t
-            return out
-        p = pad(torch.full((B, n1), 1.0 / n1, dtype=f32, device=dev) if p is None else p, N)
-        q = pad(torch.full((B, n2), 1.0 / n2, dtype=f32, device=dev) if q is None else q, N)
-        M, C1, C2 = pad(M, N, N), pad(C1, N, N), pad(C2, N, N)
-        G0 = None if G0 is None else pad(G0, N, N)
-    T = torch.empty(B, N, N, dtype=f32, device=dev)
-    dist = torch.empty(B, dtype=f32, device=dev) if with_dist else None
-    info = torch.empty(B, 4, dtype=i32, device=dev)
-    errs = torch.empty(B, (prm.max_iter + 9) // 10, dtype=f32, device=dev)
-    import ctypes
-    ws = torch.empty(int(lib().conan_fgw_pair_workspace_bytes(B, N, solver_code, sym_code)), dtype=torch.uint8, device=dev)
-    call("conan_fgw_pair_fwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, ctypes.byref(prm), solver_code, sym_code,
-         ptr(T), ptr(dist), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+    M, C1, C2, p, q, G0, (B, N, n1, n2) = _pair_prepare(M, C1, C2, p, q, G0)
+    T, dist, info, errs = _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, solver_code, sym_code, with_dist)
     return (T if n1 == n2 else T[:, :n1, :n2]), dist, info, errs
 
 
-def fgw_pair_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
-    """fgw_pair_batched for pairs of different sizes: Ms[b] [n1_b,n2_b], C1s[b], C2s[b], ps[b] / qs[b] / G0s[b] (the lists, or single entries,
-    may be None).  Every pair is embedded in the common Np = max over all n1_b, n2_b with massless nodes and the batch is ONE launch.
-    Returns ([T_b [n1_b,n2_b]], fgw_dist [B], info [B,4], errs)."""
+def _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s, keep_graph=False):
+    """The ragged pairs of fgw_pair_list embedded in the common Np = max over all n1_b, n2_b -> (M, C1, C2, p, q, G0, sizes)."""
     B = len(Ms)
     if B == 0 or len(C1s) != B or len(C2s) != B:
         raise ValueError("Ms, C1s and C2s must be non-empty lists of the same length")
@@ -1088,38 +1102,108 @@ def fgw_pair_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
     sizes = [tuple(int(k) for k in m.shape) for m in Ms]
     Np = max(max(s) for s in sizes)
 
-    def stack(ts, cols, default=None):
+    def stack(ts, cols, default=None, keep=keep_graph):
         out = torch.zeros(B, *([Np] * cols), dtype=f32, device=dev)
         for b in range(B):
             t = ts[b] if ts is not None and ts[b] is not None else default(b)
-            out[(b,) + tuple(slice(0, k) for k in t.shape)] = t.detach().to(f32)
+            out[(b,) + tuple(slice(0, k) for k in t.shape)] = (t if keep else t.detach()).to(f32)
         return out
 
     G0 = None
     if G0s is not None and any(g is not None for g in G0s):
         if any(g is None for g in G0s):
             raise ValueError("G0s must hold a start plan for every pair or for none")
-        G0 = stack(G0s, 2)
-    T, dist, info, errs = fgw_pair_batched(
-        stack(Ms, 2), stack(C1s, 2), stack(C2s, 2), stack(ps, 1, lambda b: torch.full((sizes[b][0],), 1.0 / sizes[b][0], device=dev)),
-        stack(qs, 1, lambda b: torch.full((sizes[b][1],), 1.0 / sizes[b][1], device=dev)), G0, **params)
-    return [T[b, :sizes[b][0], :sizes[b][1]] for b in range(B)], dist, info, errs
+        G0 = stack(G0s, 2, keep=False)
+    return (stack(Ms, 2), stack(C1s, 2), stack(C2s, 2), stack(ps, 1, lambda b: torch.full((sizes[b][0],), 1.0 / sizes[b][0], device=dev)),
+            stack(qs, 1, lambda b: torch.full((sizes[b][1],), 1.0 / sizes[b][1], device=dev)), G0, sizes)
+
+
+def fgw_pair_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
+    """fgw_pair_batched for pairs of different sizes: Ms[b] [n1_b,n2_b], C1s[b], C2s[b], ps[b] / qs[b] / G0s[b] (the lists, or single entries,
+    may be None).  Every pair is embedded in the common Np = max over all n1_b, n2_b with massless nodes and the batch is ONE launch.
+    Returns ([T_b [n1_b,n2_b]], fgw_dist [B], info [B,4], errs).  No gradient: fgw_pair_distance_list is the differentiable form."""
+    M, C1, C2, p, q, G0, sizes = _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s)
+    T, dist, info, errs = fgw_pair_batched(M, C1, C2, p, q, G0, **params)
+    return [T[b, :n1, :n2] for b, (n1, n2) in enumerate(sizes)], dist, info, errs
+
+
+class _FgwPairDistFn(torch.autograd.Function):
+    """fgw_dist of B square pairs as a differentiable value: forward runs `run()` -> (dist [B], T [B,N,N], info, errs) (the solve with its own
+    distance kernel, or conan_fgw_pair_dist of a given plan: the distance is never formed twice), backward is conan_fgw_pair_dist_bwd at that
+    plan, which is a constant (the reference solves the barycenter's couplings under torch.no_grad() too, barycenter.py:120).  M, C1, C2 [B,N,N]
+    and p, q [B,N] or None are the prepared fp32 operands; only the gradients that are needed are computed.  No double backward."""
+    @staticmethod
+    def forward(ctx, M, C1, C2, p, q, run, alpha, loss_code):
+        dist, T, info, errs = run()
+        ctx.save_for_backward(C1, C2, p, q, T)
+        ctx.alpha, ctx.loss_code = float(alpha), int(loss_code)
+        ctx.mark_non_differentiable(*(t for t in (T, info, errs) if t is not None))
+        return dist, T, info, errs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        C1, C2, p, q, T = ctx.saved_tensors
+        B, N, _n = T.shape
+        want = ctx.needs_input_grad[:5]
+        out = [torch.empty(B, *([N] * k), dtype=f32, device=T.device) if w else None for w, k in zip(want, (2, 2, 2, 1, 1))]
+        call("conan_fgw_pair_dist_bwd", ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(T, f32), ptr(_c(g.to(f32)), f32), B, N, ctx.alpha, ctx.loss_code,
+             *(ptr(t) for t in out), stream_ptr())
+        return (*out, None, None, None)
+
+
+_LOSS_CODE = {"square_loss": 0, "kl_loss": 1}
+
+
+def fgw_pair_distance(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, G0: Optional[Tensor] = None, *,
+                      alpha: float = 0.5, epsilon: float = 0.1, max_iter: int = 100, tol: float = 1e-5, num_iter_max: int = 100,
+                      stop_thr: float = 1e-5, loss_fun: str = "square_loss", solver: str = "PGD", symmetric=None, return_plan: bool = False):
+    """The FGW distances of B pairs as a loss: fgw_pair_batched's solve (same arguments, same launch, same bits of fgw_dist) -> dist [B], which
+    carries gradients to M, C1, C2, p and q — those of (1 - alpha) sum(M * T) + alpha gwloss(init_matrix(C1, C2, p, q), T) at the RETURNED plan T,
+    held constant (conan_fgw_pair_dist_bwd).  This is not the reference's log["fgw_dist"].backward(), which unrolls every Sinkhorn sweep.  T and G0
+    get no gradient; no double backward.  Rectangular pairs are embedded as in fgw_pair_batched and the gradients come back in the caller's
+    shapes; only the gradients of inputs that require grad are computed.  return_plan: (dist, T [B,n1,n2], info, errs), the last three without
+    gradient."""
+    prm, solver_code, sym_code = _pair_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric)
+    M, C1, C2, p, q, G0, (B, N, n1, n2) = _pair_prepare(M, C1, C2, p, q, G0, keep_graph=True)
+
+    def run():
+        T, dist, info, errs = _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, solver_code, sym_code, True)
+        return dist, T, info, errs
+
+    dist, T, info, errs = _FgwPairDistFn.apply(M, C1, C2, p, q, run, alpha, prm.loss_fun)
+    return (dist, (T if n1 == n2 else T[:, :n1, :n2]), info, errs) if return_plan else dist
+
+
+def fgw_pair_distance_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, *, return_plan: bool = False, **params):
+    """fgw_pair_distance for pairs of different sizes (the lists of fgw_pair_list, one launch) -> dist [B]; with return_plan
+    (dist, [T_b [n1_b,n2_b]], info, errs)."""
+    M, C1, C2, p, q, G0, sizes = _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s, keep_graph=True)
+    dist, T, info, errs = fgw_pair_distance(M, C1, C2, p, q, G0, return_plan=True, **params)
+    return (dist, [T[b, :n1, :n2] for b, (n1, n2) in enumerate(sizes)], info, errs) if return_plan else dist
 
 
 def fgw_pair_dist(M: Tensor, C1: Tensor, C2: Tensor, T: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, *, alpha: float = 0.5,
                   loss_fun: str = "square_loss") -> Tensor:
     """The reference's log["fgw_dist"] of the plans T [B,N,N] (conan_fgw_pair_dist; square problems: embed rectangular ones as fgw_pair_batched
-    does): (1 - alpha) sum(M * T) + alpha * gwloss(init_matrix(C1, C2, p, q, loss_fun), T), bregman.py:163-164 -> [B]."""
+    does): (1 - alpha) sum(M * T) + alpha * gwloss(init_matrix(C1, C2, p, q, loss_fun), T), bregman.py:163-164 -> [B].  When one of M, C1, C2, p, q
+    requires grad the result carries the gradient at the given plan to them (conan_fgw_pair_dist_bwd; T gets none); the value is the same."""
     if loss_fun not in ("square_loss", "kl_loss"):
         raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
     B, N, _ = M.shape
-    M, C1, C2, T = (_pair_tensor(t, n, B, N, N) for t, n in ((M, "M"), (C1, "C1"), (C2, "C2"), (T, "T")))
-    p = None if p is None else _pair_tensor(p, "p", B, N)
-    q = None if q is None else _pair_tensor(q, "q", B, N)
-    out = torch.empty(B, dtype=f32, device=M.device)
-    call("conan_fgw_pair_dist", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(T, f32), B, N, float(alpha),
-         {"square_loss": 0, "kl_loss": 1}[loss_fun], ptr(out), stream_ptr())
-    return out
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (M, C1, C2, p, q))
+    M, C1, C2 = (_pair_tensor(t, n, B, N, N, keep_graph=kg) for t, n in ((M, "M"), (C1, "C1"), (C2, "C2")))
+    T = _pair_tensor(T, "T", B, N, N)
+    p = None if p is None else _pair_tensor(p, "p", B, N, keep_graph=kg)
+    q = None if q is None else _pair_tensor(q, "q", B, N, keep_graph=kg)
+
+    def run():
+        out = torch.empty(B, dtype=f32, device=M.device)
+        call("conan_fgw_pair_dist", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(T, f32), B, N, float(alpha),
+             _LOSS_CODE[loss_fun], ptr(out), stream_ptr())
+        return out, T, None, None
+
+    return _FgwPairDistFn.apply(M, C1, C2, p, q, run, alpha, _LOSS_CODE[loss_fun])[0] if kg else run()[0]
 
 
 class _MseLossFn(torch.autograd.Function):

@@ -633,6 +633,18 @@ int conan_fgw_pair_fwd(const float *M, const float *C1, const float *C2, const f
  * bits on every run and in every batch.  CONAN_E_UNSUPPORTED above N ~ 1000 (16 rows of C1 T no longer fit in LDS). */
 int conan_fgw_pair_dist(const float *M, const float *C1, const float *C2, const float *p, const float *q, const float *T, int B, int N,
                         float alpha, int loss_fun, float *out, void *stream);
+/* The gradient of conan_fgw_pair_dist's out[b] at a FIXED plan T (T itself gets none: the plan is a constant of the backward, as the couplings are
+ * in conan_fgw_barycenter_bwd_full), times gout[B].  With r = T 1, c = T^T 1 and g = gout[b]:
+ *   dM = (1 - alpha) g T;   square loss: dC1 = alpha g (2 C1 o (r p^T) - 2 T C2 T^T), dC2 = alpha g (2 C2 o (c q^T) - 2 T^T C1 T),
+ *   dp = alpha g (C1 o C1)^T r, dq = alpha g (C2 o C2)^T c;   KL: dC1 = alpha g ((log(C1 + 1e-15) + C1 / (C1 + 1e-15) - 1) o (r p^T) - T log(C2 + 1e-15) T^T),
+ *   dC2 = alpha g (c q^T - (T^T C1 T) / (C2 + 1e-15)), dp = alpha g (C1 log(C1 + 1e-15) - C1)^T r, dq = alpha g C2^T c.
+ * No symmetry of C1 / C2 is assumed.  dM / dC1 / dC2 [B,N,N], dp / dq [B,N], fp32; any of them NULL = not wanted (its products are skipped, the buffer
+ * untouched).  p / q NULL = uniform.  fp64 sums in a fixed order, no atomics: the same bits on every run and in every batch.  No workspace.
+ * CONAN_E_BADARG, before any launch, for a null C1 / C2 / T / gout, all five outputs NULL, dp wanted with p NULL or dq with q NULL, B <= 0, N <= 0 or an
+ * unknown loss_fun; CONAN_E_UNSUPPORTED where conan_fgw_pair_dist is. */
+int conan_fgw_pair_dist_bwd(const float *C1, const float *C2, const float *p, const float *q, const float *T, const float *gout,
+                            int B, int N, float alpha, int loss_fun,
+                            float *dM, float *dC1, float *dC2, float *dp, float *dq, void *stream);
 
 /* dYs[b,s,j,:] = lambdas[s] * sum_i T[b,s,i,j] * (1/p[b,i]) * dY[b,i,:]  — the whole backward of the block given the
  * saved couplings (the reference solves them under torch.no_grad(), barycenter.py:120). */
