@@ -167,6 +167,9 @@ SIGNATURES = {
     "conan_fgw_pair_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(FgwParams), c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "conan_fgw_pair_dist": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P]),
     "conan_fgw_pair_dist_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P]),
+    "conan_sinkhorn_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
+    "conan_sinkhorn_lds_resident": (c_int, [c_int, c_int]),
+    "conan_sinkhorn_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_ll, c_float, c_int, c_int, c_float] + [_P] * 8),
     "conan_fgw_barycenter_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "conan_fgw_barycenter_bwd_full_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "conan_fgw_barycenter_bwd_full": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1206,6 +1206,151 @@ def fgw_pair_dist(M: Tensor, C1: Tensor, C2: Tensor, T: Tensor, p: Optional[Tens
     return _FgwPairDistFn.apply(M, C1, C2, p, q, run, alpha, _LOSS_CODE[loss_fun])[0] if kg else run()[0]
 
 
+# ------------------------------------------------------------------------------------------------ entropic OT on its own (sinkhorn.hip)
+SINKHORN_METHODS = {"sinkhorn_log": 0, "sinkhorn": 1}
+
+
+def _sinkhorn_tensor(t, name, shapes, dtype=f32, keep_graph=False):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise NotImplementedError(f"the Sinkhorn solve runs on the GPU only: {name} is a CPU tensor")
+    if tuple(t.shape) not in shapes:
+        raise ValueError(f"{name} must have shape {' or '.join(str(list(sh)) for sh in shapes)}, not {list(t.shape)}")
+    return _c((t if keep_graph else t.detach()).to(dtype))
+
+
+def _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=False):
+    """The checked, contiguous operands of conan_sinkhorn_fwd -> (M, a, b, wu, wv, n1, n2, (B, N1, N2, method code)).  M [B,N1,N2], or [N1,N2]
+    shared by the B problems of a / b / n1 / n2 (m_batch_stride = 0)."""
+    if method not in SINKHORN_METHODS:
+        raise ValueError("Unknown method '%s'." % method)
+    if not torch.is_tensor(M) or not M.is_cuda:
+        raise NotImplementedError("the Sinkhorn solve runs on the GPU only: M is a CPU tensor")
+    if M.dim() not in (2, 3):
+        raise ValueError(f"M must be [B,N1,N2] or [N1,N2], not {list(M.shape)}")
+    N1, N2 = int(M.shape[-2]), int(M.shape[-1])
+    if M.dim() == 3:
+        B = int(M.shape[0])
+    else:
+        B = next((int(t.shape[0]) for t in (b, a, n1, n2) if t is not None and t.dim() == (1 if t is n1 or t is n2 else 2)), 1)
+    M = _sinkhorn_tensor(M, "M", [(B, N1, N2), (N1, N2)], keep_graph=keep_graph)
+    vec = lambda t, name, n: None if t is None else _sinkhorn_tensor(t, name, [(B, n)] + ([(n,)] if B == 1 else []))
+    a, b = vec(a, "a", N1), vec(b, "b", N2)
+    wu, wv = (None, None) if warmstart is None else (vec(warmstart[0], "warmstart[0]", N1), vec(warmstart[1], "warmstart[1]", N2))
+    n1 = None if n1 is None else _sinkhorn_tensor(n1, "n1", [(B,)], i32)
+    n2 = None if n2 is None else _sinkhorn_tensor(n2, "n2", [(B,)], i32)
+    return M, a, b, wu, wv, n1, n2, (B, N1, N2, SINKHORN_METHODS[method])
+
+
+def _sinkhorn_fwd(M, a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr):
+    """conan_sinkhorn_fwd on prepared operands -> T [B,N1,N2], loss [B], log_u [B,N1], log_v [B,N2], info [B,4], errs.  No host synchronisation."""
+    dev = M.device
+    T = torch.empty(B, N1, N2, dtype=f32, device=dev)
+    loss = torch.empty(B, dtype=f32, device=dev)
+    log_u, log_v = torch.empty(B, N1, dtype=f32, device=dev), torch.empty(B, N2, dtype=f32, device=dev)
+    info = torch.empty(B, 4, dtype=i32, device=dev)
+    errs = torch.empty(B, (int(num_iter_max) + 9) // 10, dtype=f32, device=dev)
+    ws = torch.empty(max(int(lib().conan_sinkhorn_workspace_bytes(B, N1, N2)), 1), dtype=torch.uint8, device=dev)
+    call("conan_sinkhorn_fwd", ptr(M, f32), ptr(a), ptr(b), ptr(wu), ptr(wv), ptr(n1), ptr(n2), B, N1, N2, N1 * N2 if M.dim() == 3 else 0,
+         float(reg), code, int(num_iter_max), float(stop_thr), ptr(T), ptr(loss), ptr(log_u), ptr(log_v), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+    return T, loss, log_u, log_v, info, errs
+
+
+def sinkhorn_batched(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, *, reg: float, method: str = "sinkhorn_log",
+                     num_iter_max: int = 1000, stop_thr: float = 1e-9, warmstart=None, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None):
+    """B independent entropic OT problems in one launch (one workgroup per problem): the reference's sinkhorn_log (method "sinkhorn_log",
+    sinkhorn.py:318-450) or sinkhorn_knopp ("sinkhorn", :207-315).  M [B,N1,N2] costs, or [N1,N2] shared by the whole batch; a [B,N1] / b [B,N2]
+    marginals or None (uniform over the problem's own size); warmstart (log_u [B,N1], log_v [B,N2]) or None; n1 / n2 [B] int32 device tensors: the
+    problems' own sizes inside the container, or None.  Rectangular problems are solved as they are.
+    -> T [B,N1,N2], loss [B] = sum(M * T), log_u [B,N1], log_v [B,N2] (for "sinkhorn" the logs of its u, v), info [B,4] int32 = {niter (the
+    reference's log["niter"]), flags (bit 0: stopped on err < stop_thr, bit 1: Knopp's numerical-errors exit, bit 2: the exact log-domain path was
+    taken), checks executed, 0}, errs [B, ceil(num_iter_max / 10)] (log["err"]; NaN where not executed).  Outside a problem's own block every
+    output is zero.  A problem's bits do not depend on the batch, its position or the container.  The Knopp exit is decided on fp64 values, so it
+    follows the reference's fp64 run (fp32 exp underflows earlier).  No gradient (sinkhorn_loss is the differentiable form) and no host
+    synchronisation."""
+    M, a, b, wu, wv, n1, n2, (B, N1, N2, code) = _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method)
+    return _sinkhorn_fwd(M, a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr)
+
+
+def _sinkhorn_list_stack(Ms, as_, bs, warmstarts, container, keep_graph=False):
+    """Ragged problems in one container [B,N1,N2] (default: the largest n1 and n2) with their sizes on the device."""
+    B = len(Ms)
+    if B == 0:
+        raise ValueError("Ms must be a non-empty list")
+    for t in Ms:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise NotImplementedError("the Sinkhorn solve runs on the GPU only: got a CPU tensor")
+    dev = Ms[0].device
+    sizes = [tuple(int(k) for k in m.shape) for m in Ms]
+    N1, N2 = container if container is not None else (max(s[0] for s in sizes), max(s[1] for s in sizes))
+    if any(s[0] > N1 or s[1] > N2 for s in sizes):
+        raise ValueError("container is smaller than a problem")
+
+    def stack(ts, shape, axis, keep=False):
+        if ts is None or all(t is None for t in ts):
+            return None
+        out = torch.zeros(B, *shape, dtype=f32, device=dev)
+        for k in range(B):
+            t = ts[k]
+            if t is None or t.numel() == 0:       # uniform over the problem's own size
+                out[k, :sizes[k][axis]] = 1.0 / sizes[k][axis]
+            else:
+                out[(k,) + tuple(slice(0, n) for n in t.shape)] = (t if keep else t.detach()).to(f32)
+        return out
+
+    M = stack(Ms, (N1, N2), 0, keep=keep_graph)
+    warm = None
+    if warmstarts is not None and any(w is not None for w in warmstarts):
+        if any(w is None for w in warmstarts):
+            raise ValueError("warmstarts must hold a warm start for every problem or for none")
+        warm = (stack([w[0] for w in warmstarts], (N1,), 0), stack([w[1] for w in warmstarts], (N2,), 1))
+    n1 = torch.tensor([s[0] for s in sizes], dtype=i32, device=dev)
+    n2 = torch.tensor([s[1] for s in sizes], dtype=i32, device=dev)
+    return M, stack(as_, (N1,), 0), stack(bs, (N2,), 1), warm, n1, n2, sizes
+
+
+def sinkhorn_list(Ms, as_=None, bs=None, *, warmstarts=None, container=None, **params):
+    """sinkhorn_batched for problems of different sizes: Ms[k] [n1_k,n2_k], as_[k] / bs[k] / warmstarts[k] (the lists, or single entries of
+    as_ / bs, may be None: uniform).  ONE launch through the per-problem sizes: no problem is embedded in a larger one, each runs over its own
+    rows and columns inside the container (N1, N2) (default: the largest sizes).
+    -> ([T_k [n1_k,n2_k]], loss [B], [log_u_k], [log_v_k], info [B,4], errs)."""
+    M, a, b, warm, n1, n2, sizes = _sinkhorn_list_stack(Ms, as_, bs, warmstarts, container)
+    T, loss, lu, lv, info, errs = sinkhorn_batched(M, a, b, warmstart=warm, n1=n1, n2=n2, **params)
+    return ([T[k, :s[0], :s[1]] for k, s in enumerate(sizes)], loss, [lu[k, :s[0]] for k, s in enumerate(sizes)],
+            [lv[k, :s[1]] for k, s in enumerate(sizes)], info, errs)
+
+
+class _SinkhornLossFn(torch.autograd.Function):
+    """loss[B] = sum(M * T) of the solved plans as a differentiable value under the project's fixed-plan convention (fgw_pair_distance's): the
+    plan is a constant of the backward, dM = gout * T (a torch multiply on the saved plan), nothing flows to a, b or the warm start.  No double
+    backward."""
+    @staticmethod
+    def forward(ctx, M, run):
+        T, loss, log_u, log_v, info, errs = run()
+        ctx.save_for_backward(T)
+        ctx.shared = M.dim() == 2
+        ctx.mark_non_differentiable(T, log_u, log_v, info, errs)
+        return loss, T, log_u, log_v, info, errs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        (T,) = ctx.saved_tensors
+        dM = g.to(f32)[:, None, None] * T
+        return (dM.sum(0) if ctx.shared else dM), None
+
+
+def sinkhorn_loss(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, *, reg: float, method: str = "sinkhorn_log",
+                  num_iter_max: int = 1000, stop_thr: float = 1e-9, warmstart=None, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None,
+                  return_plan: bool = False):
+    """The entropic OT costs sum(M * T) of B problems as a loss: sinkhorn_batched's solve (same arguments, same launch, same bits) -> loss [B],
+    which carries the gradient at the RETURNED plan, held constant, to M: dM = gout * T.  This is not the reference's unrolled gradient through
+    every Sinkhorn sweep.  a, b and the warm start get none; no double backward; no host synchronisation.  return_plan: (loss, T, log_u, log_v,
+    info, errs), all but the first without gradient."""
+    Mp, a, b, wu, wv, n1, n2, (B, N1, N2, code) = _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=True)
+    out = _SinkhornLossFn.apply(Mp, lambda: _sinkhorn_fwd(Mp.detach(), a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr))
+    return out if return_plan else out[0]
+
+
 class _MseLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target):

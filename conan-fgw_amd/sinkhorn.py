@@ -1,0 +1,127 @@
+"""Entropic optimal transport, mirroring the reference's conan_fgw/src/model/fgw/sinkhorn.py: `sinkhorn`, `sinkhorn_log`, `sinkhorn_knopp` and
+`sinkhorn2` with its signatures and defaults, on the batched HIP kernel of csrc/sinkhorn.hip (one workgroup per problem, rectangular problems
+solved as they are), plus `wasserstein_pairwise_distances`, the alpha = 0 sibling of `fgw.fgw_pairwise_distances`.
+
+Same return values (`log=True`: the reference's dict), the same two warnings with the reference's texts, the same `ValueError` for an unknown
+method.  Deviations, each a `NotImplementedError`: the methods "greenkhorn", "sinkhorn_stabilized" and "sinkhorn_epsilon_scaling" are not built; a
+2-D `b` (several histograms at once) is not built (the reference's Knopp form stops all histograms jointly, which one workgroup per problem
+does not reproduce: loop over the columns, or stack them through ops.sinkhorn_batched with a shared M); CPU tensors (the solve runs on the GPU
+only).  `verbose` is ignored.  Outputs are fp32; the iteration runs in fp64, so iteration counts, the error list and the Knopp numerical-errors
+exit follow the reference's fp64 run, not its fp32 run (fp32 exp underflows earlier, and an fp32 run cannot reach stopThr = 1e-9).  The plan
+carries no gradient; `sinkhorn2`'s value carries the gradient to M at the returned plan, held constant (the project's fixed-plan convention,
+fgw.fgw_distance's), not the reference's gradient through the unrolled iterations; a, b and the warm start get none.
+"""
+from __future__ import annotations
+
+import warnings
+from typing import Optional, Sequence
+
+import torch
+from torch import Tensor
+
+from . import ops
+from .fgw import feature_cost
+
+_UNBUILT = ("greenkhorn", "sinkhorn_stabilized", "sinkhorn_epsilon_scaling")
+_NOT_CONVERGED = ("Sinkhorn did not converge. You might want to increase the number of iterations `numItermax` or the regularization "
+                  "parameter `reg`.")
+
+
+def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost=False):
+    """One problem through ops (B = 1) with the reference's return value and warnings (one host synchronisation, as fgw._pair_solve)."""
+    if b is not None and torch.is_tensor(b) and b.dim() > 1:
+        raise NotImplementedError("several histograms at once (a 2-D b) are not implemented: solve them one by one, or as a batch with a shared M "
+                                  "through ops.sinkhorn_batched")
+    tensors = [("M", M), ("a", a), ("b", b)] + ([] if warmstart is None else [("warmstart[0]", warmstart[0]), ("warmstart[1]", warmstart[1])])
+    for name, t in tensors:
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"sinkhorn runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    a = None if a is None or len(a) == 0 else a.unsqueeze(0)                # sinkhorn.py:221-224: an empty histogram means uniform
+    b = None if b is None or len(b) == 0 else b.unsqueeze(0)
+    warm = None if warmstart is None else (warmstart[0].unsqueeze(0), warmstart[1].unsqueeze(0))
+    kw = dict(reg=reg, method=method, num_iter_max=numItermax, stop_thr=stopThr, warmstart=warm)
+    if cost:
+        loss, T, log_u, log_v, info, errs = ops.sinkhorn_loss(M.unsqueeze(0), a, b, return_plan=True, **kw)
+    else:
+        T, loss, log_u, log_v, info, errs = ops.sinkhorn_batched(M.unsqueeze(0), a, b, **kw)
+    res = loss[0] if cost else T[0]
+    if not (log or warn or method == "sinkhorn"):
+        return res
+    niter, flags, nchk, _ = info[0].tolist()
+    if flags & 2:
+        warnings.warn("Warning: numerical errors at iteration %d" % niter)
+    elif not flags & 1 and warn:
+        warnings.warn(_NOT_CONVERGED)
+    if not log:
+        return res
+    log_ = {"err": [errs[0, i] for i in range(nchk)], "niter": niter}
+    if method == "sinkhorn_log":
+        log_["log_u"], log_["log_v"] = log_u[0], log_v[0]
+    log_["u"], log_["v"] = torch.exp(log_u[0]), torch.exp(log_v[0])
+    return res, log_
+
+
+def sinkhorn_knopp(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, **kwargs):
+    """The reference's sinkhorn_knopp (sinkhorn.py:207-315): T [n1,n2]; log=True: (T, {"err", "niter", "u", "v"}).  The numerical-errors exit
+    (a zero K^T u, a NaN or Inf in u or v: the previous u, v are returned, with the reference's warning) is decided on fp64 values."""
+    return _solve(a, b, M, reg, "sinkhorn", numItermax, stopThr, log, warn, warmstart)
+
+
+def sinkhorn_log(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, **kwargs):
+    """The reference's sinkhorn_log (sinkhorn.py:318-450): T [n1,n2]; log=True: (T, {"err", "niter", "log_u", "log_v", "u", "v"})."""
+    return _solve(a, b, M, reg, "sinkhorn_log", numItermax, stopThr, log, warn, warmstart)
+
+
+def sinkhorn(a, b, M, reg, method="sinkhorn_log", numItermax=100, stopThr=1e-5, verbose=False, log=False, warn=True, warmstart=None, **kwargs):
+    """The reference's sinkhorn (sinkhorn.py:6-91): the entropic OT plan between the histograms a [n1] and b [n2] (empty: uniform) for the cost
+    M [n1,n2], by method "sinkhorn_log" or "sinkhorn" (Knopp).  warmstart = (log_u, log_v) for both.  See the module docstring for the deviations."""
+    m = str(method).lower()
+    if m in _UNBUILT:
+        raise NotImplementedError(f"method='{method}' is not implemented on this backend: use 'sinkhorn_log' or 'sinkhorn'")
+    if m not in ops.SINKHORN_METHODS:
+        raise ValueError("Unknown method '%s'." % method)
+    return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart)
+
+
+def sinkhorn2(a, b, M, reg, method="sinkhorn", numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=False, warmstart=None, **kwargs):
+    """The reference's sinkhorn2 (sinkhorn.py:94-204): the transport cost sum(M * T) of the entropic plan as a 0-d tensor (log=True: with the
+    solver's log).  It carries the gradient dM = T at the returned plan, held constant; a and b get none."""
+    m = str(method).lower()
+    if m == "sinkhorn_stabilized":
+        raise NotImplementedError(f"method='{method}' is not implemented on this backend: use 'sinkhorn_log' or 'sinkhorn'")
+    if m not in ops.SINKHORN_METHODS:                                      # (the reference's sinkhorn2 knows neither greenkhorn nor epsilon scaling)
+        raise ValueError("Unknown method '%s'." % method)
+    return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True)
+
+
+def wasserstein_pairwise_distances(Ys: Sequence[Tensor], ps=None, reg=0.1, method="sinkhorn_log", numItermax=100, stopThr=1e-5) -> Tensor:
+    """The entropic Wasserstein cost matrix of G feature clouds (the conformers of an ensemble), the structure-free (alpha = 0) sibling of
+    fgw.fgw_pairwise_distances: Ys[g] [n_g,d], ps[g] weights or None (uniform) -> [G,G], symmetric with a zero diagonal.  The G (G - 1) / 2 pairs
+    a < b are solved in ONE launch (per-problem sizes when the clouds differ in size) with M = fgw.feature_cost(Ys[a], Ys[b]); entry (a, b) is
+    sinkhorn2(ps[a], ps[b], M, reg, method=method, numItermax=numItermax, stopThr=stopThr), bit for bit.  When any of Ys requires grad the result
+    carries gradients to them: sinkhorn2's fixed-plan gradient to every M, and torch's through feature_cost.  ps get none."""
+    G = len(Ys)
+    if ps is not None and len(ps) != G:
+        raise ValueError("Ys and ps must have one entry per cloud")
+    m = str(method).lower()
+    if m not in ops.SINKHORN_METHODS:
+        raise ValueError("Unknown method '%s'." % method)
+    if not all(torch.is_tensor(t) and t.is_cuda for t in Ys):
+        raise NotImplementedError("wasserstein_pairwise_distances runs on the GPU only: pass CUDA (ROCm) tensors")
+    Ys = [y.to(torch.float32) for y in Ys]
+    out = torch.zeros(G, G, dtype=torch.float32, device=Ys[0].device)
+    ia, ib = torch.triu_indices(G, G, 1).tolist() if G > 1 else ([], [])
+    if not ia:
+        return out
+    Ms = [feature_cost(Ys[i], Ys[j]) for i, j in zip(ia, ib)]
+    pick = lambda idx: None if ps is None else [ps[i] for i in idx]
+    kw = dict(reg=reg, method=m, num_iter_max=numItermax, stop_thr=stopThr)
+    if len({int(y.shape[0]) for y in Ys}) == 1:
+        st = lambda ts: None if ts is None else torch.stack([t.detach().to(torch.float32) for t in ts])
+        cost = ops.sinkhorn_loss(torch.stack(Ms), st(pick(ia)), st(pick(ib)), **kw)
+    else:
+        M, a, b, _w, n1, n2, _sizes = ops._sinkhorn_list_stack(Ms, pick(ia), pick(ib), None, None, keep_graph=True)
+        cost = ops.sinkhorn_loss(M, a, b, n1=n1, n2=n2, **kw)
+    out[ia, ib] = cost
+    out[ib, ia] = cost
+    return out

@@ -646,6 +646,32 @@ int conan_fgw_pair_dist_bwd(const float *C1, const float *C2, const float *p, co
                             int B, int N, float alpha, int loss_fun,
                             float *dM, float *dC1, float *dC2, float *dp, float *dq, void *stream);
 
+/* Entropic optimal transport on its own, B problems at once: the reference's sinkhorn_log (sinkhorn.py:318-450, method 0) and sinkhorn_knopp
+ * (:207-315, method 1), one workgroup per problem (sinkhorn.hip).
+ * M[B,N1,N2] the costs, problem b at M + b * m_batch_stride floats (0: one M shared by the whole batch); a[B,N1] / b[B,N2] the marginals or NULL
+ * (uniform over the problem's OWN size); warm_u[B,N1] / warm_v[B,N2] the warm start (log_u, log_v) or NULL; n1[B] / n2[B] int32 on the device: the
+ * problem's own size inside the [N1,N2] container, or NULL (N1 / N2).  Rectangular problems are solved as they are, and a problem's work and
+ * bits depend on its own size alone: the same bits alone, in any batch, at any position and in any container.  Entries of a / b may be zero
+ * (an exactly zero row / column, potential -inf).  reg, num_iter_max, stop_thr: the reference's reg, numItermax, stopThr.  fp32 in and out, fp64
+ * inside, every sum in a fixed order, no atomics.
+ * Method 0 runs the iteration in its scaling form on exp(Mr - max_i Mr) per column with a range guard, and falls back to the exact log-domain
+ * iteration when a sum leaves [1e-100, 1e100]; method 1 follows the reference's fp64 run, its numerical-errors exit included (decided on the
+ * fp64 values: fp32 exp underflows earlier than this does).
+ * Outputs: T[B,N1,N2]; loss[B] = sum(M o T) (fp64 sum, rounded once); log_u[B,N1], log_v[B,N2] the potentials (for method 1 the logs of its u, v);
+ * info[B,4] int32 = {niter (the reference's log["niter"]: the loop index at exit, num_iter_max - 1 when exhausted), flags, checks executed, 0},
+ * flags bit 0: stopped on err < stop_thr, bit 1: method 1 left on numerical errors (previous u, v restored), bit 2: method 0 took the exact
+ * log-domain path; errs[B, ceil(num_iter_max / 10)] fp32: the violation of the column marginal at every 10th iteration (log["err"]), formed in
+ * fp64, NaN where not executed.  Every output except T may be NULL.  Everything outside a problem's n1 x n2 block (and n1, n2 entries) is zero.
+ * The matrix is LDS-resident when the container fits: conan_sinkhorn_lds_resident(N1, N2) (host only; (16 + 3 N1 + 4 N2 + N1 (N2 | 1)) * 8
+ * bytes <= 160 KiB, e.g. 140 x 139), else it is streamed from the workspace.  Workspace: conan_sinkhorn_workspace_bytes(B, N1, N2) (0 for
+ * arguments the solve refuses).  CONAN_E_BADARG, before any launch, for a null M / T / workspace, B, N1, N2 or num_iter_max <= 0, a negative
+ * m_batch_stride, reg <= 0 or not finite, or a method outside 0..1; CONAN_E_UNSUPPORTED when the vectors alone exceed the LDS (N1, N2 ~ 5000). */
+long long conan_sinkhorn_workspace_bytes(int B, int N1, int N2);
+int conan_sinkhorn_lds_resident(int n1, int n2);
+int conan_sinkhorn_fwd(const float *M, const float *a, const float *b, const float *warm_u, const float *warm_v, const int *n1, const int *n2,
+                       int B, int N1, int N2, long long m_batch_stride, float reg, int method, int num_iter_max, float stop_thr, float *T,
+                       float *loss, float *log_u, float *log_v, int *info, float *errs, void *workspace, void *stream);
+
 /* dYs[b,s,j,:] = lambdas[s] * sum_i T[b,s,i,j] * (1/p[b,i]) * dY[b,i,:]  — the whole backward of the block given the
  * saved couplings (the reference solves them under torch.no_grad(), barycenter.py:120). */
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,
