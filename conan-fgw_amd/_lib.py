@@ -10,7 +10,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libconan_fgw_hip.so")
 _LIB = None
-ABI_VERSION = 5            # == CONAN_FGW_ABI_VERSION of include/conan_fgw_hip.h (tests/test_abi.py compares the two)
+ABI_VERSION = 6            # == CONAN_FGW_ABI_VERSION of include/conan_fgw_hip.h (tests/test_abi.py compares the two)
 
 c_int, c_float, c_void_p, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong
 
@@ -147,22 +147,11 @@ SIGNATURES = {
     "conan_visnet_gate_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "conan_fgw_densify": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P]),
     "conan_fgw_densify_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
-    "conan_fgw_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
-    "conan_fgw_barycenter_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, ctypes.POINTER(FgwParams),
+    "conan_fgw_workspace_bytes": (c_ll, [c_int] * 7),
+    "conan_fgw_barycenter_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, ctypes.POINTER(FgwParams), c_int, c_int,
                                          _P, _P, _P, _P, _P, _P, _P, _P]),
-    "conan_fgw_workspace_bytes_ragged": (c_ll, [c_int, c_int, c_int, c_int]),
     "conan_fgw_barycenter_fwd_ragged": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, ctypes.POINTER(FgwParams),
-                                                _P, _P, _P, _P, _P, _P, _P, _P]),
-    "conan_fgw_barycenter_fwd_solver": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, ctypes.POINTER(FgwParams),
-                                                _P, _P, _P, _P, _P, _P, _P, _P, c_int]),
-    "conan_fgw_barycenter_fwd_ragged_solver": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
-                                                       ctypes.POINTER(FgwParams), _P, _P, _P, _P, _P, _P, _P, _P, c_int]),
-    "conan_fgw_workspace_bytes_sym": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "conan_fgw_workspace_bytes_ragged_sym": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "conan_fgw_barycenter_fwd_sym": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, ctypes.POINTER(FgwParams),
-                                             _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int]),
-    "conan_fgw_barycenter_fwd_ragged_sym": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
-                                                    ctypes.POINTER(FgwParams), _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int]),
+                                                c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "conan_fgw_pair_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "conan_fgw_pair_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(FgwParams), c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "conan_fgw_pair_dist": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P]),

@@ -696,7 +696,7 @@ inline size_t big_lds(int N, bool c2_bytes) {
 }
 
 // Every region of the caller's workspace, in order (the table is in DESIGN.md, "FGW workspace"); total = 0 for a shape or a code that the
-// entry points refuse.  The size queries return `total`, the solve takes every pointer from the offsets: there is no second description.
+// entry points refuse.  The size query returns `total`, the solve takes every pointer from the offsets: there is no second description.
 FgwWorkspace fgw_workspace(int B, int K, int N, int d, bool ragged, int solver, int symmetric) {
     FgwWorkspace w{};
     if (B <= 0 || K <= 0 || N <= 0 || d <= 0 || solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return w;
@@ -749,10 +749,10 @@ void launch_general(const FgwCall &c, const FgwPlan &pl, int outer, int y_zero, 
                     pl.kl, pl.ppa, pl.asym);
 }
 
-// The one host driver of every forward entry point: PGD, PPA and BAPG, symmetric or not, dense or ragged, any N.
+// The one host driver of both forward entry points: PGD, PPA and BAPG, symmetric or not, dense or ragged, any N.
 int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
                  const float *init_Y, int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter,
-                 int *info, float *errs, void *workspace, void *stream, FgwAdj adj, int solver = 0, int symmetric = 1) {
+                 int *info, float *errs, void *workspace, void *stream, FgwAdj adj, int solver, int symmetric) {
     if (solver < 0 || solver > 2 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
     if (!Ys || !(Cs || (adj.gptr && adj.rowptr && adj.col && adj.tgt)) || !params || !Y || !C || !T || !info || !errs || !workspace || B <= 0 || K <= 0 || N <= 0 || d <= 0)
         return CONAN_E_BADARG;
@@ -834,70 +834,31 @@ int fgw_fwd_impl(const float *Ys, const float *Cs, const float *ps, const float 
     return CONAN_OK;
 }
 
-inline FgwAdj ragged_adj(const int *graph_ptr, const int *rowptr, const int *col, const int *tgt) {
-    return FgwAdj{graph_ptr, rowptr, col, tgt, nullptr, nullptr};
-}
-const FgwAdj DENSE_ADJ{};
-
 }  // namespace
 
 extern "C" {
 
-// The four size queries: one layout (fgw_workspace), asked for its total.
-long long conan_fgw_workspace_bytes(int B, int K, int N, int d) { return (long long)fgw_workspace(B, K, N, d, false, 0, 1).total; }
-long long conan_fgw_workspace_bytes_ragged(int B, int K, int N, int d) { return (long long)fgw_workspace(B, K, N, d, true, 0, 1).total; }
-long long conan_fgw_workspace_bytes_sym(int B, int K, int N, int d, int solver, int symmetric) {
-    return (long long)fgw_workspace(B, K, N, d, false, solver, symmetric).total;
-}
-long long conan_fgw_workspace_bytes_ragged_sym(int B, int K, int N, int d, int solver, int symmetric) {
-    return (long long)fgw_workspace(B, K, N, d, true, solver, symmetric).total;
+// The size query: the one layout (fgw_workspace), asked for its total.
+long long conan_fgw_workspace_bytes(int B, int K, int N, int d, int ragged, int solver, int symmetric) {
+    if (ragged != 0 && ragged != 1) return 0;
+    return (long long)fgw_workspace(B, K, N, d, ragged != 0, solver, symmetric).total;
 }
 
-// The six forward entry points: fgw_fwd_impl with dense (Cs) or ragged (the four lists) structure; it refuses a null among them.
+// The two forward entry points: fgw_fwd_impl with dense (Cs) or ragged (the four lists) structure; it refuses a null among them.
 int conan_fgw_barycenter_fwd(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
                              const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                             const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
-                             float *errs, void *workspace, void *stream) {
-    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream, DENSE_ADJ);
+                             const conan_fgw_params *params, int solver, int symmetric, float *Y, float *C, float *T, float *T_iter,
+                             int *info, float *errs, void *workspace, void *stream) {
+    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream, FgwAdj{}, solver,
+                        symmetric);
 }
 
 int conan_fgw_barycenter_fwd_ragged(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt, const float *ps,
                                     const float *p, const float *lambdas, const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                                    const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info, float *errs,
-                                    void *workspace, void *stream) {
+                                    const conan_fgw_params *params, int solver, int symmetric, float *Y, float *C, float *T, float *T_iter,
+                                    int *info, float *errs, void *workspace, void *stream) {
     return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        ragged_adj(graph_ptr, rowptr, col, tgt));
-}
-
-int conan_fgw_barycenter_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
-                                    const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                                    const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
-                                    float *errs, void *workspace, void *stream, int solver) {
-    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream, DENSE_ADJ, solver);
-}
-
-int conan_fgw_barycenter_fwd_ragged_solver(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
-                                           const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
-                                           int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T,
-                                           float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver) {
-    return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        ragged_adj(graph_ptr, rowptr, col, tgt), solver);
-}
-
-int conan_fgw_barycenter_fwd_sym(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
-                                 const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                                 const conan_fgw_params *params, float *Y, float *C, float *T, float *T_iter, int *info,
-                                 float *errs, void *workspace, void *stream, int solver, int symmetric) {
-    return fgw_fwd_impl(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream, DENSE_ADJ, solver,
-                        symmetric);
-}
-
-int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
-                                        const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
-                                        int B, int K, int N, int d, const conan_fgw_params *params, float *Y, float *C, float *T,
-                                        float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver, int symmetric) {
-    return fgw_fwd_impl(Ys, nullptr, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, Y, C, T, T_iter, info, errs, workspace, stream,
-                        ragged_adj(graph_ptr, rowptr, col, tgt), solver, symmetric);
+                        FgwAdj{graph_ptr, rowptr, col, tgt, nullptr, nullptr}, solver, symmetric);
 }
 
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,

@@ -18,7 +18,7 @@
 //
 // ASYM: symmetric=False / None (bregman.py:199-222): df(T) = -alpha (hC1 T hC2^T + hC1^T T hC2) + (1 - alpha) M.  The second product needs the
 // iterate after the first is done, so G1 = A hC2^T waits in one more fp64 matrix G (36 bytes per entry: LDS up to N = 64, else a scratch of
-// its own behind the regular workspace, conan_fgw_workspace_bytes_sym); C1^T is read through the element-reader form of the product.  Bit 1
+// its own behind the regular workspace, conan_fgw_workspace_bytes); C1^T is read through the element-reader form of the product.  Bit 1
 // of y_zero selects symmetric=None: torch.allclose(C1, C1^T, atol=1e-10) and the same for C2 (bregman.py:199-200), per coupling solve, and the
 // symmetric form when both hold.
 #include "fgw_common.h"

@@ -1051,7 +1051,7 @@ __device__ __forceinline__ void mm_lds2(int M, int Nn, int Kd, const TX *__restr
 
 // ---- host side of the solve: fgw.hip drives (fgw_fwd_impl), fgw_small.hip and fgw_bapg.hip launch their own kernels --------------------------
 
-// Byte offsets of the regions of the caller's workspace, in this order, and the total the size queries return (fgw_workspace in fgw.hip fills
+// Byte offsets of the regions of the caller's workspace, in this order, and the total the size query returns (fgw_workspace in fgw.hip fills
 // it, once per query and once per solve; the table is in DESIGN.md, "FGW workspace").
 struct FgwWorkspace {
     size_t Cw, Yw, active, scratch, order, Ypart, Cpart, zvec, yvec, redo, dense, asym, total;

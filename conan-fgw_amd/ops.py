@@ -5,6 +5,7 @@ libconan_fgw_hip.so.  All ops require CUDA(ROCm) tensors and raise otherwise.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -164,7 +165,6 @@ def flush_weight_gradients():
     global _pending
     if not _pending:
         return {}
-    import ctypes
     from ._lib import WgradJob, WgradSlabJob
     jobs = (WgradJob * len(_pending))()
     cur = torch.cuda.current_stream()
@@ -881,11 +881,12 @@ PROD_FGW = dict(alpha=0.1, epsilon=0.1, max_iter=5, tol=1e-2, inner_tol=1e-4, nu
                 fixed_structure=False, fixed_features=False, warmstart=True)       # schnet_no_sum.py:281-306
 
 
-FGW_SOLVERS = {"PGD": 0, "PPA": 1, "BAPG": 2}               # the `solver` codes of conan_fgw_barycenter_fwd_solver (bregman.py:8-67)
+FGW_SOLVERS = {"PGD": 0, "PPA": 1, "BAPG": 2}               # the `solver` codes of the FGW entry points (bregman.py:8-67)
+_LOSS_CODE = {"square_loss": 0, "kl_loss": 1}               # conan_fgw_params.loss_fun
 
 
 def _symmetric_code(symmetric) -> int:
-    """The `symmetric` code of conan_fgw_barycenter_fwd_sym: True -> 1, False -> 0, None -> -1 (decided per coupling solve)."""
+    """The `symmetric` code of the FGW entry points: True -> 1, False -> 0, None -> -1 (decided per coupling solve)."""
     if symmetric is True:
         return 1
     if symmetric is False:
@@ -893,6 +894,12 @@ def _symmetric_code(symmetric) -> int:
     if symmetric is None:
         return -1
     raise ValueError(f"symmetric must be True, False or None, not {symmetric!r}")
+
+
+def _fgw_params(alpha, epsilon, max_iter, tol, inner_tol, num_iter_max, stop_thr, fixed_structure, fixed_features, warmstart, loss_fun,
+                cs_small_int=False) -> FgwParams:
+    return FgwParams(float(alpha), float(epsilon), int(max_iter), float(tol), float(inner_tol), int(num_iter_max), float(stop_thr),
+                     int(bool(fixed_structure)), int(bool(fixed_features)), int(bool(warmstart)), _LOSS_CODE[loss_fun], int(bool(cs_small_int)))
 
 
 class _FgwBarycenterFn(torch.autograd.Function):
@@ -905,33 +912,26 @@ class _FgwBarycenterFn(torch.autograd.Function):
         if adj is not None and adj.num_graphs != B * K:
             raise RuntimeError(f"adjacency graph holds {adj.num_graphs} conformer graphs, Ys holds {B} x {K}")
         dev = Ys.device
-        prm = FgwParams(float(params["alpha"]), float(params["epsilon"]), int(params["max_iter"]), float(params["tol"]),
-                        float(params["inner_tol"]), int(params["num_iter_max"]), float(params["stop_thr"]),
-                        int(bool(params["fixed_structure"])), int(bool(params["fixed_features"])), int(bool(params["warmstart"])),
-                        {"square_loss": 0, "kl_loss": 1}[params.get("loss_fun", "square_loss")], int(bool(params.get("cs_small_int", False))))
+        prm = _fgw_params(params["alpha"], params["epsilon"], params["max_iter"], params["tol"], params["inner_tol"], params["num_iter_max"],
+                          params["stop_thr"], params["fixed_structure"], params["fixed_features"], params["warmstart"],
+                          params.get("loss_fun", "square_loss"), params.get("cs_small_int", False))
         Y = torch.empty(B, N, d, dtype=f32, device=dev)
         C = torch.empty(B, N, N, dtype=f32, device=dev)
         T = torch.empty(B, K, N, N, dtype=f32, device=dev)
         T_iter = torch.empty(prm.max_iter, B, K, N, N, dtype=f32, device=dev) if params.get("keep_iterates") else None
         info = torch.empty(B, 4, dtype=i32, device=dev)
         errs = torch.empty(B, 2, prm.max_iter, dtype=f32, device=dev)
-        import ctypes
         solver = FGW_SOLVERS[params.get("solver", "PGD")]
         symmetric = _symmetric_code(params.get("symmetric", True))
-        # One call: symmetric=False / None takes the `_sym` pair (trailing solver and symmetric codes), PPA / BAPG the `_solver` pair (trailing
-        # solver code), PGD the original pair; a RadiusGraph the `_ragged` twin of each, with its four lists in place of Cs.
-        if symmetric != 1:
-            suffix, query, tail = "_sym", "_sym", (solver, symmetric)
-        elif solver != 0:
-            suffix, query, tail = "_solver", "", (solver,)
-        else:
-            suffix, query, tail = "", "", ()
-        ragged = "" if adj is None else "_ragged"
-        ws_bytes = getattr(lib(), "conan_fgw_workspace_bytes" + ragged + query)(B, K, N, d, *(tail if query else ()))
+        ws_bytes = lib().conan_fgw_workspace_bytes(B, K, N, d, int(adj is not None), solver, symmetric)
         ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
-        structure = (ptr(Cs, f32),) if adj is None else (ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32), ptr(adj.tgt, i32))
-        call("conan_fgw_barycenter_fwd" + ragged + suffix, ptr(Ys, f32), *structure, ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y),
-             B, K, N, d, ctypes.byref(prm), ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr(), *tail)
+        common = (ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d, ctypes.byref(prm), solver, symmetric,
+                  ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+        if adj is None:
+            call("conan_fgw_barycenter_fwd", ptr(Ys, f32), ptr(Cs, f32), *common)
+        else:       # a RadiusGraph: its four lists in place of Cs
+            call("conan_fgw_barycenter_fwd_ragged", ptr(Ys, f32), ptr(adj.graph_ptr, i32), ptr(adj.rowptr, i32), ptr(adj.col, i32), ptr(adj.tgt, i32),
+                 *common)
         ctx.dims = (B, K, N, d)
         ctx.set_materialize_grads(False)          # C, T, info, errs carry no gradient: without this autograd fills four zero tensors per backward
         # Gradients beyond Ys (conan_fgw_barycenter_bwd_full): the last update steps are differentiable in Cs, p, lambdas (and init_C /
@@ -1002,7 +1002,7 @@ def fgw_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, 
     coupling kernels from the ragged neighbour lists — no [B,K,N,N] tensor exists (what the models do).
     `solver` = "PGD" (default: the models' solver), "PPA" or "BAPG" — the reference's three coupling solvers (bregman.py:8-67); info[:, 3] bit 2
     is raised for a molecule whose BAPG / PPA iterate had a zero row or column sum (the reference's NaN case).
-    `symmetric` = True (default: today's entry points), False (directed graphs / asymmetric structure matrices: the cost of bregman.py:98-128
+    `symmetric` = True (default: the models' solve), False (directed graphs / asymmetric structure matrices: the cost of bregman.py:98-128
     averages the problem and its transpose) or None (decided per coupling solve by torch.allclose(C, C^T, atol=1e-10) on the barycenter
     structure and the input graph, as the reference's every fgw() call does); False / None run the general kernels for every solver."""
     if params.get("solver", "PGD") not in FGW_SOLVERS:
@@ -1020,8 +1020,7 @@ def _pair_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun
     if loss_fun not in ("square_loss", "kl_loss"):
         raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
     # conan_fgw_pair_fwd reads alpha, epsilon, max_iter, tol, num_iter_max, stop_thr and loss_fun; the other fields are ignored
-    prm = FgwParams(float(alpha), float(epsilon), int(max_iter), float(tol), float(tol), int(num_iter_max), float(stop_thr), 1, 1, 0,
-                    {"square_loss": 0, "kl_loss": 1}[loss_fun], 0)
+    prm = _fgw_params(alpha, epsilon, max_iter, tol, tol, num_iter_max, stop_thr, True, True, False, loss_fun)
     return prm, FGW_SOLVERS[solver], _symmetric_code(None if symmetric is None else bool(symmetric))
 
 
@@ -1064,7 +1063,6 @@ def _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, solver_code, sym_code, with_dist):
     dist = torch.empty(B, dtype=f32, device=dev) if with_dist else None
     info = torch.empty(B, 4, dtype=i32, device=dev)
     errs = torch.empty(B, (prm.max_iter + 9) // 10, dtype=f32, device=dev)
-    import ctypes
     ws = torch.empty(int(lib().conan_fgw_pair_workspace_bytes(B, N, solver_code, sym_code)), dtype=torch.uint8, device=dev)
     call("conan_fgw_pair_fwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, ctypes.byref(prm), solver_code, sym_code,
          ptr(T), ptr(dist), ptr(info), ptr(errs), ptr(ws), stream_ptr())
@@ -1150,9 +1148,6 @@ class _FgwPairDistFn(torch.autograd.Function):
         call("conan_fgw_pair_dist_bwd", ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(T, f32), ptr(_c(g.to(f32)), f32), B, N, ctx.alpha, ctx.loss_code,
              *(ptr(t) for t in out), stream_ptr())
         return (*out, None, None, None)
-
-
-_LOSS_CODE = {"square_loss": 0, "kl_loss": 1}
 
 
 def fgw_pair_distance(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, G0: Optional[Tensor] = None, *,

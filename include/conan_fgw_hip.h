@@ -37,7 +37,7 @@ extern "C" {
 /* Library / device probe.  Returns CONAN_FGW_ABI_VERSION of the build.  The version changes whenever an existing export changes its
  * signature or meaning (v2: num_embeddings / pre_act arguments of round 2; v3: round-3 signatures), so a consumer compiled against
  * this header can detect a stale library: compare the return value with the macro. */
-#define CONAN_FGW_ABI_VERSION 5
+#define CONAN_FGW_ABI_VERSION 6
 int conan_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- batch assembly */
@@ -528,84 +528,66 @@ typedef struct conan_fgw_params {
                              * workgroups per CU at N = 33).  0 = arbitrary floats (fgw_barycenters called with general matrices). */
 } conan_fgw_params;
 
-/* Workspace size in BYTES for conan_fgw_barycenter_fwd (the regions of all four size queries: DESIGN.md, "FGW workspace"). */
-long long conan_fgw_workspace_bytes(int B, int K, int N, int d);
-
-/* Batched fgw_barycenters (barycenter.py:7-225 -> bregman.py:70-167 -> sinkhorn.py:318-450 -> utils.py), one
+/* Batched fgw_barycenters (barycenter.py:7-225 -> bregman.py:8-279 -> sinkhorn.py:318-450 -> utils.py), one
  * independent problem per molecule, all K input graphs of a molecule padded to the same N nodes (the production glue
  * always does; schnet_no_sum.py:281-306).  Replaces the Python loop over molecules (schnet_no_sum.py:259-312).
- * Ys[B,K,N,d], Cs[B,K,N,N], ps[B,K,N] or NULL (uniform), p[B,N] or NULL (uniform), lambdas[K] or NULL (1/K),
+ * Two entry points, one per form of the input graphs' structure; everything else is the same solve with the same arguments.
+ *
+ * Inputs.  Ys[B,K,N,d], ps[B,K,N] or NULL (uniform), p[B,N] or NULL (uniform), lambdas[K] or NULL (1/K),
  * init_C[B,N,N] or NULL (= Cs[b,0], schnet_no_sum.py:303), init_Y[B,N,d] or NULL (zeros).
  * Entries of ps / p may be ZERO: a node without mass takes no part in the problem (its row / column of every coupling, its row of Y and
  * its row / column of C are exactly zero).  That is how input graphs with fewer than N nodes, or a barycenter with fewer nodes than its
  * inputs (barycenter.py:50-67 takes any sizes), are passed: zero rows in Ys / Cs / init_C and zero weights (conan-fgw_amd/fgw.py does
  * this); couplings with massless nodes are solved on the log-domain path (flags bit 0).
+ *
+ * Structure.  conan_fgw_barycenter_fwd takes it dense, Cs[B,K,N,N].  conan_fgw_barycenter_fwd_ragged reads it straight from the ragged
+ * neighbour lists (the reference materialises to_dense_adj per conformer, schnet_no_sum.py:249-252; here no [G,N,N]
+ * tensor exists): graph g = b * K + s owns the nodes graph_ptr[g] .. graph_ptr[g+1]-1 and the edges rowptr[lo] .. rowptr[lo+n]-1 of the
+ * by-target CSR that conan_radius_graph_csr leaves (col = source, tgt = target of every edge; n clamped to N as in conan_fgw_densify);
+ * structure entry [source][target] = multiplicity of the edge.  The coupling kernels of the model path (solver 0, symmetric 1, square loss;
+ * N <= 64, or N > 64 within the LDS budget) build the adjacency counts as bytes in LDS in their load stage; any other shape / loss / solver /
+ * symmetric code, and the exact second pass of a flagged coupling, expand graphs into a scratch behind the regular workspace (ragged = 1 of
+ * the size query; untouched otherwise).  cs_small_int is implied.  Same outputs, same arithmetic: results equal conan_fgw_barycenter_fwd on
+ * the densified inputs bit for bit.
+ *
+ * solver: the reference's choice of coupling solver (fgw_barycenters(..., solver=S), barycenter.py:118-160 -> bregman.py:8-67).
+ * 0 = "PGD" (the models' solver), 1 = "PPA" (bregman.py:70-167: PGD whose Sinkhorn cost carries -epsilon log(T) of the previous coupling;
+ * numItermax / stopThr as for PGD), 2 = "BAPG" (fgw_bregman, bregman.py:170-279 with marginal_loss=False: two Bregman projections per
+ * iteration in fp64 multiplicative form, no inner Sinkhorn; num_iter_max / stop_thr unused).  Inner iterations run up to max_iter with tol
+ * inner_tol, the error ||T - Tprev|| checked at every 10th, as in the reference.  Solvers 1 and 2 run the general kernels only (no fast / big
+ * path, no padded-node merge: flags bits 0 and 1 stay 0) and expand ragged input to the dense scratch first.
+ * symmetric: the reference's `symmetric` argument (fgw_barycenters(..., symmetric=S), barycenter.py:118-160 -> bregman.py:98-128 / :199-222).
+ * 1 = True (the models' solve), 0 = False (the cost is the mean of the gradients of the problem and of its transpose,
+ * init_matrix(C1^T, C2^T): for directed graphs and other asymmetric structure matrices), -1 = None (decided per coupling solve, as the
+ * reference's every fgw() call does: False unless the barycenter structure and the input graph both pass
+ * torch.allclose(X, X^T, atol=1e-10)).  symmetric != 1 runs the general kernels for every solver (PGD as well: no fast / big path, no
+ * padded-node merge, flags bits 0 / 1 as for solvers 1 / 2) and expands ragged input to the dense scratch first.
+ *
  * Outputs: Y[B,N,d], C[B,N,N], T[B,K,N,N] (final couplings, saved for the backward),
  * T_iter[max_iter,B,K,N,N] or NULL: the couplings after every outer iteration (the reference's log["Ts_iter"], barycenter.py:196;
  * a molecule that stopped early keeps its last couplings in the later slots),
- * info[B,4] int32 = {outer iterations, total PGD iterations, total Sinkhorn iterations, flags}; flags bit 0: at least one coupling
- * solve of the molecule left the range of the scaling-form Sinkhorn and was redone on the exact log-domain path (same result
+ * info[B,4] int32 = {outer iterations, total PGD (PPA) or BAPG iterations, total Sinkhorn iterations (0 for BAPG), flags}; flags bit 0: at
+ * least one coupling solve of the molecule left the range of the scaling-form Sinkhorn and was redone on the exact log-domain path (same result
  * contract, slower); bit 1 (round 6): at least one coupling solve ran with the molecule's padded nodes merged into one node (the N - n padded nodes
- * of a conformer graph and of the barycenter are exchangeable: same iteration, same result contract, (n + 1)^3 instead of N^3 — DESIGN.md 3.3),
+ * of a conformer graph and of the barycenter are exchangeable: same iteration, same result contract, (n + 1)^3 instead of N^3 — DESIGN.md 3.3);
+ * bit 2: an iterate of a coupling solve had a zero row or column sum (underflow of the multiplicative form; the reference's NaN case, where
+ * it only warns) — the molecule's outputs are then NaN as the reference's are,
  * errs[B,2,max_iter] fp32 = err_feature / err_structure per outer iteration (NaN where not executed).
- * Internal arithmetic is fp64 (DESIGN.md section "FGW numerics"); I/O is fp32. */
+ * Internal arithmetic is fp64 (DESIGN.md section "FGW numerics"); I/O is fp32.
+ *
+ * Workspace: conan_fgw_workspace_bytes BYTES, asked with the solve's B, K, N, d, ragged = 0 (conan_fgw_barycenter_fwd) or 1 (_ragged), solver and
+ * symmetric (the regions: DESIGN.md, "FGW workspace").  The size depends on the two codes in one case only: BAPG with symmetric != 1 at
+ * N > 64, whose solve needs a scratch of its own.  The solve returns CONAN_E_BADARG before any launch, and the query 0, for a solver outside
+ * 0..2 or a symmetric outside -1..1; the query also returns 0 for a non-positive dimension or a ragged outside {0, 1}. */
+long long conan_fgw_workspace_bytes(int B, int K, int N, int d, int ragged, int solver, int symmetric);
 int conan_fgw_barycenter_fwd(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
                              const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                             const conan_fgw_params *params /* (host) */, float *Y, float *C, float *T, float *T_iter,
-                             int *info, float *errs, void *workspace, void *stream);
-/* The same solve with the input graphs' structure read straight from the ragged neighbour lists instead of Cs[B,K,N,N] (SURVEY.md 2.2 / 7:
- * the reference materialises to_dense_adj per conformer, schnet_no_sum.py:249-252; here no [G,N,N] tensor exists): graph g = b * K + s owns the
- * nodes graph_ptr[g] .. graph_ptr[g+1]-1 and the edges rowptr[lo] .. rowptr[lo+n]-1 of the by-target CSR that conan_radius_graph_csr leaves
- * (col = source, tgt = target of every edge; n clamped to N as in conan_fgw_densify); structure entry [source][target] = multiplicity of the edge.
- * The coupling kernels of the model path (square loss; N <= 64, or N > 64 within the LDS budget) build the adjacency counts as bytes in LDS in
- * their load stage; any other shape / loss, and the exact second pass of a flagged coupling, expand graphs into a scratch behind the regular
- * workspace (conan_fgw_workspace_bytes_ragged; untouched otherwise).  cs_small_int is implied.  Same outputs, same arithmetic: results equal
- * conan_fgw_barycenter_fwd on the densified inputs bit for bit. */
-long long conan_fgw_workspace_bytes_ragged(int B, int K, int N, int d);
+                             const conan_fgw_params *params /* (host) */, int solver, int symmetric, float *Y, float *C, float *T,
+                             float *T_iter, int *info, float *errs, void *workspace, void *stream);
 int conan_fgw_barycenter_fwd_ragged(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt, const float *ps,
                                     const float *p, const float *lambdas, const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                                    const conan_fgw_params *params /* (host) */, float *Y, float *C, float *T, float *T_iter, int *info,
-                                    float *errs, void *workspace, void *stream);
-
-/* The same two solves with the reference's choice of coupling solver (fgw_barycenters(..., solver=S), barycenter.py:118-160 -> bregman.py:8-67):
- * solver 0 = "PGD" (runs exactly what conan_fgw_barycenter_fwd / _ragged run), 1 = "PPA" (bregman.py:70-167: PGD whose Sinkhorn cost carries
- * -epsilon log(T) of the previous coupling; numItermax / stopThr as for PGD), 2 = "BAPG" (fgw_bregman, bregman.py:170-279 with
- * marginal_loss=False: two Bregman projections per iteration in fp64 multiplicative form, no inner Sinkhorn; num_iter_max / stop_thr unused).
- * Inner iterations run up to max_iter with tol inner_tol, the error ||T - Tprev|| checked at every 10th, as in the reference.  Same workspace
- * (conan_fgw_workspace_bytes / _ragged), same outputs.  info word 1 counts the PGD (PPA) or BAPG iterations, word 2 the Sinkhorn iterations
- * (0 for BAPG).  flags bit 2: an iterate of a coupling solve had a zero row or column sum (underflow of the multiplicative form; the
- * reference's NaN case, where it only warns) — the molecule's outputs are then NaN as the reference's are.  Bits 0 and 1 stay 0 for
- * solvers 1 and 2 (general kernels only, no padded-node merge; ragged input is expanded to the dense scratch first).  Returns
- * CONAN_E_BADARG for any other solver value. */
-int conan_fgw_barycenter_fwd_solver(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
-                                    const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                                    const conan_fgw_params *params /* (host) */, float *Y, float *C, float *T, float *T_iter,
-                                    int *info, float *errs, void *workspace, void *stream, int solver);
-int conan_fgw_barycenter_fwd_ragged_solver(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
-                                           const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
-                                           int B, int K, int N, int d, const conan_fgw_params *params /* (host) */, float *Y, float *C,
-                                           float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver);
-
-/* The `_solver` pair with the reference's `symmetric` argument as well (fgw_barycenters(..., symmetric=S), barycenter.py:118-160 ->
- * bregman.py:98-128 / :199-222): symmetric 1 = True (runs exactly what conan_fgw_barycenter_fwd_solver / _ragged_solver run), 0 = False (the
- * cost is the mean of the gradients of the problem and of its transpose, init_matrix(C1^T, C2^T): for directed graphs and other asymmetric
- * structure matrices), -1 = None (decided per coupling solve, as the reference's every fgw() call does: False unless the barycenter structure
- * and the input graph both pass torch.allclose(X, X^T, atol=1e-10)).  symmetric != 1 runs the general kernels for every solver (PGD as well:
- * no fast / big path, no padded-node merge, flags bits 0 / 1 as for solvers 1 / 2) and expands ragged input to the dense scratch first.
- * Workspace: conan_fgw_workspace_bytes_sym / _ragged_sym with the same solver and symmetric (equal to conan_fgw_workspace_bytes / _ragged
- * except for BAPG with symmetric != 1 at N > 64, whose solve needs a scratch of its own).  Returns CONAN_E_BADARG (size queries: 0) for a
- * solver outside 0..2 or a symmetric outside -1..1. */
-long long conan_fgw_workspace_bytes_sym(int B, int K, int N, int d, int solver, int symmetric);
-long long conan_fgw_workspace_bytes_ragged_sym(int B, int K, int N, int d, int solver, int symmetric);
-int conan_fgw_barycenter_fwd_sym(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
-                                 const float *init_C, const float *init_Y, int B, int K, int N, int d,
-                                 const conan_fgw_params *params /* (host) */, float *Y, float *C, float *T, float *T_iter,
-                                 int *info, float *errs, void *workspace, void *stream, int solver, int symmetric);
-int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, const int *rowptr, const int *col, const int *tgt,
-                                        const float *ps, const float *p, const float *lambdas, const float *init_C, const float *init_Y,
-                                        int B, int K, int N, int d, const conan_fgw_params *params /* (host) */, float *Y, float *C,
-                                        float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream, int solver,
-                                        int symmetric);
+                                    const conan_fgw_params *params /* (host) */, int solver, int symmetric, float *Y, float *C, float *T,
+                                    float *T_iter, int *info, float *errs, void *workspace, void *stream);
 
 /* The coupling solve on its own, B pairs of attributed graphs at once: the reference's fgw(M, C1, C2, p, q, ...) (bregman.py:8-67 -> fgw_projected
  * :70-167 / fgw_bregman :170-279), one workgroup per pair on the pair form of the general coupling kernels.
@@ -616,7 +598,7 @@ int conan_fgw_barycenter_fwd_ragged_sym(const float *Ys, const int *graph_ptr, c
  * params: alpha, epsilon, loss_fun as everywhere; max_iter and tol are the SOLVE's cap and tolerance on ||T - Tprev|| (checked at every 10th
  * iteration, bregman.py:119,144-147 / :238,252-255); num_iter_max / stop_thr the Sinkhorn keywords numItermax / stopThr (unused by solver 2);
  * inner_tol, fixed_*, warmstart and cs_small_int are ignored.  solver 0 / 1 / 2 = PGD / PPA / BAPG, symmetric 1 / 0 / -1 = True / False / None as in
- * conan_fgw_barycenter_fwd_sym.
+ * conan_fgw_barycenter_fwd.
  * Outputs: T[B,N,N]; fgw_dist[B] or NULL (not wanted): conan_fgw_pair_dist of the returned T, same bits; info[B,4] int32 = {PGD / PPA / BAPG
  * iterations, Sinkhorn iterations (0 for BAPG), flags, symmetric decision taken (1 / 0)}, flags bit 2: an iterate had a zero row or column sum
  * at a node WITH mass (the reference's NaN case); errs[B, ceil(max_iter / 10)] fp32: ||T - Tprev||_F of every check (the reference's

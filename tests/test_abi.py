@@ -59,7 +59,7 @@ def test_params_struct_layout(built):
 
 def test_workspace_queries_need_no_gpu(built):
     L = built.lib()
-    assert L.conan_fgw_workspace_bytes(256, 5, 33, 64) > 0
+    assert L.conan_fgw_workspace_bytes(256, 5, 33, 64, 0, 0, 1) > 0
     assert L.conan_linear_wgrad_ws(1000, 128, 128) >= 128 * 128
 
 

@@ -1,4 +1,4 @@
-"""CPU-side checks of the PPA / BAPG coupling solvers: the C ABI exports them, the ctypes table declares them, and fgw_barycenters validates
+"""CPU-side checks of the PPA / BAPG coupling solvers: the two forward entry points take the solver code, and fgw_barycenters validates
 its arguments like the reference (barycenter.py:33-44, 55-72) before refusing CPU tensors (GPU only)."""
 import ctypes
 import os
@@ -11,7 +11,8 @@ from conan_fgw_amd import fgw as pfgw
 from conan_fgw_amd import ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("conan_fgw_barycenter_fwd_solver", "conan_fgw_barycenter_fwd_ragged_solver")
+FWD = ("conan_fgw_barycenter_fwd", "conan_fgw_barycenter_fwd_ragged")
+REMOVED = tuple("conan_fgw_barycenter_fwd" + s for s in ("_solver", "_ragged_solver", "_sym", "_ragged_sym"))
 
 
 @pytest.fixture(scope="module")
@@ -22,28 +23,34 @@ def built():
     return _lib
 
 
+def _args(hdr, name):
+    m = re.search(r"\b(?:int|long long)\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.S)
+    assert m, f"{name} not declared"
+    return [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")]
+
+
 def test_solver_exports_are_declared_and_exported(built):
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "conan_fgw_hip.h")).read(), flags=re.S)
     L = ctypes.CDLL(built.library_path())
-    for name in NEW:
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.S)
-        assert m, f"{name} not declared"
-        args = [a.strip() for a in m.group(1).split(",")]
-        assert args[-1] == "int solver"
+    # the two forward entry points take `int solver, int symmetric` right after `params`, where conan_fgw_pair_fwd has them
+    for name in FWD:
+        args, table = _args(hdr, name), built.SIGNATURES[name][1]
+        at = args.index("const conan_fgw_params *params")
+        assert args[at + 1:at + 3] == ["int solver", "int symmetric"], name
+        assert table[at] == ctypes.POINTER(built.FgwParams) and table[at + 1:at + 3] == [ctypes.c_int, ctypes.c_int] and len(table) == len(args)
         assert hasattr(L, name)
-        assert len(built.SIGNATURES[name][1]) == len(args)
-    # the PGD entry points are unchanged: the solver exports take exactly one argument more
-    assert len(built.SIGNATURES[NEW[0]][1]) == len(built.SIGNATURES["conan_fgw_barycenter_fwd"][1]) + 1
-    assert len(built.SIGNATURES[NEW[1]][1]) == len(built.SIGNATURES["conan_fgw_barycenter_fwd_ragged"][1]) + 1
+    # the layered variants are gone (the size query: tests/test_fgw_sym_cpu.py)
+    for name in REMOVED:
+        assert not re.search(r"\b" + name + r"\b", hdr) and name not in built.SIGNATURES and not hasattr(L, name), name
 
 
 def test_solver_exports_refuse_bad_arguments_without_launching(built):
     L = built.lib()
     for solver in (0, 1, 2, 3, -1):
-        assert L.conan_fgw_barycenter_fwd_solver(None, None, None, None, None, None, None, 1, 1, 1, 1, None, None, None, None, None, None,
-                                                 None, None, None, solver) == -1
-        assert L.conan_fgw_barycenter_fwd_ragged_solver(None, None, None, None, None, None, None, None, None, None, 1, 1, 1, 1, None, None,
-                                                        None, None, None, None, None, None, None, solver) == -1
+        assert L.conan_fgw_barycenter_fwd(None, None, None, None, None, None, None, 1, 1, 1, 1, None, solver, 1, None, None, None, None, None,
+                                          None, None, None) == -1
+        assert L.conan_fgw_barycenter_fwd_ragged(None, None, None, None, None, None, None, None, None, None, 1, 1, 1, 1, None, solver, 1, None,
+                                                 None, None, None, None, None, None, None) == -1
 
 
 @pytest.mark.parametrize("solver", ["PPA", "BAPG"])

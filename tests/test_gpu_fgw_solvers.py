@@ -133,36 +133,38 @@ def test_bapg_zero_row_sum_raises_the_flag_and_the_warning():
     assert bool(torch.isfinite(Y2).all())
 
 
-def _fwd_solver_entry(Ys, Cs, graph, solver, **params):
-    """conan_fgw_barycenter_fwd_solver / _ragged_solver called directly (ops routes solver="PGD" to the original entry points)."""
+def _fwd_entry(Ys, Cs, graph, solver, symmetric, **params):
+    """conan_fgw_barycenter_fwd (graph is None) / _ragged called directly through ctypes, with the size query's numbers."""
     prm_d = dict(ops.PROD_FGW); prm_d.update(params)
     B, K, N, d = Ys.shape
     prm = FgwParams(float(prm_d["alpha"]), float(prm_d["epsilon"]), int(prm_d["max_iter"]), float(prm_d["tol"]), float(prm_d["inner_tol"]),
                     int(prm_d["num_iter_max"]), float(prm_d["stop_thr"]), 0, 0, int(bool(prm_d["warmstart"])), 0, 1)
     Y = torch.empty(B, N, d, device=dev); C = torch.empty(B, N, N, device=dev); T = torch.empty(B, K, N, N, device=dev)
     info = torch.empty(B, 4, dtype=torch.int32, device=dev); errs = torch.empty(B, 2, prm.max_iter, device=dev)
-    Ys = Ys.contiguous()
-    out = (ptr(Y), ptr(C), ptr(T), None, ptr(info), ptr(errs))
-    if graph is None:
-        ws = torch.empty(int(lib().conan_fgw_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
-        call("conan_fgw_barycenter_fwd_solver", ptr(Ys), ptr(Cs.contiguous()), None, None, None, None, None, B, K, N, d, ctypes.byref(prm), *out,
-             ptr(ws), stream_ptr(), solver)
-    else:
-        ws = torch.empty(int(lib().conan_fgw_workspace_bytes_ragged(B, K, N, d)), dtype=torch.uint8, device=dev)
-        call("conan_fgw_barycenter_fwd_ragged_solver", ptr(Ys), ptr(graph.graph_ptr), ptr(graph.rowptr), ptr(graph.col), ptr(graph.tgt),
-             None, None, None, None, None, B, K, N, d, ctypes.byref(prm), *out, ptr(ws), stream_ptr(), solver)
+    ws = torch.empty(int(lib().conan_fgw_workspace_bytes(B, K, N, d, int(graph is not None), solver, symmetric)), dtype=torch.uint8, device=dev)
+    structure = (ptr(Cs.contiguous()),) if graph is None else (ptr(graph.graph_ptr), ptr(graph.rowptr), ptr(graph.col), ptr(graph.tgt))
+    call("conan_fgw_barycenter_fwd" if graph is None else "conan_fgw_barycenter_fwd_ragged", ptr(Ys.contiguous()), *structure, None, None, None,
+         None, None, B, K, N, d, ctypes.byref(prm), solver, symmetric, ptr(Y), ptr(C), ptr(T), None, ptr(info), ptr(errs), ptr(ws), stream_ptr())
     return Y, C, T, info, errs
 
 
+def _same(direct, through_ops):
+    for a, b, name in zip(direct, through_ops, ("Y", "C", "T", "info", "errs")):
+        if name == "errs":                          # NaN where not run
+            assert torch.equal(torch.nan_to_num(a), torch.nan_to_num(b)), name
+        else:                                       # bit for bit, the NaN of a BAPG molecule with flags bit 2 included
+            assert a.dtype == b.dtype and torch.equal(a.view(torch.int32), b.view(torch.int32)), name
+
+
+@pytest.mark.parametrize("code,solver,eps", [(0, "PGD", 0.1), (1, "PPA", 0.1), (2, "BAPG", 2.0)], ids=["pgd", "ppa", "bapg"])
 @pytest.mark.parametrize("shape,B,K", [("esol", 256, 5), ("lipo", 104, 5)], ids=["cfg2", "lipophilicity"])
-def test_pgd_through_the_solver_entry_points_is_the_old_solve(shape, B, K):
-    """solver = 0 runs exactly what conan_fgw_barycenter_fwd(_ragged) runs (the models' path): every output bit for bit."""
+def test_the_entry_points_called_directly_are_the_ops_solve(shape, B, K, code, solver, eps):
+    """Both entry points with (solver code, symmetric 1) against ops.fgw_barycenter_batched(solver=<name>, symmetric=True), ragged and dense:
+    ops sends the right codes and asks the right size for every solver, and its default is the models' solve (PGD, symmetric)."""
     Ys, Cs, graph = _model_batch(shape, B, K)
-    old = ops.fgw_barycenter_batched(Ys, None, adjacency=graph)
-    new = _fwd_solver_entry(Ys, None, graph, 0)
-    for a, b, name in zip(old, new, ("Y", "C", "T", "info", "errs")):
-        assert torch.equal(a, b) or (name == "errs" and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))), name
-    old = ops.fgw_barycenter_batched(Ys, Cs, cs_small_int=True)
-    new = _fwd_solver_entry(Ys, Cs, None, 0)
-    for a, b, name in zip(old, new, ("Y", "C", "T", "info", "errs")):
-        assert torch.equal(a, b) or (name == "errs" and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))), name
+    ragged, dense = _fwd_entry(Ys, None, graph, code, 1, epsilon=eps), _fwd_entry(Ys, Cs, None, code, 1, epsilon=eps)
+    _same(ragged, ops.fgw_barycenter_batched(Ys, None, adjacency=graph, solver=solver, symmetric=True, epsilon=eps))
+    _same(dense, ops.fgw_barycenter_batched(Ys, Cs, cs_small_int=True, solver=solver, symmetric=True, epsilon=eps))
+    if code == 0:
+        _same(ragged, ops.fgw_barycenter_batched(Ys, None, adjacency=graph))
+        _same(dense, ops.fgw_barycenter_batched(Ys, Cs, cs_small_int=True))

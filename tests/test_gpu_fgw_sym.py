@@ -1,9 +1,8 @@
 """fgw_barycenters(..., symmetric=False | None) on the GPU against the reference's own fp32 / fp64 runs (tests/golden/fgw_sym_*.npz, written
 by make_fgw_sym_golden.py): directed graphs and asymmetric float matrices, square and KL loss, PGD / PPA / BAPG, N <= 64 and N > 64.  Same
 yardsticks as test_gpu_fgw_solvers.py: outer, inner and Sinkhorn iteration counts of r64, errs within rtol 2e-3, Y and C within 1e-4 of r64,
-T within 1e-4 of r32 or no further from r64 than r32 is.  Further: symmetric=None against False / True, symmetric=True through the `_sym`
-exports against the `_solver` ones, the adjacency path, the backward and the notebook call (notebooks/fgw.ipynb on cfm_log)."""
-import ctypes
+T within 1e-4 of r32 or no further from r64 than r32 is.  Further: symmetric=None against False / True, the adjacency path, the backward
+and the notebook call (notebooks/fgw.ipynb on cfm_log)."""
 import os
 
 import numpy as np
@@ -13,7 +12,6 @@ import torch
 from helpers import GOLDEN, golden_files, rel
 from conan_fgw_amd import fgw as pfgw
 from conan_fgw_amd import ops
-from conan_fgw_amd._lib import FgwParams, call, lib, ptr, stream_ptr
 from conan_fgw_amd.synthetic import make_batch
 
 pytestmark = pytest.mark.gpu
@@ -143,41 +141,6 @@ def test_symmetric_none_on_symmetric_input_matches_true(shape, B, K, solver, kw)
         assert rel(b.cpu().numpy(), a.cpu().numpy()) <= 1e-5, name
     assert torch.equal(true[3][:, :3], none[3][:, :3])                   # outer, inner and Sinkhorn iteration counts
     assert int((none[3][:, 3] & 2).sum()) == 0                           # (no padded-node merge off the model path)
-
-
-def _fwd_entry(Ys, Cs, graph, solver, symmetric=None, **params):
-    """conan_fgw_barycenter_fwd_solver / _ragged_solver (symmetric=None here: the argument is absent), or the `_sym` pair with `symmetric`."""
-    prm_d = dict(ops.PROD_FGW); prm_d.update(params)
-    B, K, N, d = Ys.shape
-    prm = FgwParams(float(prm_d["alpha"]), float(prm_d["epsilon"]), int(prm_d["max_iter"]), float(prm_d["tol"]), float(prm_d["inner_tol"]),
-                    int(prm_d["num_iter_max"]), float(prm_d["stop_thr"]), 0, 0, int(bool(prm_d["warmstart"])), 0, 1)
-    Y = torch.empty(B, N, d, device=dev); C = torch.empty(B, N, N, device=dev); T = torch.empty(B, K, N, N, device=dev)
-    info = torch.empty(B, 4, dtype=torch.int32, device=dev); errs = torch.empty(B, 2, prm.max_iter, device=dev)
-    Ys = Ys.contiguous()
-    out = (ptr(Y), ptr(C), ptr(T), None, ptr(info), ptr(errs))
-    tail = (solver,) if symmetric is None else (solver, symmetric)
-    sfx = "_solver" if symmetric is None else "_sym"
-    if graph is None:
-        nb = lib().conan_fgw_workspace_bytes(B, K, N, d) if symmetric is None else lib().conan_fgw_workspace_bytes_sym(B, K, N, d, solver, symmetric)
-        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-        call("conan_fgw_barycenter_fwd" + sfx, ptr(Ys), ptr(Cs.contiguous()), None, None, None, None, None, B, K, N, d, ctypes.byref(prm), *out,
-             ptr(ws), stream_ptr(), *tail)
-    else:
-        nb = (lib().conan_fgw_workspace_bytes_ragged(B, K, N, d) if symmetric is None
-              else lib().conan_fgw_workspace_bytes_ragged_sym(B, K, N, d, solver, symmetric))
-        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-        call("conan_fgw_barycenter_fwd_ragged" + sfx, ptr(Ys), ptr(graph.graph_ptr), ptr(graph.rowptr), ptr(graph.col), ptr(graph.tgt),
-             None, None, None, None, None, B, K, N, d, ctypes.byref(prm), *out, ptr(ws), stream_ptr(), *tail)
-    return Y, C, T, info, errs
-
-
-@pytest.mark.parametrize("solver,eps", [(0, 0.1), (1, 0.1), (2, 2.0)], ids=["pgd", "ppa", "bapg"])
-@pytest.mark.parametrize("shape,B,K", [("esol", 256, 5), ("lipo", 104, 5)], ids=["cfg2", "lipophilicity"])
-def test_symmetric_true_through_the_sym_entry_points_is_the_solver_solve(shape, B, K, solver, eps):
-    """symmetric = 1 runs exactly what conan_fgw_barycenter_fwd_solver / _ragged_solver run: every output bit for bit."""
-    Ys, Cs, graph = _model_batch(shape, B, K)
-    _same(_fwd_entry(Ys, None, graph, solver, epsilon=eps), _fwd_entry(Ys, None, graph, solver, 1, epsilon=eps))
-    _same(_fwd_entry(Ys, Cs, None, solver, epsilon=eps), _fwd_entry(Ys, Cs, None, solver, 1, epsilon=eps))
 
 
 @pytest.mark.parametrize("solver,kw", SOLVERS, ids=SOLVER_IDS)

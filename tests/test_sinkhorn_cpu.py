@@ -83,7 +83,7 @@ def test_signatures_and_host_queries():
     for name in ("conan_sinkhorn_workspace_bytes", "conan_sinkhorn_lds_resident", "conan_sinkhorn_fwd"):
         assert name in _lib.SIGNATURES
     L = _lib.lib()
-    assert L.conan_abi_version() == 5
+    assert L.conan_abi_version() == 6
     assert L.conan_sinkhorn_lds_resident(33, 33) == 1 and L.conan_sinkhorn_lds_resident(257, 65) == 1
     assert L.conan_sinkhorn_lds_resident(140, 140) == 0 and L.conan_sinkhorn_lds_resident(1000, 1000) == 0
     assert L.conan_sinkhorn_lds_resident(0, 5) == 0 and L.conan_sinkhorn_lds_resident(5, -1) == 0
