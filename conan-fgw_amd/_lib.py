@@ -49,6 +49,8 @@ SIGNATURES = {
     "conan_radius_graph_csr": (c_int, [_P, _P, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "conan_csr_transpose": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "conan_edge_pairs": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "conan_radius_graph_build_ws": (c_ll, [c_int, c_int, c_int, c_int]),
+    "conan_radius_graph_build": (c_int, [_P, _P, c_int, c_int, c_float, c_int, c_int] + [_P] * 12 + [_P]),
     "conan_edge_index_i64": (c_int, [_P, _P, c_int, _P, _P]),
     "conan_embedding_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "conan_onehot_rows": (c_int, [_P, c_int, c_int, c_int, _P, _P]),

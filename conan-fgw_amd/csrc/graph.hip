@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(1024) k_exclusive_scan_lds(const int *__restri
 
 // Single-workgroup exclusive scan, n up to a few million: out[0..n], out[n] = total.
 constexpr int SCAN_THREADS = 1024;
-__global__ void __launch_bounds__(SCAN_THREADS) k_exclusive_scan(const int *__restrict__ in, int n, int *__restrict__ out) {
+__device__ __forceinline__ void exclusive_scan_block(const int *__restrict__ in, int n, int *__restrict__ out) {
     __shared__ int wsum[SCAN_THREADS / 64];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int chunk = (n + SCAN_THREADS - 1) / SCAN_THREADS;
@@ -145,6 +145,15 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_exclusive_scan(const int *__re
         for (int i = b; i < e; ++i) { const int x = in[i]; out[i] = run; run += x; }
     }
     if (t == 0) out[n] = total;
+}
+__global__ void __launch_bounds__(SCAN_THREADS) k_exclusive_scan(const int *__restrict__ in, int n, int *__restrict__ out) {
+    exclusive_scan_block(in, n, out);
+}
+// two independent sequences of the same length in one launch (the per-graph edge and pair counts of the fused graph build): workgroup 0 / 1
+__global__ void __launch_bounds__(SCAN_THREADS) k_exclusive_scan_two(const int *__restrict__ in0, const int *__restrict__ in1, int n,
+                                                                     int *__restrict__ out0, int *__restrict__ out1) {
+    if (blockIdx.x == 0) exclusive_scan_block(in0, n, out0);
+    else exclusive_scan_block(in1, n, out1);
 }
 
 static void launch_exclusive_scan(const int *in, int n, int *out, hipStream_t s) {
@@ -209,14 +218,9 @@ static void scan_large(const int *in, int n, int *out, int *ws, hipStream_t s) {
 // scan: t_rowptr[j] = e0 + (number of edges of the graph whose source is < j).  One wavefront per source atom scans the
 // graph's edges 64 at a time: ballot + popcount give the row start (scan 1) and the in-order write slots (scan 2).
 constexpr int TR_THREADS = 1024;     // 16 wavefronts per graph: a BACE / Lipophilicity-sized graph has 64-97 source atoms to place (4 wavefronts: 107 us per step at Lipophilicity B = 128)
-__global__ void __launch_bounds__(TR_THREADS) k_transpose_graph(const int *__restrict__ gptr, const int *__restrict__ rowptr,
-                                                                const int *__restrict__ col, int num_atoms,
-                                                                int *__restrict__ t_rowptr, int *__restrict__ t_eid) {
-    const int g = blockIdx.x;
-    const int lo = gptr[g], hi = gptr[g + 1];
-    if (g == gridDim.x - 1 && threadIdx.x == 0) t_rowptr[num_atoms] = rowptr[num_atoms];
-    if (hi <= lo) return;
-    const int e0 = rowptr[lo], e1 = rowptr[hi];
+// The by-source rows of ONE graph (atoms lo .. hi - 1, edges e0 .. e1 - 1); all TR_THREADS threads of the workgroup, contains barriers.
+__device__ __forceinline__ void transpose_graph_rows(int lo, int hi, int e0, int e1, const int *__restrict__ col,
+                                                     int *__restrict__ t_rowptr, int *__restrict__ t_eid) {
     const int steps = (e1 - e0 + 63) >> 6;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -284,6 +288,15 @@ __global__ void __launch_bounds__(TR_THREADS) k_transpose_graph(const int *__res
         }
     }
 }
+__global__ void __launch_bounds__(TR_THREADS) k_transpose_graph(const int *__restrict__ gptr, const int *__restrict__ rowptr,
+                                                                const int *__restrict__ col, int num_atoms,
+                                                                int *__restrict__ t_rowptr, int *__restrict__ t_eid) {
+    const int g = blockIdx.x;
+    const int lo = gptr[g], hi = gptr[g + 1];
+    if (g == gridDim.x - 1 && threadIdx.x == 0) t_rowptr[num_atoms] = rowptr[num_atoms];
+    if (hi <= lo) return;
+    transpose_graph_rows(lo, hi, rowptr[lo], rowptr[hi], col, t_rowptr, t_eid);
+}
 
 // ---- undirected pairs ----------------------------------------------------------------------------------------------
 // The continuous filter depends on the edge only through d_ij = d_ji, so both directions of a pair can share one filter
@@ -324,6 +337,218 @@ __global__ void k_pair_fill(const int *__restrict__ rowptr, const int *__restric
         } else {
             pid[e] = pidx[rev];
         }
+    }
+}
+
+// ---- fused build: neighbour lists, pairs and transpose in three launches -----------------------------------------------------------------
+// Launch 1 (one workgroup per graph) scans the neighbours ONCE into rows of fixed pitch W = (loop ? cap : cap + 1) in the graph's slice of a
+// staging buffer (slice of graph g = rows gptr[g] .. gptr[g + 1] - 1), numbers edges, reverse edges and pair representatives LOCALLY
+// (a graph's edges and pairs are contiguous in the global numbering) and leaves the graph's edge and pair counts.  Launch 2 scans the two
+// count sequences.  Launch 3 (one workgroup per graph) adds the graph's offsets and writes every output list.  No workgroup reads what
+// another workgroup of the same launch wrote: the launch boundaries are the only hand-off, and no list order depends on timing.
+constexpr int GB_THREADS = 256;
+constexpr int GB_POS_LDS = 1024;       // atoms whose positions are staged in LDS (12 KB)
+constexpr int GB_LIST_LDS = 4096;      // list slots kept in LDS (sources and reverse slots as 16-bit words, 16 KB): 124 atoms at cap 32.  With the
+                                       // degrees that is 30 KB per workgroup: five per CU, a cfg2 batch (1 280 graphs) is resident at once
+struct GraphBuildWs {
+    int *deg, *lrow, *prow;            // [n] edges per target; first edge of the row inside its graph; first pair of the row inside its graph
+    int *ecnt, *pcnt, *eoff, *poff;    // [G] edges / pairs per graph; [G + 1] their exclusive scans
+    int *sym;                          // [G] every edge of the graph has its reverse (the by-source transpose then is the reverse-edge map)
+    int *s_col, *s_rev, *s_rank;       // [n * W] staged rows: source (graph-local), slot of the reverse edge in ITS row or -1, rank of a
+    float *s_dist;                     //         representative among the representatives of its row or -1; distance
+};
+static long long graph_build_ws_ints(long long n, long long G, long long W) { return 3 * n + 5 * G + 2 + 4 * n * W; }
+static GraphBuildWs graph_build_ws(int *ws, int n, int G, int W) {
+    GraphBuildWs w;
+    const size_t nw = (size_t)n * W;
+    w.deg = ws; w.lrow = w.deg + n; w.prow = w.lrow + n;
+    w.ecnt = w.prow + n; w.pcnt = w.ecnt + G; w.eoff = w.pcnt + G; w.poff = w.eoff + G + 1; w.sym = w.poff + G + 1;
+    w.s_col = w.sym + G; w.s_rev = w.s_col + nw; w.s_rank = w.s_rev + nw;
+    w.s_dist = reinterpret_cast<float *>(w.s_rank + nw);
+    return w;
+}
+
+// exclusive scan of n ints by one workgroup of NT threads, any n (chunks of NT with a running carry); in == out allowed; returns the total
+template <int NT>
+__device__ __forceinline__ int block_exclusive_scan(const int *in, int n, int *out, int *wsum) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int carry = 0;
+    for (int base = 0; base < n; base += NT) {
+        const int i = base + t;
+        const int v = i < n ? in[i] : 0;
+        int inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int woff = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < NT / 64; ++w) { const int x = wsum[w]; if (w < wave) woff += x; total += x; }
+        if (i < n) out[i] = carry + woff + inc - v;
+        carry += total;
+        __syncthreads();
+    }
+    return carry;
+}
+
+// What is local to a graph once its rows are staged: the slot of every edge's reverse (binary search of the target in the source's row: rows are
+// sorted by source), whether an edge lacks its reverse, k_pair_flag's rule per row — an edge (s -> i) represents its pair when s <= i or its
+// reverse is absent — and the rank of every representative in edge order.  LDS: rows, reverse slots and degrees are read from the workgroup's LDS
+// copies (a small graph), otherwise from the staging slice in global memory.
+template <bool LDS>
+__device__ __forceinline__ void graph_build_local(int g, int n, int W, int want_pairs, const short *s_col, short *s_rev, const short *s_deg,
+                                                  const int *gcol, int *grev, int *grank, const int *gdeg, int *prow, int *wsum,
+                                                  const GraphBuildWs &ws) {
+    auto col_at = [&](int idx) { return LDS ? (int)s_col[idx] : gcol[idx]; };
+    auto deg_at = [&](int i) { return LDS ? (int)s_deg[i] : gdeg[i]; };
+    int missing = 0;
+    for (int idx = threadIdx.x; idx < n * W; idx += GB_THREADS) {
+        const int i = idx / W, k = idx - i * W;
+        if (k >= deg_at(i)) continue;
+        const int s = col_at(idx);
+        int a = 0, b = deg_at(s) - 1, rev = -1;
+        while (a <= b) {
+            const int mid = (a + b) >> 1;
+            const int c = col_at(s * W + mid);
+            if (c == i) { rev = mid; break; }
+            if (c < i) a = mid + 1; else b = mid - 1;
+        }
+        grev[idx] = rev;
+        if (LDS) s_rev[idx] = (short)rev;
+        missing |= rev < 0;
+    }
+    __threadfence_block();
+    const int any_missing = __syncthreads_or(missing);
+    if (threadIdx.x == 0) ws.sym[g] = any_missing ? 0 : 1;
+    if (!want_pairs) {
+        if (threadIdx.x == 0) ws.pcnt[g] = 0;
+        return;
+    }
+    for (int i = threadIdx.x; i < n; i += GB_THREADS) {
+        const int d = deg_at(i);
+        int cnt = 0;
+        for (int k = 0; k < d; ++k) {
+            const int idx = i * W + k;
+            const int rev = LDS ? (int)s_rev[idx] : grev[idx];
+            const bool rep = col_at(idx) <= i || rev < 0;
+            grank[idx] = rep ? cnt : -1;
+            cnt += rep;
+        }
+        prow[i] = cnt;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const int np = block_exclusive_scan<GB_THREADS>(prow, n, prow, wsum);
+    if (threadIdx.x == 0) ws.pcnt[g] = np;
+}
+
+__global__ void __launch_bounds__(GB_THREADS) k_graph_build_lists(const float *__restrict__ pos, const int *__restrict__ gptr, float r2, int cap,
+                                                                  int loop, int W, int want_rev, int want_pairs, GraphBuildWs ws) {
+    __shared__ float sp[GB_POS_LDS * 3];
+    __shared__ short s_col[GB_LIST_LDS], s_rev[GB_LIST_LDS], s_deg[GB_POS_LDS];
+    __shared__ int wsum[GB_THREADS / 64];
+    const int g = blockIdx.x;
+    const int lo = gptr[g], hi = gptr[g + 1];
+    const int n = hi - lo;
+    if (n <= 0) {
+        if (threadIdx.x == 0) { ws.ecnt[g] = 0; ws.pcnt[g] = 0; ws.sym[g] = 0; }
+        return;
+    }
+    const bool in_lds = n <= GB_POS_LDS;
+    const bool list_lds = in_lds && n * W <= GB_LIST_LDS;       // (then W <= 4096 and n <= 1024: sources, slots and degrees fit 16-bit words)
+    const size_t slice = (size_t)lo * W;
+    int *gcol = ws.s_col + slice, *grev = ws.s_rev + slice, *grank = ws.s_rank + slice;
+    float *gdist = ws.s_dist + slice;
+    int *deg = ws.deg + lo;
+    if (in_lds)
+        for (int t = threadIdx.x; t < n * 3; t += GB_THREADS) sp[t] = pos[(size_t)lo * 3 + t];
+    __syncthreads();
+    // the scan of k_radius, rule for rule (torch-cluster 1.6.1: ascending source index INCLUDING the target, stop after `limit` hits, the self
+    // pair dropped afterwards unless `loop`), run once: the row goes to the staging slice instead of being counted first and filled later
+    for (int i = threadIdx.x; i < n; i += GB_THREADS) {
+        float ax, ay, az;
+        if (in_lds) { ax = sp[i * 3]; ay = sp[i * 3 + 1]; az = sp[i * 3 + 2]; }
+        else { ax = pos[(size_t)(lo + i) * 3]; ay = pos[(size_t)(lo + i) * 3 + 1]; az = pos[(size_t)(lo + i) * 3 + 2]; }
+        const int limit = loop ? cap : cap + 1;
+        int cnt = 0, out = 0;
+        for (int j = 0; j < n && cnt < limit; ++j) {
+            float bx, by, bz;
+            if (in_lds) { bx = sp[j * 3]; by = sp[j * 3 + 1]; bz = sp[j * 3 + 2]; }
+            else { bx = pos[(size_t)(lo + j) * 3]; by = pos[(size_t)(lo + j) * 3 + 1]; bz = pos[(size_t)(lo + j) * 3 + 2]; }
+            const float d2 = dist2_rn(bx, by, bz, ax, ay, az);
+            if (d2 < r2) {
+                ++cnt;
+                if (loop || j != i) {               // out < W: at most `limit` hits, and without `loop` limit = W
+                    gcol[i * W + out] = j; gdist[i * W + out] = __fsqrt_rn(d2);
+                    if (list_lds) s_col[i * W + out] = (short)j;
+                    ++out;
+                }
+            }
+        }
+        deg[i] = out;
+        if (list_lds) s_deg[i] = (short)out;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const int ne = block_exclusive_scan<GB_THREADS>(deg, n, ws.lrow + lo, wsum);
+    if (threadIdx.x == 0) ws.ecnt[g] = ne;
+    if (!want_rev) {
+        if (threadIdx.x == 0) { ws.pcnt[g] = 0; ws.sym[g] = 0; }
+        return;
+    }
+    if (list_lds) graph_build_local<true>(g, n, W, want_pairs, s_col, s_rev, s_deg, gcol, grev, grank, deg, ws.prow + lo, wsum, ws);
+    else graph_build_local<false>(g, n, W, want_pairs, s_col, s_rev, s_deg, gcol, grev, grank, deg, ws.prow + lo, wsum, ws);
+}
+
+__global__ void __launch_bounds__(TR_THREADS) k_graph_build_fill(const int *__restrict__ gptr, int num_atoms, int W, GraphBuildWs ws,
+                                                                 int *__restrict__ rowptr, int *col, int *__restrict__ tgt,
+                                                                 float *__restrict__ dist, int *__restrict__ pid, int *__restrict__ pe0,
+                                                                 int *__restrict__ pe1, float *__restrict__ pdist, int *__restrict__ num_pairs,
+                                                                 int *__restrict__ t_rowptr, int *__restrict__ t_eid) {
+    const int g = blockIdx.x, G = gridDim.x;
+    const int lo = gptr[g], hi = gptr[g + 1];
+    const int n = hi - lo;
+    if (g == G - 1 && threadIdx.x == 0) {
+        const int E = ws.eoff[G];
+        rowptr[num_atoms] = E;
+        if (t_rowptr) t_rowptr[num_atoms] = E;
+        if (num_pairs) *num_pairs = ws.poff[G];
+    }
+    if (n <= 0) return;
+    const int eo = ws.eoff[g], po = ws.poff[g];
+    const bool sym = t_eid && ws.sym[g];
+    const size_t slice = (size_t)lo * W;
+    const int *gcol = ws.s_col + slice, *grev = ws.s_rev + slice, *grank = ws.s_rank + slice;
+    const float *gdist = ws.s_dist + slice;
+    const int *deg = ws.deg + lo, *lrow = ws.lrow + lo, *prow = ws.prow + lo;
+    for (int i = threadIdx.x; i < n; i += TR_THREADS) {
+        const int r = eo + lrow[i];
+        rowptr[lo + i] = r;
+        if (sym) t_rowptr[lo + i] = r;           // every edge has its reverse: out-degree = in-degree
+    }
+    for (int idx = threadIdx.x; idx < n * W; idx += TR_THREADS) {
+        const int i = idx / W, k = idx - i * W;
+        if (k >= deg[i]) continue;
+        const int e = eo + lrow[i] + k;
+        const int s = gcol[idx];
+        const float d = gdist[idx];
+        col[e] = lo + s; tgt[e] = lo + i; dist[e] = d;
+        if (pid) {
+            const int rev = grev[idx], rk = grank[idx];
+            if (rk >= 0) {
+                const int p = po + prow[i] + rk;
+                pid[e] = p; pe0[p] = e; pe1[p] = (s == i || rev < 0) ? -1 : eo + lrow[s] + rev; pdist[p] = d;
+            } else {
+                pid[e] = po + prow[s] + grank[s * W + rev];      // not a representative: s > i and the reverse edge (i -> s) is slot rev of row s
+            }
+        }
+        // by-source row of atom i in ascending edge id = the edges (i -> s) by ascending s = the reverses of row i in row order
+        if (sym) t_eid[e] = eo + lrow[s] + grev[idx];
+    }
+    if (t_eid && !sym) {                             // truncated rows: k_transpose_graph's placement over the graph's edges just written
+        __threadfence_block();
+        __syncthreads();
+        transpose_graph_rows(lo, hi, eo, eo + ws.ecnt[g], col, t_rowptr, t_eid);
     }
 }
 
@@ -432,6 +657,31 @@ int conan_edge_pairs(const int *rowptr, const int *col, const int *tgt, const fl
     // k_pair_fill only for pair ids < number of pairs <= number of edges, and the scan is complete by then)
     scan_large(flag_ws, max_edges, pidx_ws, scan_ws, s);
     k_pair_fill<<<blocks, 256, 0, s>>>(rowptr, col, tgt, dist, num_edges_dev, max_edges, flag_ws, pidx_ws, pid, pair_e0, pair_e1, pair_dist);
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+long long conan_radius_graph_build_ws(int num_atoms, int num_graphs, int cap, int loop) {
+    if (num_atoms < 0 || num_graphs < 0 || cap <= 0) return CONAN_E_BADARG;
+    return graph_build_ws_ints(num_atoms, num_graphs, loop ? cap : cap + 1);
+}
+
+int conan_radius_graph_build(const float *pos, const int *graph_ptr, int num_atoms, int num_graphs, float r, int cap, int loop, int *ws,
+                             int *rowptr, int *col, int *tgt, float *dist, int *pid, int *pair_e0, int *pair_e1, float *pair_dist,
+                             int *num_pairs, int *t_rowptr, int *t_eid, void *stream) {
+    if ((!pos && num_atoms > 0) || !graph_ptr || !ws || !rowptr || !col || !tgt || !dist || num_atoms < 0 || num_graphs <= 0 || cap <= 0)
+        return CONAN_E_BADARG;
+    const bool pairs = pid || pair_e0 || pair_e1 || pair_dist || num_pairs;
+    if (pairs && !(pid && pair_e0 && pair_e1 && pair_dist && num_pairs)) return CONAN_E_BADARG;
+    if ((t_rowptr == nullptr) != (t_eid == nullptr)) return CONAN_E_BADARG;
+    const int W = loop ? cap : cap + 1;
+    if ((long long)num_atoms * W > 0x7fffffffLL) return CONAN_E_UNSUPPORTED;
+    hipStream_t s = as_stream(stream);
+    const GraphBuildWs w = graph_build_ws(ws, num_atoms, num_graphs, W);
+    k_graph_build_lists<<<num_graphs, GB_THREADS, 0, s>>>(pos, graph_ptr, r * r, cap, loop, W, pairs || t_eid, pairs, w);
+    k_exclusive_scan_two<<<2, SCAN_THREADS, 0, s>>>(w.ecnt, w.pcnt, num_graphs, w.eoff, w.poff);
+    k_graph_build_fill<<<num_graphs, TR_THREADS, 0, s>>>(graph_ptr, num_atoms, W, w, rowptr, col, tgt, dist, pid, pair_e0, pair_e1, pair_dist,
+                                                         num_pairs, t_rowptr, t_eid);
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;
 }

@@ -21,6 +21,10 @@ def _c(t: Tensor) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ graphs
+FUSED_GRAPH_BUILD = True      # neighbour lists, pairs and transpose from conan_radius_graph_build (three launches); tools / tests switch the three
+                              # separate entry points back on to compare (never read from the environment)
+
+
 class RadiusGraph:
     """Device-resident neighbour lists of a batch of conformer graphs: CSR by target (+ lazily its by-source transpose).
 
@@ -28,7 +32,10 @@ class RadiusGraph:
     the layout the kernels consume.  `edge_index()` / `edge_weight()` export the reference's tensors (one host sync for E).
     """
 
-    def __init__(self, pos: Tensor, graph_ptr: Tensor, num_graphs: int, cutoff: float, max_num_neighbors: int, loop: bool = False):
+    def __init__(self, pos: Tensor, graph_ptr: Tensor, num_graphs: int, cutoff: float, max_num_neighbors: int, loop: bool = False,
+                 pairs: bool = False, transpose: bool = False):
+        """`pairs` / `transpose`: hints that the caller will ask for `pairs()` / `transpose()` — the fused build (FUSED_GRAPH_BUILD) then writes them
+        in the same three launches as the neighbour lists; without the hint they are built on first use by their own entry points."""
         pos = _c(pos)
         if pos.dtype != f32:
             raise RuntimeError("pos must be float32")
@@ -37,18 +44,34 @@ class RadiusGraph:
         self.num_atoms, self.num_graphs, self.graph_ptr = n, num_graphs, graph_ptr
         self.cutoff, self.cap, self.loop = float(cutoff), int(max_num_neighbors), bool(loop)
         # worst case per target: cap + 1 edges without self loops (the self hit may fall outside torch-cluster's cap + 1 window)
-        self.max_edges = max(1, n * (self.cap if self.loop else self.cap + 1))
+        self.max_edges = ME = max(1, n * (self.cap if self.loop else self.cap + 1))
         self.rowptr = torch.empty(n + 1, dtype=i32, device=dev)
-        self.col = torch.empty(self.max_edges, dtype=i32, device=dev)
-        self.tgt = torch.empty(self.max_edges, dtype=i32, device=dev)
-        self.dist = torch.empty(self.max_edges, dtype=f32, device=dev)
+        self.col = torch.empty(ME, dtype=i32, device=dev)
+        self.tgt = torch.empty(ME, dtype=i32, device=dev)
+        self.dist = torch.empty(ME, dtype=f32, device=dev)
         self._deg = torch.empty(n + 1, dtype=i32, device=dev)
-        call("conan_radius_graph_csr", ptr(pos), ptr(graph_ptr, i32), n, num_graphs, self.cutoff, self.cap, int(self.loop),
-             ptr(self._deg), ptr(self.rowptr), ptr(self.col), ptr(self.tgt), ptr(self.dist), stream_ptr())
-        self.num_edges_dev = self.rowptr[n:]            # device-side edge count (1-element view)
-        self._num_edges: Optional[int] = None
         self._t_rowptr = self._t_eid = None
         self.pid = None
+        if FUSED_GRAPH_BUILD:
+            ws = torch.empty(max(1, lib().conan_radius_graph_build_ws(n, num_graphs, self.cap, int(self.loop))), dtype=i32, device=dev)
+            if pairs:
+                self.pid = torch.empty(ME, dtype=i32, device=dev)
+                self.pair_e0 = torch.empty(ME, dtype=i32, device=dev)
+                self.pair_e1 = torch.empty(ME, dtype=i32, device=dev)
+                self.pair_dist = torch.empty(ME, dtype=f32, device=dev)
+                self.num_pairs_dev = torch.empty(1, dtype=i32, device=dev)
+            if transpose:
+                self._t_rowptr = torch.empty(n + 1, dtype=i32, device=dev)
+                self._t_eid = torch.empty(ME, dtype=i32, device=dev)
+            call("conan_radius_graph_build", ptr(pos) if n else None, ptr(graph_ptr, i32), n, num_graphs, self.cutoff, self.cap, int(self.loop), ptr(ws),
+                 ptr(self.rowptr), ptr(self.col), ptr(self.tgt), ptr(self.dist),
+                 ptr(self.pid), ptr(self.pair_e0 if pairs else None), ptr(self.pair_e1 if pairs else None), ptr(self.pair_dist if pairs else None),
+                 ptr(self.num_pairs_dev if pairs else None), ptr(self._t_rowptr), ptr(self._t_eid), stream_ptr())
+        else:
+            call("conan_radius_graph_csr", ptr(pos), ptr(graph_ptr, i32), n, num_graphs, self.cutoff, self.cap, int(self.loop),
+                 ptr(self._deg), ptr(self.rowptr), ptr(self.col), ptr(self.tgt), ptr(self.dist), stream_ptr())
+        self.num_edges_dev = self.rowptr[n:]            # device-side edge count (1-element view)
+        self._num_edges: Optional[int] = None
 
     @property
     def num_edges(self) -> int:

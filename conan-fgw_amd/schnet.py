@@ -63,8 +63,8 @@ class RadiusInteractionGraph(torch.nn.Module):
         self.cutoff = cutoff
         self.max_num_neighbors = max_num_neighbors
 
-    def csr(self, pos: Tensor, graph_ptr: Tensor, num_graphs: int) -> ops.RadiusGraph:
-        return ops.RadiusGraph(pos, graph_ptr, num_graphs, self.cutoff, self.max_num_neighbors, loop=False)
+    def csr(self, pos: Tensor, graph_ptr: Tensor, num_graphs: int, pairs: bool = False, transpose: bool = False) -> ops.RadiusGraph:
+        return ops.RadiusGraph(pos, graph_ptr, num_graphs, self.cutoff, self.max_num_neighbors, loop=False, pairs=pairs, transpose=transpose)
 
     def forward(self, pos: Tensor, batch: Tensor):
         num_graphs = int(batch[-1].item()) + 1 if batch.numel() else 0
@@ -204,7 +204,9 @@ class SchNetNoSum(torch.nn.Module):
         if num_graphs is None:
             num_graphs = hint_g if hint_g is not None else int(batch[-1].item()) + 1      # host sync only for foreign tensors; pass num_graphs= to avoid it
         gptr = ops.graph_ptr_from_batch(batch, num_graphs)
-        graph = self.interaction_graph.csr(pos, gptr, num_graphs)
+        # the fused filter shares one row per undirected pair, the backward of the message passing walks the by-source lists: built with the graph
+        pairs = self.fused_filter and ops.filter_fused_supported(self.num_gaussians, self.num_filters)
+        graph = self.interaction_graph.csr(pos, gptr, num_graphs, pairs=pairs, transpose=torch.is_grad_enabled())
         graph.max_nodes_hint = hint_n if hint_g == num_graphs else None
         return batch, gptr, graph, num_graphs
 

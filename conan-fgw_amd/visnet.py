@@ -107,7 +107,8 @@ class ViSNetBlock(torch.nn.Module):
     def forward(self, z: Tensor, pos: Tensor, graph_ptr: Tensor, num_graphs: int):
         """torch_geometric_visnet.py:843-886."""
         H, dev, n, s = self.hidden_channels, z.device, z.shape[0], stream_ptr()
-        g = ops.RadiusGraph(pos, graph_ptr, num_graphs, self.cutoff, self.max_num_neighbors, loop=True)      # Distance, :331-347
+        g = ops.RadiusGraph(pos, graph_ptr, num_graphs, self.cutoff, self.max_num_neighbors, loop=True,
+                            transpose=torch.is_grad_enabled())                                            # Distance, :331-347
         md, ME = g.num_edges_dev, g.max_edges
         dvec = torch.empty(ME, 3, dtype=f32, device=dev)                                                     # geometry: no gradient (pos is an input)
         call("conan_visnet_edge_unit", ptr(pos.contiguous(), f32), ptr(g.col), ptr(g.tgt), ptr(md), ME, ptr(dvec), s)

@@ -115,6 +115,17 @@ int conan_edge_pairs(const int *rowptr, const int *col, const int *tgt, const fl
                      int max_edges, int *flag_ws, int *pidx_ws, int *scan_ws, int *pid, int *pair_e0, int *pair_e1,
                      float *pair_dist, void *stream);
 
+/* The three calls above in one: neighbour lists, and — when their outputs are not NULL — the undirected pairs (pid, pair_e0, pair_e1, pair_dist
+ * and the device-side pair count num_pairs[1]: all five or none) and the by-source transpose (t_rowptr, t_eid: both or none), entry for entry what
+ * conan_radius_graph_csr + conan_edge_pairs + conan_csr_transpose leave (rows beyond the edge / pair count are unspecified), in three launches:
+ * one workgroup per graph scans the neighbours once and numbers edges, reverse edges and pair representatives inside the graph, a scan of the
+ * per-graph edge and pair counts, one workgroup per graph writes the lists at the graph's offsets.  No workgroup waits for another.  Output sizes as
+ * for the three calls; ws: conan_radius_graph_build_ws(...) ints of scratch.  pos may be NULL when num_atoms == 0. */
+long long conan_radius_graph_build_ws(int num_atoms, int num_graphs, int cap, int loop);
+int conan_radius_graph_build(const float *pos, const int *graph_ptr, int num_atoms, int num_graphs, float r, int cap, int loop, int *ws,
+                             int *rowptr, int *col, int *tgt, float *dist, int *pid, int *pair_e0, int *pair_e1, float *pair_dist,
+                             int *num_pairs, int *t_rowptr, int *t_eid, void *stream);
+
 /* edge_index[2, E] int64 in the reference's layout from the CSR (E = capacity of the output rows = host-known edge
  * count).  Row 0 = source, row 1 = target. */
 int conan_edge_index_i64(const int *col, const int *tgt, int num_edges, int64_t *edge_index, void *stream);
