@@ -11,7 +11,10 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # `conan_fgw_amd.get_model(name, device, **kw)` / `conan_fgw_amd.EquivModelsHolder`: the reference's model factory
     # (conan_fgw/src/model/common.py:469-546), resolved lazily so that importing the package needs neither torch nor the .so
-    if name in ("get_model", "EquivModelsHolder"):
+    # the five model classes train_val.py / experiments.py reach (schnet_based_models.py) and `classification_loss` (common.py:210-217) likewise
+    if name in ("get_model", "EquivModelsHolder", "EmbeddingsWithGATAggregation", "EmbeddingsWithGATAggregationBaryCenter",
+                "EmbeddingsWithGATAggregationClassification", "EmbeddingsWithGATAggregationClassificationBaryCenter", "EmbeddingsWithGAT",
+                "classification_loss"):
         from . import head
         return getattr(head, name)
     raise AttributeError(name)

@@ -136,6 +136,36 @@ __global__ void __launch_bounds__(256) k_mse_loss(const float *__restrict__ pred
     if (tid == 0) loss[0] = (((red[0] + red[1]) + red[2]) + red[3]) * inv;
 }
 
+// Binary cross-entropy of the classification step (the reference's classification_loss, common.py:210-217: F.binary_cross_entropy with an optional
+// weight) and its gradient in ONE launch, cut like k_mse_loss; n is a number of molecules.  Term for term torch's kernel and its backward:
+//   loss = (1/n) sum_i w_i * -( y_i max(log p_i, -100) + (1 - y_i) max(log(1 - p_i), -100) ),   dpred_i = w_i (p_i - y_i) / max(p_i (1 - p_i), 1e-12) / n.
+// The logarithms are clamped BEFORE they meet y (p = 1, y = 1 gives 0, not 0 * -inf).  nw = 0: no weight; 1: one weight for every element (the
+// reference's torch.tensor([cw[1] / cw[0]]), train_val.py:62); n: one per element.  A p outside [0, 1] gives NaN (logf of a negative number) where
+// torch raises a device-side assert, which would abort the process.  logf / log1pf, not the fast intrinsics.  One workgroup; the sum runs in a
+// fixed order (bitwise reproducible).
+__global__ void __launch_bounds__(256) k_bce_loss(const float *__restrict__ pred, const float *__restrict__ target, const float *__restrict__ weight, int nw,
+                                                  int n, float *__restrict__ loss, float *__restrict__ dpred) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const float inv = 1.0f / (float)n;
+    const float w1 = nw == 1 ? weight[0] : 1.0f;
+    float acc = 0.f;
+    for (int i = tid; i < n; i += 256) {
+        const float p = pred[i], y = target[i];
+        const float w = nw > 1 ? weight[i] : w1;
+        float lp = logf(p), lq = log1pf(-p);                         // log(1 - p) as torch forms it (1 - p itself rounds away 3e-5 of the term at p = 0.001)
+        lp = lp < -100.0f ? -100.0f : lp;                            // std::max as torch writes it: a NaN stays (fmaxf would turn it into -100)
+        lq = lq < -100.0f ? -100.0f : lq;
+        acc += w * -(y * lp + (1.0f - y) * lq);
+        dpred[i] = w * (p - y) / fmaxf(p * (1.0f - p), 1e-12f) * inv;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) loss[0] = (((red[0] + red[1]) + red[2]) + red[3]) * inv;
+}
+
 
 // Adam (torch.optim.Adam, no amsgrad / maximize) over ONE flat parameter buffer and its flat gradient, moment and step buffers (round 5): the step of
 // the reference's optimiser (train_val.py) for the whole model in one launch instead of torch's multi-tensor kernels (a step-counter foreach add
@@ -278,6 +308,14 @@ int conan_adam_flat_step(float *params, const float *grads, float *exp_avg, floa
 int conan_mse_loss_fwd(const float *pred, const float *target, int n, float *loss, float *dpred, void *stream) {
     if (!pred || !target || !loss || !dpred || n <= 0) return CONAN_E_BADARG;
     k_mse_loss<<<1, 256, 0, as_stream(stream)>>>(pred, target, n, loss, dpred);
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+int conan_bce_loss_fwd(const float *pred, const float *target, const float *weight, int n_weight, int n, float *loss, float *dpred, void *stream) {
+    if (!pred || !target || !loss || !dpred || n <= 0) return CONAN_E_BADARG;
+    if ((n_weight != 0 && n_weight != 1 && n_weight != n) || (n_weight > 0 && !weight)) return CONAN_E_BADARG;
+    k_bce_loss<<<1, 256, 0, as_stream(stream)>>>(pred, target, weight, n_weight, n, loss, dpred);
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;
 }

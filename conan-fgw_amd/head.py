@@ -158,8 +158,9 @@ class EmbeddingsWithGATAggregation(EmbeddingsWithGATAggregationBaryCenter):
 
 
 class _SelfAttentionParams(torch.nn.Module):
-    """`SelfAttention(out_channels)` (attention_layer.py:17-33): the classification model constructs it (:336) but never calls
-    it in forward; it exists here so that the reference's state_dict loads strictly."""
+    """`SelfAttention(out_channels)` (attention_layer.py:17-33): the stage-2 classification model constructs it (:336) but never calls
+    it in forward; it exists here so that the reference's state_dict loads strictly.  The stage-1 classification model applies it to a
+    sequence of length 1, which is `value` alone."""
 
     def __init__(self, dim: int):
         super().__init__()
@@ -220,3 +221,77 @@ class EmbeddingsWithGATAggregationClassificationBaryCenter(EmbeddingsWithGATAggr
         x = ops.relu(ops.linear(x, mlp[2].weight, mlp[2].bias))
         x = ops.linear(x, mlp[4].weight, mlp[4].bias)
         return ops.sigmoid(x)                                                                                         # :367
+
+
+class EmbeddingsWithGATAggregationClassification(EmbeddingsWithGATAggregationClassificationBaryCenter):
+    """Stage-1 classification model: `EmbeddingsWithGATAggregationClassification` (schnet_based_models.py:247-305 on
+    `EquivAggregationClassification`, common.py:426-466), the first stage of both classification experiments.  Same constructor and the same
+    sub-modules as the stage-2 twin above (`agg_weight` is accepted and unused: train_val.py passes it to every model class;
+    `transformation_matrix_bary` and the backbone's barycenter layers exist and are unused), so its `state_dict` has the twin's keys and shapes
+    and the stage-1 checkpoint loads strictly into stage 2 (train_val.py:175-183).
+
+    forward (:286-305): x = Lin3d(backbone(z, pos)) + Lin_cov(GAT(...)), `SelfAttention` over a sequence of length 1, conformer mean, the
+    three-layer ReLU MLP, sigmoid -> [G/K, 1] probabilities.  Everything before the MLP is linear, so the conformer mean is taken first.
+
+    Deviation: with one key the softmax of `SelfAttention` (attention_layer.py:17-33) is identically 1 and its output is
+    `self_attention.value(x)`; only that is computed.  `query` and `key` are not evaluated and their `.grad` stays None where the reference
+    leaves exact zeros — the same thing to Adam without weight decay (the reference's optimiser) and to `FlatGradients`.
+
+    The covalent branch runs on the current stream (no side stream): a captured step of this model has no parallel branches."""
+
+    def forward(self, batch, conformers_index: Tensor, node_index: Tensor, num_graphs: int = None, max_nodes: int = None) -> Tensor:
+        K = self.num_conformers
+        hint = {"num_graphs": num_graphs} if num_graphs is not None else {}
+        x_3d = self.node_embeddings_model(batch.z, batch.pos, node_index, **hint)                                     # :286
+        x_3d = ops.linear(x_3d, self.transformation_matrix_3d.weight, self.transformation_matrix_3d.bias)            # :287
+        x_cov = self.gat_embeddings_model(batch.x, batch.edge_index, batch.edge_attr, batch.batch, **hint)            # :289-291
+        x_cov = ops.linear(x_cov, self.transformation_matrix_cov.weight, self.transformation_matrix_cov.bias)        # :292
+        x = x_3d + x_cov                                                                                               # :294
+        G, d = x.shape
+        if conformers_index is not None and conformers_index.numel() != G:
+            raise ValueError("conformers_index must have one entry per conformer graph")
+        x = x.view(G // K, K, d).mean(dim=1).contiguous()                                                             # :301, ahead of the linear :297-299
+        value = self.self_attention.value
+        x = ops.linear(x, value.weight, value.bias)                                                                   # :297-299: softmax over one key = 1
+        mlp = self.molecular_regression_lin
+        x = ops.relu(ops.linear(x, mlp[0].weight, mlp[0].bias))                                                       # :302
+        x = ops.relu(ops.linear(x, mlp[2].weight, mlp[2].bias))
+        x = ops.linear(x, mlp[4].weight, mlp[4].bias)
+        return ops.sigmoid(x)                                                                                         # :303
+
+
+class EmbeddingsWithGAT(torch.nn.Module):
+    """The 2-D baseline of `GATExperiment`: `EmbeddingsWithGAT` (schnet_based_models.py:495-533 on `EquivAggregation`) without its Lightning
+    shell.  forward = molecular_regression_lin(GAT(x, edge_index, edge_attr, batch.batch)) -> [G, 1]: one row per conformer graph and NO
+    conformer mean — the reference's forward takes none (:528-533).  `node_embeddings_model` is constructed by the reference's base class
+    (common.py:400-402) and never used; it is kept so that a reference checkpoint loads strictly, and its parameters get no gradient."""
+
+    def __init__(self, num_conformers: int, device=None, model_name: str = "schnet", gat_in_channels: int = 9):
+        super().__init__()
+        from .gat import GATBased
+        self.num_conformers = num_conformers
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.node_embeddings_model = EquivModelsHolder.get_model(model_name, device, feat_dim=128)                    # common.py:400-402
+        out_channels = self.node_embeddings_model.hidden_channels // 2
+        self.gat_embeddings_model = (EquivModelsHolder.get_model("gat", device, feat_dim=128) if gat_in_channels == 9   # :508
+                                     else GATBased(out_channels=128 // 2, in_channels=gat_in_channels))
+        self.molecular_regression_lin = Linear(out_channels, 1)                                                       # build_mlp(out_channels), :509
+
+    def forward_dummy(self, batch, conformers_index, node_index):
+        """Nothing to materialise (see `EmbeddingsWithGATAggregationBaryCenter.forward_dummy`): returns None, CPU inputs included."""
+        return None
+
+    create_aggregation_index = EmbeddingsWithGATAggregationBaryCenter.create_aggregation_index
+    _aggregation_index = EmbeddingsWithGATAggregationBaryCenter._aggregation_index
+
+    def forward(self, batch, conformers_index: Tensor = None, node_index: Tensor = None, num_graphs: int = None, max_nodes: int = None) -> Tensor:
+        x_cov = self.gat_embeddings_model(batch.x, batch.edge_index, batch.edge_attr, batch.batch,
+                                          **({"num_graphs": num_graphs} if num_graphs is not None else {}))           # :528-530
+        return ops.linear(x_cov, self.molecular_regression_lin.weight, self.molecular_regression_lin.bias)            # :531
+
+
+def classification_loss(predicted: Tensor, expected: Tensor, class_weights: Tensor = None) -> Tensor:
+    """`classification_loss` of the reference's Lightning module (common.py:210-217): F.binary_cross_entropy(predicted, expected,
+    weight=class_weights), here `ops.bce_loss` — loss and gradient in one launch.  `class_weights` is tested with `is not None`: the reference's
+    `if class_weights:` on a one-element tensor is a host synchronisation (and the move to `expected`'s device happens inside the op)."""
+    return ops.bce_loss(predicted, expected, weight=class_weights)

@@ -1396,6 +1396,43 @@ def mse_loss(pred: Tensor, target: Tensor) -> Tensor:
     return _MseLossFn.apply(pred, target)
 
 
+class _BceLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, weight):
+        pred, target = _c(pred), _c(target)
+        if pred.shape != target.shape:
+            raise RuntimeError(f"bce_loss: pred {tuple(pred.shape)} and target {tuple(target.shape)} must have the same shape")
+        loss = torch.empty((), dtype=f32, device=pred.device)
+        dpred = torch.empty_like(pred)
+        call("conan_bce_loss_fwd", ptr(pred, f32), ptr(target, f32), ptr(weight, f32), 0 if weight is None else weight.numel(), pred.numel(),
+             ptr(loss), ptr(dpred), stream_ptr())
+        ctx.save_for_backward(dpred)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        if g.is_cuda and g.dtype == f32 and g.numel() == 1:        # the seed of loss.backward(): one HIP launch, as in _MseLossFn
+            out = torch.empty_like(dpred)
+            call("conan_scale_scalar", ptr(dpred), ptr(_c(g)), dpred.numel(), ptr(out), stream_ptr())
+            return out, None, None
+        return dpred * g, None, None
+
+
+def bce_loss(pred: Tensor, target: Tensor, weight: Optional[Tensor] = None) -> Tensor:
+    """torch.nn.functional.binary_cross_entropy(pred, target, weight) (mean reduction) with its gradient formed in the same launch: the criterion
+    of the reference's classification models (`classification_loss`, common.py:210-217).  Same terms as torch's kernel and its backward: both
+    logarithms clamped at -100, the gradient's denominator at 1e-12.  `weight`: None, one element (the reference's class weight,
+    train_val.py:62) or one per prediction; it is moved to pred's device and dtype without a host synchronisation.  The gradient goes to `pred`
+    only.  A prediction outside [0, 1] gives NaN where torch raises a device-side assert (which aborts the process).  No host synchronisation."""
+    if weight is not None:
+        if not isinstance(weight, Tensor) or weight.numel() not in (1, pred.numel()):
+            raise ValueError(f"bce_loss: weight must be a tensor of 1 or {pred.numel()} elements"
+                             + (f", got {weight.numel()}" if isinstance(weight, Tensor) else f", got {type(weight).__name__}"))
+        weight = _c(weight.detach().to(device=pred.device, dtype=pred.dtype, non_blocking=True).reshape(-1))
+    return _BceLossFn.apply(pred, target, weight)
+
+
 class _ReadoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Y, K, mode):

@@ -295,6 +295,17 @@ int conan_stage2_head_bwd(const float *dout, const float *W3, const float *Wb, c
  * small launches on the critical path between the forward and the backward of a step.  Fixed summation order. */
 int conan_mse_loss_fwd(const float *pred, const float *target, int n, float *loss, float *dpred, void *stream);
 
+/* Classification criterion of the training step and its gradient in one launch: torch.nn.functional.binary_cross_entropy (mean reduction) and its
+ * backward, term for term (classification_loss of the reference, common.py:210-217):
+ *   loss[0]  = (1/n) sum_i w_i * -( y_i max(log p_i, -100) + (1 - y_i) max(log(1 - p_i), -100) )
+ * (clamped before the product: p = y = 1 gives 0; log(1 - p) is formed as log1p(-p), as torch does)
+ *   dpred[i] = w_i (p_i - y_i) / max(p_i (1 - p_i), 1e-12) / n
+ * weight: n_weight = 0 (NULL allowed; w = 1), 1 (one value for every element: the reference's torch.tensor([cw[1] / cw[0]]), train_val.py:62) or n
+ * (one per element).  CONAN_E_BADARG, before any launch, for a null pred / target / loss / dpred, n <= 0, n_weight outside {0, 1, n}, or n_weight > 0
+ * with a null weight.  A p outside [0, 1] yields NaN (the logarithm of a negative number); torch raises a device-side assert there, which aborts the
+ * process, and that is not reproduced.  One workgroup, fixed summation order.  (Added export: the ABI version is unchanged.) */
+int conan_bce_loss_fwd(const float *pred, const float *target, const float *weight, int n_weight, int n, float *loss, float *dpred, void *stream);
+
 /* torch.optim.Adam's step (the reference's optimiser, train_val.py; no amsgrad, no maximize) for a WHOLE model in one launch (round 5): parameters,
  * gradients and both moments are flat fp32 buffers of n elements in one common order (16-byte aligned; conan_fgw_amd.parallel.FlatAdam lays the
  * parameters out in FlatGradients' order and re-points every Parameter at its slice).  step_dev: one device float holding the number of steps
