@@ -26,48 +26,19 @@
 // running beside them: the kernel is bound by the SUM of the two pipes, not by HBM (floor 61 us).  A variant with two waves per
 // tile (half the channel blocks each, 96 accumulator registers, 2 waves per SIMD) overlapped more (31 %) but issued 24 M VALU
 // instructions for the duplicated splitting and measured the same 95-98 us.
-#include "common.h"
+#include "fp_planes.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int FB_THREADS = 256, FB_WAVES = 4;
 constexpr int FB_GRID_MAX = 256;
 
-__device__ __forceinline__ void fb_split3(const float *v, bf16x8 &p1, bf16x8 &p2, bf16x8 &p3) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 h1 = (__bf16)v[j];
-        const float r1 = v[j] - (float)h1;
-        const __bf16 h2 = (__bf16)r1;
-        const float r2 = r1 - (float)h2;
-        p1[j] = h1; p2[j] = h2; p3[j] = (__bf16)r2;
-    }
-}
-
 // H16 (round 3): both products on TWO fp16 planes per operand (p1q1 + p1q2 + p2q1: 3 MFMAs instead of the 6 of the three-plane bf16
-// form, ~2^-22 relative) — see filter_fused.hip.  fp16's range needs the gradient operand scaled: `gmax` is max |g| over the whole
+// form, ~2^-22 relative) — see fp_planes.h.  fp16's range needs the gradient operand scaled: `gmax` is max |g| over the whole
 // tensor (the kernel that produced g tracked it, conan_cfconv_bwd_w_pairs), s = 2^k with s * gmax in [16, 32); A = s * g, the w2
 // planes carry their own power-of-two scale (from max |w2|), dh1 is formed as s * dh1 (<= 32 * column abs-sum of w2: far inside 65504) and the accumulated s * dW1 is
 // unscaled once, when the slab is written.  Entries below 2e-6 * gmax fall into fp16's subnormal spacing (3e-8 / s absolute): they
 // cannot matter to a sum dominated by entries 1e6 times larger.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void fb_split2h(const float *v, float sc, f16x8 &p1, f16x8 &p2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = v[j] * sc;
-        const _Float16 h1 = (_Float16)x;
-        p1[j] = h1; p2[j] = (_Float16)(x - (float)h1);
-    }
-}
-// plane scale of w2 (see filter_fused.hip: 2^k with max |w| * 2^k in [256, 512)); its inverse is applied where dh1 is formed
-__device__ __forceinline__ void fb_plane_scale(float amax, float &sc, float &un) {
-    sc = 1.0f; un = 1.0f;
-    if (amax > 0.f && amax < 3.0e38f) { int e; (void)frexpf(amax, &e); sc = ldexpf(1.0f, 9 - e); un = ldexpf(1.0f, e - 9); }
-}
 
 template <int F, bool H16>
 __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restrict__ g, const float *__restrict__ h1,
@@ -109,22 +80,10 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
 #pragma unroll
             for (int u = 0; u < PERW; ++u)
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    am = fmaxf(fmaxf(am, fmaxf(fabsf(wv[u][j].x), fabsf(wv[u][j].y))), fmaxf(fabsf(wv[u][j].z), fabsf(wv[u][j].w)));
-            am = wave_max(am);
-            if (lane == 0) wred[wave] = am;
-            __syncthreads();
-            const float wmax = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
-            fb_plane_scale(wmax, wsc, wun);
-            // gradient scale: s * gmax in [16, 32), lowered when the weights are so large that s * dh1 (<= 32 * F * max |w2|) could leave fp16
-            const float gm = *gmax;
-            if (gm > 0.f && gm < 3.0e38f) {
-                int e; (void)frexpf(gm, &e);
-                int sh = 5 - e;
-                const float bound = 32.0f * F * wmax;                   // upper bound of |s * dh1| at the nominal scale
-                if (bound > 16384.0f && bound < 3.0e38f) { int eb; (void)frexpf(bound * (1.0f / 16384.0f), &eb); sh -= eb; }
-                gsc = ldexpf(1.0f, sh); gun = ldexpf(1.0f, -sh);
-            }
+                for (int j = 0; j < 4; ++j) am = absmax4(am, wv[u][j]);
+            const float wmax = block_absmax<FB_THREADS>(am, wred);
+            pow2_scale(wmax, wsc, wun);                              // the plane scale of w2; its inverse is applied where dh1 is formed
+            grad_scale(*gmax, 32.0f * F * wmax, gsc, gun);           // bound: |s * dh1| <= 32 * F * max |w2| at the nominal scale
         }
 #pragma unroll
         for (int u = 0; u < PERW; ++u) {
@@ -137,14 +96,7 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
                                      e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
                                      e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
                                      e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                if constexpr (H16) {
-                    f16x4 q1, q2;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { const float x = v4[j] * wsc; q1[j] = (_Float16)x; q2[j] = (_Float16)(x - (float)q1[j]); }
-                    *reinterpret_cast<f16x4 *>(&WH[(0 * F + c0 + e) * WS + r0]) = q1;
-                    *reinterpret_cast<f16x4 *>(&WH[(1 * F + c0 + e) * WS + r0]) = q2;
-                    continue;
-                }
+                if constexpr (H16) { store4_planes(WH, F, WS, c0 + e, r0, v4, wsc); continue; }
                 bf16x4 q1, q2, q3;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -221,7 +173,7 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
             f16x8 qa[2][2];                                        // [double buffer][plane] of the A fragment (s * g)
             auto split_xh = [&](f16x8 (&dst)[2], int s) {
                 const float xv[8] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w, xb[s].x, xb[s].y, xb[s].z, xb[s].w};
-                fb_split2h(xv, gsc, dst[0], dst[1]);
+                split2h(xv, gsc, dst[0], dst[1]);
                 if (has_next) {                                    // this k-step's slice of g is consumed: reload it for the next tile
                     xa[s] = *reinterpret_cast<const float4 *>(xn + 16 * s);
                     xb[s] = *reinterpret_cast<const float4 *>(xn + 16 * s + 4);
@@ -260,7 +212,7 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
                         const float ex = exp_neg_f(coeff * (t * t));
                         rv[j] = jkind[jb] == 0 ? ex : (jkind[jb] == 2 ? 1.0f : 0.0f);
                     }
-                    fb_split2h(rv, 1.0f, rbh[s2][jb][0], rbh[s2][jb][1]);
+                    split2h(rv, rbh[s2][jb][0], rbh[s2][jb][1]);
                 }
             }
             // epilogue per channel block: s * dh1 = acc / 2^6 * ssp'(h1), then s * dw1[32kb.., :] += (s * dh1)^T rbf
@@ -277,7 +229,7 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
                         v[j] = ok ? d : 0.f;
                     }
                     f16x8 a1, a2;
-                    fb_split2h(v, 1.0f, a1, a2);
+                    split2h(v, a1, a2);
 #pragma unroll
                     for (int jb = 0; jb < 2; ++jb) dwacc[kb][jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, rbh[s2][jb][0], dwacc[kb][jb], 0, 0, 0);
 #pragma unroll
@@ -305,7 +257,7 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
         };
         auto split_x = [&](bf16x8 (&dst)[3], int s) {
             const float xv[8] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w, xb[s].x, xb[s].y, xb[s].z, xb[s].w};
-            fb_split3(xv, dst[0], dst[1], dst[2]);
+            split3(xv, dst[0], dst[1], dst[2]);
             if (has_next) {                                    // this k-step's slice of g is consumed: reload it for the next tile
                 xa[s] = *reinterpret_cast<const float4 *>(xn + 16 * s);
                 xb[s] = *reinterpret_cast<const float4 *>(xn + 16 * s + 4);
@@ -347,7 +299,7 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
                     const float ex = exp_neg_f(coeff * (t * t));
                     rv[j] = jkind[jb] == 0 ? ex : (jkind[jb] == 2 ? 1.0f : 0.0f);
                 }
-                fb_split3(rv, rb[s2][jb][0], rb[s2][jb][1], rb[s2][jb][2]);
+                split3(rv, rb[s2][jb][0], rb[s2][jb][1], rb[s2][jb][2]);
             }
         }
         constexpr int PP2[6] = {0, 1, 2, 0, 1, 0};             // (a3,b1) (a2,b2) (a1,b3) (a2,b1) (a1,b2) (a1,b1)
@@ -365,7 +317,7 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
                     v[j] = ok ? d : 0.f;
                 }
                 bf16x8 a1, a2, a3;
-                fb_split3(v, a1, a2, a3);
+                split3(v, a1, a2, a3);
 #pragma unroll
                 for (int t = 0; t < 6; ++t)
 #pragma unroll

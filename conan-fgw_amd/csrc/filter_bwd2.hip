@@ -27,7 +27,7 @@
 //
 // Arithmetic: identical to the two kernels it replaces (two fp16 planes per operand, three partial products per fp32 product, fp32
 // accumulation; g scaled from its device-side maximum, w2 planes carrying their own power-of-two scale) — the same tests, same tolerances.
-#include "common.h"
+#include "fp_planes.h"
 
 // Phase timing (tools/f2_phase_profile.py builds a private library with -DCONAN_F2_PROFILE; the product library contains none of this): lane 0
 // of every wavefront accumulates shader-clock ticks between marks and adds them to 16 global slots at the end (slots 0-7: A wavefronts, 8-15: B).
@@ -49,9 +49,6 @@ extern "C" int conan_debug_f2_prof(long long *out, int reset) {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 
 constexpr int F2_RING = 1;                                     // tiles in flight per workgroup beyond the one being stored (staging registers: 16 + 8 per tile and thread; 2 measured no faster)
@@ -87,18 +84,6 @@ __device__ __forceinline__ f16x8 f2_tr8(const char *plane, int r0, int c0, int l
     r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3]; r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
     return r;
 }
-__device__ __forceinline__ void f2_split2h(const float *v, float sc, f16x8 &p1, f16x8 &p2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = v[j] * sc;
-        const _Float16 h1 = (_Float16)x;
-        p1[j] = h1; p2[j] = (_Float16)(x - (float)h1);
-    }
-}
-__device__ __forceinline__ void f2_plane_scale(float amax, float &sc, float &un) {      // 2^k with amax * 2^k in [256, 512) (filter_fused.hip)
-    sc = 1.0f; un = 1.0f;
-    if (amax > 0.f && amax < 3.0e38f) { int e; (void)frexpf(amax, &e); sc = ldexpf(1.0f, 9 - e); un = ldexpf(1.0f, e - 9); }
-}
 
 __global__ void __launch_bounds__(F2_THREADS, 1) k_filter_bwd2(const float *__restrict__ g, const float *__restrict__ h1, const float *__restrict__ dist,
                                                                const float *__restrict__ offset, int Gs, float coeff, const float *__restrict__ w2, int M,
@@ -132,24 +117,10 @@ __global__ void __launch_bounds__(F2_THREADS, 1) k_filter_bwd2(const float *__re
 #pragma unroll
         for (int u = 0; u < PERW; ++u)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                am = fmaxf(fmaxf(am, fmaxf(fabsf(wv[u][j].x), fabsf(wv[u][j].y))), fmaxf(fabsf(wv[u][j].z), fabsf(wv[u][j].w)));
-        am = wave_max(am);
-        if (lane == 0) wred[wave] = am;
-        __syncthreads();
-        float wmax = wred[0];
-#pragma unroll
-        for (int w = 1; w < F2_WAVES; ++w) wmax = fmaxf(wmax, wred[w]);
-        f2_plane_scale(wmax, wsc, wun);
-        // gradient scale: s * gmax in [16, 32), lowered when the weights are so large that s * dh1 (<= 32 * F * max |w2|) could leave fp16
-        const float gm = *gmax;
-        if (gm > 0.f && gm < 3.0e38f) {
-            int e; (void)frexpf(gm, &e);
-            int sh = 5 - e;
-            const float bound = 32.0f * F * wmax;
-            if (bound > 16384.0f && bound < 3.0e38f) { int eb; (void)frexpf(bound * (1.0f / 16384.0f), &eb); sh -= eb; }
-            gsc = ldexpf(1.0f, sh); gun = ldexpf(1.0f, -sh);
-        }
+            for (int j = 0; j < 4; ++j) am = absmax4(am, wv[u][j]);
+        const float wmax = block_absmax<F2_THREADS>(am, wred);
+        pow2_scale(wmax, wsc, wun);
+        grad_scale(*gmax, 32.0f * F * wmax, gsc, gun);           // the same scales as k_filter_bwd (filter_bwd.hip): bound of |s * dh1| at the nominal scale
 #pragma unroll
         for (int u = 0; u < PERW; ++u) {
             const int pt = wave + u * F2_WAVES;
@@ -161,11 +132,7 @@ __global__ void __launch_bounds__(F2_THREADS, 1) k_filter_bwd2(const float *__re
                                      e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
                                      e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
                                      e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                f16x4 q1, q2;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { const float x = v4[j] * wsc; q1[j] = (_Float16)x; q2[j] = (_Float16)(x - (float)q1[j]); }
-                *reinterpret_cast<f16x4 *>(&WH[(0 * F + c0 + e) * WS + r0]) = q1;
-                *reinterpret_cast<f16x4 *>(&WH[(1 * F + c0 + e) * WS + r0]) = q2;
+                store4_planes(WH, F, WS, c0 + e, r0, v4, wsc);
             }
         }
     }
@@ -216,10 +183,10 @@ __global__ void __launch_bounds__(F2_THREADS, 1) k_filter_bwd2(const float *__re
         for (int j = 0; j < 8; ++j) cs[j] += gv[j];
         f16x8 p1, p2;
         const int o = buf * F2_IMG_BYTES + f2_off(srow, sch);
-        f2_split2h(gv, gsc, p1, p2);
+        split2h(gv, gsc, p1, p2);
         *reinterpret_cast<f16x8 *>(GI + o) = p1;
         *reinterpret_cast<f16x8 *>(GI + o + F2_IMG_PLANE) = p2;
-        f2_split2h(hv, 1.0f, p1, p2);
+        split2h(hv, p1, p2);
         *reinterpret_cast<f16x8 *>(HI + o) = p1;
         *reinterpret_cast<f16x8 *>(HI + o + F2_IMG_PLANE) = p2;
         if (wave >= 4) {
@@ -230,7 +197,7 @@ __global__ void __launch_bounds__(F2_THREADS, 1) k_filter_bwd2(const float *__re
                 const float ex = exp_neg_f(coeff * (t * t));
                 rv[j] = jkind == 0 ? ex : (jkind == 2 ? 1.0f : 0.0f);
             }
-            f2_split2h(rv, 1.0f, p1, p2);
+            split2h(rv, p1, p2);
             char *ro = RB + buf * F2_RB_BYTES + (bu * 2) * F2_RB_FRAG + lane * 16;
             *reinterpret_cast<f16x8 *>(ro) = p1;
             *reinterpret_cast<f16x8 *>(ro + F2_RB_FRAG) = p2;
@@ -313,7 +280,7 @@ __global__ void __launch_bounds__(F2_THREADS, 1) k_filter_bwd2(const float *__re
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 f16x8 a1, a2;
-                f2_split2h(dh + 8 * s2, 1.0f, a1, a2);
+                split2h(dh + 8 * s2, a1, a2);
 #pragma unroll
                 for (int jb = 0; jb < 2; ++jb) {
                     const f16x8 r1 = *reinterpret_cast<const f16x8 *>(Rp + ((s2 * 2 + jb) * 2) * F2_RB_FRAG);

@@ -18,43 +18,12 @@
 // Wavefronts never synchronise after staging: 8 independent waves per CU issue MFMAs back to back, both GEMMs as two-plane fp16 splits on
 // v_mfma_f32_32x32x16_f16 (three partial products per fp32 product, fp32-class accuracy; there is no other arithmetic mode and no
 // environment switch.  Round 2 used three bf16 planes and six partial products: same accuracy, 28 % slower, removed in round 4).
-#include "common.h"
+#include "fp_planes.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-// Two-plane fp16 split of 8 fp32 values: v = h1 + h2 up to 2^-22 |v| while the remainder v - h1 is a normal fp16 number (|v| >~ 0.06),
-// and to 3e-8 absolute below that (fp16 subnormal spacing).  With the three products p1q1, p1q2, p2q1 (the dropped p2q2 is 2^-22
-// relative) an fp16 MFMA chain reproduces the fp32 product to ~2.4e-7 at HALF the matrix-pipe time and ~2/3 of the splitting work
-// of a three-plane bf16 form (6 products).  Range: the operands here are O(1e-2..1e2) — Gaussians in [0, 1], shifted-softplus
-// outputs, weights pre-scaled by a power of two chosen from their maximum (exact, undone in the epilogue's FMA) — far inside fp16's 6e-5..65504.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void split2h(const float *v, f16x8 &p1, f16x8 &p2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const _Float16 h1 = (_Float16)v[j];
-        p1[j] = h1; p2[j] = (_Float16)(v[j] - (float)h1);
-    }
-}
-// Weight pre-scale of the fp16 planes: 2^k with max |w| * 2^k in [256, 512) — whatever the magnitude of the weights, their planes sit in the
-// middle of fp16's range (remainders normal, nothing near 65504); the exact inverse goes into the epilogue's FMA.  One block-wide
-// maximum per matrix at staging time.
-__device__ __forceinline__ void plane_scale(float amax, float &sc, float &un) {
-    sc = 1.0f; un = 1.0f;
-    if (amax > 0.f && amax < 3.0e38f) { int e; (void)frexpf(amax, &e); sc = ldexpf(1.0f, 9 - e); un = ldexpf(1.0f, e - 9); }
-}
-template <int NT>
-__device__ __forceinline__ float block_absmax(float v, float *red) {      // red: NT / 64 floats of LDS; every thread gets the maximum
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float m = red[0];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, red[w]);
-    return m;
-}
-
+// Both GEMMs on two fp16 planes per operand (fp_planes.h).  Range: the operands here are O(1e-2..1e2) — Gaussians in [0, 1], shifted-softplus
+// outputs, weights pre-scaled by pow2_scale of their block maximum (one per matrix at staging time, undone in the epilogue's FMA).
 constexpr int GP = 64;        // gaussians padded to four MFMA k-steps of 16 (zero weights beyond num_gaussians)
 constexpr int W1S = GP + 8;   // LDS pitch of a W1 row in the split images (16-bit elements: 144 B, 16-B slots of 8 consecutive rows stay distinct)
 constexpr int FF_THREADS = 512;      // eight wavefronts per workgroup.  (Twelve — three per SIMD, 154 KB of LDS, 160 registers — measured the same in an in-process A/B:
@@ -107,7 +76,8 @@ __global__ void __launch_bounds__(NT) k_filter_fused(
         float am = 0.f;
 #pragma unroll
         for (int u = 0; u < PER1; ++u) am = fmaxf(am, fabsf(wv[u]));
-        plane_scale(block_absmax<NT>(am, wred), sc1, us1);
+        __syncthreads();                                         // (wred)
+        pow2_scale(block_absmax<NT>(am, wred), sc1, us1);
 #pragma unroll
         for (int u = 0; u < PER1; ++u) {
             const int t = tid + u * NT, f = t / GP, k = t - f * GP;
@@ -133,7 +103,8 @@ __global__ void __launch_bounds__(NT) k_filter_fused(
         float am = 0.f;
 #pragma unroll
         for (int u = 0; u < PER2; ++u) am = fmaxf(am, fabsf(wv[u]));
-        plane_scale(block_absmax<NT>(am, wred), sc2, us2);
+        __syncthreads();                                         // wred is reused
+        pow2_scale(block_absmax<NT>(am, wred), sc2, us2);
 #pragma unroll
         for (int u = 0; u < PER2; ++u) {
             const int t = tid + u * NT;

@@ -7,11 +7,9 @@
 // Tiling: 256 threads = 4 wavefronts as 2(M) x 2(N); block tile 64 x (64*NB), K step 32.  Operands are staged in LDS
 // with odd pitches (33 / BN+1 floats) so that both the transposed staging writes and the MFMA fragment reads
 // (lane -> row for A, lane -> column for B) are bank-conflict free with ds_read_b32.
-#include "common.h"
+#include "fp_planes.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 64;
 constexpr int BK = 32;
@@ -251,17 +249,6 @@ constexpr int WG_SLICES_MAX = 768;      // 3 workgroups per CU
 // bf16-split arithmetic of the weight gradient: 16 rows per MFMA step; an operand fragment (8 consecutive rows of one
 // column per lane) is split exactly into three bf16 parts, six partial products per 32x32 block on
 // v_mfma_f32_32x32x16_bf16 (fp32-class accuracy, 2.7x the fp32 MFMA rate).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void wg_split3(const float *v, bf16x8 &p1, bf16x8 &p2, bf16x8 &p3) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 h1 = (__bf16)v[j];
-        const float r1 = v[j] - (float)h1;
-        const __bf16 h2 = (__bf16)r1;
-        const float r2 = r1 - (float)h2;
-        p1[j] = h1; p2[j] = h2; p3[j] = (__bf16)r2;
-    }
-}
 __device__ __forceinline__ f32x16 wg_mma6(const bf16x8 &a1, const bf16x8 &a2, const bf16x8 &a3, const bf16x8 &b1, const bf16x8 &b2,
                                          const bf16x8 &b3, f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
@@ -284,9 +271,8 @@ __device__ __forceinline__ f32x16 wg_mma6(const bf16x8 &a1, const bf16x8 &a2, co
 // `slice` of `num_slices` row slices, 128-row tile `tile_n` of N, KT-wide tile `tile_k` of K: blockIdx / gridDim of the plain launch,
 // decoded from a job table by the batched one.
 // H16 (round 3, the edge-level dw2 = g^T h1 of the filter network): two fp16 planes per operand and three MFMAs per product instead of
-// three bf16 planes and six (filter_fused.hip); g is scaled by s = 2^k with s * gmax in [16, 32) (gmax = max |g|, tracked by the kernel
+// three bf16 planes and six (fp_planes.h); g is scaled by s = 2^k with s * gmax in [16, 32) (gmax = max |g|, tracked by the kernel
 // that produced g), x (shifted-softplus outputs, O(1)) goes in unscaled, the slab is unscaled as it is written.
-typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
 template <int KT, bool RBF, bool H16 = false>
 __device__ __forceinline__ void wgrad_lds_body(const float *__restrict__ g, const float *__restrict__ x, int M, int K, int N,
                                                float *__restrict__ slabs, float *__restrict__ bias_slabs,
@@ -300,10 +286,7 @@ __device__ __forceinline__ void wgrad_lds_body(const float *__restrict__ g, cons
     __shared__ uint4 frag[2][NPL][RG][W];
     if (m_dev) M = min(M, *m_dev);
     float gsc = 1.0f, gun = 1.0f;
-    if constexpr (H16) {
-        const float gm = *gmax;
-        if (gm > 0.f && gm < 3.0e38f) { int e; (void)frexpf(gm, &e); gsc = ldexpf(1.0f, 5 - e); gun = ldexpf(1.0f, e - 5); }
-    }
+    if constexpr (H16) grad_scale(*gmax, 0.f, gsc, gun);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
     const int n0 = KT == 128 ? (wave >> 1) * 64 : wave * 32, k0 = KT == 128 ? (wave & 1) * 64 : 0;     // inside the tile
@@ -379,15 +362,14 @@ __device__ __forceinline__ void wgrad_lds_body(const float *__restrict__ g, cons
             if (f_isg[i]) bsum[i] += ((st[i][0] + st[i][1]) + (st[i][2] + st[i][3])) + ((st[i][4] + st[i][5]) + (st[i][6] + st[i][7]));
             if constexpr (H16) {
                 const float sc = f_isg[i] ? gsc : 1.0f;
-                wg_f16x8 p1, p2;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float v = st[i][j] * sc; p1[j] = (_Float16)v; p2[j] = (_Float16)(v - (float)p1[j]); }
+                f16x8 p1, p2;
+                split2h(st[i], sc, p1, p2);
                 frag[buf][0][f_rg[i]][f_col[i]] = __builtin_bit_cast(uint4, p1);
                 frag[buf][1][f_rg[i]][f_col[i]] = __builtin_bit_cast(uint4, p2);
                 continue;
             }
             bf16x8 p1, p2, p3;
-            wg_split3(st[i], p1, p2, p3);
+            split3(st[i], p1, p2, p3);
             frag[buf][0][f_rg[i]][f_col[i]] = __builtin_bit_cast(uint4, p1);
             frag[buf][1][f_rg[i]][f_col[i]] = __builtin_bit_cast(uint4, p2);
             frag[buf][2][f_rg[i]][f_col[i]] = __builtin_bit_cast(uint4, p3);
@@ -395,13 +377,13 @@ __device__ __forceinline__ void wgrad_lds_body(const float *__restrict__ g, cons
     };
     auto compute = [&](int buf) {
         if constexpr (H16) {
-            wg_f16x8 p[TNB][2], q[2][2];
+            f16x8 p[TNB][2], q[2][2];
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
 #pragma unroll
-                for (int a = 0; a < TNB; ++a) p[a][pl] = __builtin_bit_cast(wg_f16x8, frag[buf][pl][h][n0 + 32 * a + l31]);
+                for (int a = 0; a < TNB; ++a) p[a][pl] = __builtin_bit_cast(f16x8, frag[buf][pl][h][n0 + 32 * a + l31]);
 #pragma unroll
-                for (int b = 0; b < 2; ++b) q[b][pl] = __builtin_bit_cast(wg_f16x8, frag[buf][pl][h][128 + k0 + 32 * b + l31]);
+                for (int b = 0; b < 2; ++b) q[b][pl] = __builtin_bit_cast(f16x8, frag[buf][pl][h][128 + k0 + 32 * b + l31]);
             }
             constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 1, 0};          // (a2,b1) (a1,b2) (a1,b1): smallest terms first
 #pragma unroll
@@ -617,7 +599,7 @@ __global__ void __launch_bounds__(64 * NW, (NJ == 2 && NW == 4) ? 2 : 1) k_wgrad
             }
             if (f_op[i] < NJ) bsum[i] += ((sr[i][0] + sr[i][1]) + (sr[i][2] + sr[i][3])) + ((sr[i][4] + sr[i][5]) + (sr[i][6] + sr[i][7]));
             bf16x8 p1, p2, p3;
-            wg_split3(sr[i], p1, p2, p3);
+            split3(sr[i], p1, p2, p3);
             frag(buf, 0, f_rg[i], f_col[i]) = __builtin_bit_cast(uint4, p1);
             frag(buf, 1, f_rg[i], f_col[i]) = __builtin_bit_cast(uint4, p2);
             frag(buf, 2, f_rg[i], f_col[i]) = __builtin_bit_cast(uint4, p3);

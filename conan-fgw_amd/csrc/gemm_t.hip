@@ -7,62 +7,19 @@
 // keeps K/8 independent 16-B loads in flight.  W ([N][K+4] in LDS, <= 68 KB) is read as conflict-free ds_read_b128 A
 // fragments, software-pipelined one group ahead.  The accumulators (D layout: row = feature, column = x row) are
 // stored / combined with `residual` as float4 per lane.
-#include "common.h"
+#include "fp_planes.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int LT_THREADS = 512;
 #ifndef CONAN_LINEAR_MAX_WGS
 #define CONAN_LINEAR_MAX_WGS 256                    // persistent workgroups of an edge-level launch (one per CU: 137-141 KB of LDS each); a multiple of 16
 #endif
 
-
-// Two-plane fp16 form (default; see filter_fused.hip): v = h1 + h2 with the three products p1q1, p1q2, p2q1 on v_mfma_f32_32x32x16_f16 —
-// half the matrix-pipe time and 2/3 of the splitting work of the three-plane bf16 form.  fp16's narrow exponent range is met by exact
-// power-of-two scales: the weight by one factor per matrix (block maximum at staging time -> max |w| in [256, 512)), every x ROW by its
-// own factor (the row lives on one lane pair, so its maximum costs one cross-half exchange) — both undone by one multiply per output in
-// the epilogue (the D column is the x row, so the row factor is a per-lane scalar).  Inside a row, elements down to 2^-12 of the row
-// maximum keep 22 bits; below that the absolute error is 3e-8 / 256 of the row maximum.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+// Two-plane fp16 form (fp_planes.h): one power-of-two scale per weight matrix, one per x ROW (the row lives on one lane pair, so its maximum
+// costs one cross-half exchange) — both undone by one multiply per output in the epilogue (the D column is the x row, so the row factor is a per-lane scalar).
 constexpr int LT_NPL = 2;                                      // operand planes
 constexpr int LT_OP = 68;                                      // pitch of the per-wave output slab (floats): 64 channels + 4
-__device__ __forceinline__ void split2h(const float *v, float sc, f16x8 &p1, f16x8 &p2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float t = v[j] * sc;
-        const _Float16 h1 = (_Float16)t;
-        p1[j] = h1; p2[j] = (_Float16)(t - (float)h1);
-    }
-}
-// 2^k with amax * 2^k in [256, 512) and its inverse, from the exponent field (zero / subnormal / non-finite maxima: 1)
-__device__ __forceinline__ void pow2_scale(float amax, float &sc, float &un) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-    const bool ok = e >= 9 && e <= 254;
-    sc = ok ? __uint_as_float((unsigned)(262 - e) << 23) : 1.0f;
-    un = ok ? __uint_as_float((unsigned)(e - 8) << 23) : 1.0f;
-}
-template <int NT>
-__device__ __forceinline__ float lt_block_absmax(float v, float *red) {      // red: NT / 64 floats of LDS; every thread gets the maximum
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float m = red[0];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, red[w]);
-    return m;
-}
-// four consecutive k of image row n: 8-byte stores, one per plane
-__device__ __forceinline__ void lt_store4(void *WBv, int N, int WS, int n, int k, const float *v4, float sc) {
-    _Float16 *WB = reinterpret_cast<_Float16 *>(WBv);
-    f16x4 h1, h2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const float t = v4[e] * sc; h1[e] = (_Float16)t; h2[e] = (_Float16)(t - (float)h1[e]); }
-    *reinterpret_cast<f16x4 *>(&WB[(0 * N + n) * WS + k]) = h1;
-    *reinterpret_cast<f16x4 *>(&WB[(1 * N + n) * WS + k]) = h2;
-}
 
 // SPLIT variant: both operands are split into two fp16 planes (above) and the product is formed from the three significant
 // partial products on v_mfma_f32_32x32x16_f16 (fp32-class accuracy).  W's two planes are
@@ -146,15 +103,15 @@ __global__ void __launch_bounds__(NT) k_linear_t16(const float *__restrict__ x, 
         float wsc = 1.0f;
         float am = 0.f;
 #pragma unroll
-        for (int u = 0; u < PER; ++u) am = fmaxf(am, fmaxf(fmaxf(fabsf(wv[u].x), fabsf(wv[u].y)), fmaxf(fabsf(wv[u].z), fabsf(wv[u].w))));
-        pow2_scale(lt_block_absmax<NT>(am, wred), wsc, wun);
+        for (int u = 0; u < PER; ++u) am = absmax4(am, wv[u]);
+        pow2_scale(block_absmax<NT>(am, wred), wsc, wun);
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int q = tid + u * NT;
             if (q >= V4) continue;
             const float v4[4] = {wv[u].x, wv[u].y, wv[u].z, wv[u].w};
             const int n = (4 * q) / K, k = 4 * q - n * K;
-            lt_store4(WB, N, WS, n, k, v4, wsc);
+            store4_planes(WB, N, WS, n, k, v4, wsc);
         }
     } else {
         // w is [K][N] (the dx GEMM of the backward reads the forward weight transposed).  A thread owns a 4(k) x 4(n) block:
@@ -178,8 +135,8 @@ __global__ void __launch_bounds__(NT) k_linear_t16(const float *__restrict__ x, 
         for (int u = 0; u < PERW; ++u)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                am = fmaxf(am, fmaxf(fmaxf(fabsf(wv[u][j].x), fabsf(wv[u][j].y)), fmaxf(fabsf(wv[u][j].z), fabsf(wv[u][j].w))));
-        pow2_scale(lt_block_absmax<NT>(am, wred), wsc, wun);
+                am = absmax4(am, wv[u][j]);
+        pow2_scale(block_absmax<NT>(am, wred), wsc, wun);
 #pragma unroll
         for (int u = 0; u < PERW; ++u) {
             const int pt = wave + u * (NT / 64);
@@ -191,7 +148,7 @@ __global__ void __launch_bounds__(NT) k_linear_t16(const float *__restrict__ x, 
                                      e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
                                      e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
                                      e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                lt_store4(WB, N, WS, n0 + e, k0, v4, wsc);
+                store4_planes(WB, N, WS, n0 + e, k0, v4, wsc);
             }
         }
     }
@@ -210,8 +167,8 @@ __global__ void __launch_bounds__(NT) k_linear_t16(const float *__restrict__ x, 
         float am = 0.f;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(xa[s].x), fabsf(xa[s].y)), fmaxf(fabsf(xa[s].z), fabsf(xa[s].w))));
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(xb[s].x), fabsf(xb[s].y)), fmaxf(fabsf(xb[s].z), fabsf(xb[s].w))));
+            am = absmax4(am, xa[s]);
+            am = absmax4(am, xb[s]);
         }
         am = fmaxf(am, __shfl_xor(am, 32));                // the other half of the row sits on lane ^ 32
         float xsc, xu;
@@ -267,7 +224,7 @@ __global__ void __launch_bounds__(NT) k_linear_t16(const float *__restrict__ x, 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (act == 1) v[u] = ssp_f(v[u]);
-                    else if (act == 3) v[u] = v[u] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[u]));      // hardware reciprocal (1 ulp), as visnet.hip's silu_f
+                    else if (act == 3) v[u] = v[u] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[u]));      // hardware reciprocal (1 ulp), as silu_f of visnet_common.h
                     if (act == 2) v[u] *= 1.0f - 0.5f * __expf(-r4[u]);
                     else if (rr) v[u] += r4[u];
                 }
@@ -369,8 +326,8 @@ __device__ __forceinline__ int lt_stage_planes(const float *__restrict__ w, int 
         }
         float am = 0.f;
 #pragma unroll
-        for (int u = 0; u < PER; ++u) am = fmaxf(am, fmaxf(fmaxf(fabsf(wv[u].x), fabsf(wv[u].y)), fmaxf(fabsf(wv[u].z), fabsf(wv[u].w))));
-        ew = pow2_exp(lt_block_absmax<NT>(am, wred));
+        for (int u = 0; u < PER; ++u) am = absmax4(am, wv[u]);
+        ew = pow2_exp(block_absmax<NT>(am, wred));
         const float wsc = ew == LT_NOEXP ? 1.0f : pow2i(-ew);
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
@@ -378,7 +335,7 @@ __device__ __forceinline__ int lt_stage_planes(const float *__restrict__ w, int 
             if (q >= V4) continue;
             const float v4[4] = {wv[u].x, wv[u].y, wv[u].z, wv[u].w};
             const int n = (4 * q) / K, k = 4 * q - n * K;
-            lt_store4(WB, N, WS, n, k, v4, wsc);
+            store4_planes(WB, N, WS, n, k, v4, wsc);
         }
     } else {
         constexpr int PATCHES = (K / 16) * (N / 64), PERW = (PATCHES + NT / 64 - 1) / (NT / 64);
@@ -397,8 +354,8 @@ __device__ __forceinline__ int lt_stage_planes(const float *__restrict__ w, int 
         for (int u = 0; u < PERW; ++u)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                am = fmaxf(am, fmaxf(fmaxf(fabsf(wv[u][j].x), fabsf(wv[u][j].y)), fmaxf(fabsf(wv[u][j].z), fabsf(wv[u][j].w))));
-        ew = pow2_exp(lt_block_absmax<NT>(am, wred));
+                am = absmax4(am, wv[u][j]);
+        ew = pow2_exp(block_absmax<NT>(am, wred));
         const float wsc = ew == LT_NOEXP ? 1.0f : pow2i(-ew);
 #pragma unroll
         for (int u = 0; u < PERW; ++u) {
@@ -411,7 +368,7 @@ __device__ __forceinline__ int lt_stage_planes(const float *__restrict__ w, int 
                                      e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
                                      e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
                                      e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                lt_store4(WB, N, WS, n0 + e, k0, v4, wsc);
+                store4_planes(WB, N, WS, n0 + e, k0, v4, wsc);
             }
         }
     }
@@ -501,8 +458,8 @@ __global__ void __launch_bounds__(NT) k_linear_sum16(const LtSrcs Sx, const floa
             float am = 0.f;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                am = fmaxf(am, fmaxf(fmaxf(fabsf(xa[s].x), fabsf(xa[s].y)), fmaxf(fabsf(xa[s].z), fabsf(xa[s].w))));
-                am = fmaxf(am, fmaxf(fmaxf(fabsf(xb[s].x), fabsf(xb[s].y)), fmaxf(fabsf(xb[s].z), fabsf(xb[s].w))));
+                am = absmax4(am, xa[s]);
+                am = absmax4(am, xb[s]);
             }
             am = fmaxf(am, __shfl_xor(am, 32));
             const int ex = pow2_exp(am);
@@ -612,8 +569,8 @@ __global__ void __launch_bounds__(NT) k_linear_fan16(const float *__restrict__ x
         float am = 0.f;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(xa[s].x), fabsf(xa[s].y)), fmaxf(fabsf(xa[s].z), fabsf(xa[s].w))));
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(xb[s].x), fabsf(xb[s].y)), fmaxf(fabsf(xb[s].z), fabsf(xb[s].w))));
+            am = absmax4(am, xa[s]);
+            am = absmax4(am, xb[s]);
         }
         am = fmaxf(am, __shfl_xor(am, 32));
         float xsc, xu;

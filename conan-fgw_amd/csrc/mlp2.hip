@@ -14,39 +14,17 @@
 // 32-row tile: GEMM1's B operand are its x rows straight from global memory (requested before the weights are staged), GEMM2's B
 // operand IS GEMM1's accumulator after the element-wise step (register r of lane-half h = channel 32nb + (r&3) + 8(r>>2) + 4h, so
 // the second weight is staged with the matching column permutation) — nothing crosses lanes or LDS between the two GEMMs.  Both
-// products are two-plane fp16 splits on v_mfma_f32_32x32x16_f16 (fp32-class; gemm_t.hip describes the form and its exact power-of-two
+// products are two-plane fp16 splits on v_mfma_f32_32x32x16_f16 (fp32-class; fp_planes.h describes the form and its exact power-of-two
 // scales: one per weight matrix, one per x row — and here one per row of the intermediate, taken from the accumulators).  Both weights
 // (2 x 70 KB of planes) sit in LDS from the start: one staging phase, one barrier.  (The three-plane bf16 form of round 2
 // needed 104 KB per weight and staged them one after the other with two more barriers.)  `mid`
 // (h forward, dh backward) is also written out: the weight gradients of the two layers need it.
-#include "common.h"
+#include "fp_planes.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int M2_THREADS = 256, M2_WAVES = 4;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-constexpr int M2_NPL = 2;                                      // operand planes (two fp16 planes, gemm_t.hip)
-__device__ __forceinline__ void m2_split2h(const float *v, float sc, f16x8 &p1, f16x8 &p2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float t = v[j] * sc;
-        const _Float16 h1 = (_Float16)t;
-        p1[j] = h1; p2[j] = (_Float16)(t - (float)h1);
-    }
-}
-// 2^k with amax * 2^k in [256, 512) and its inverse (gemm_t.hip)
-__device__ __forceinline__ void m2_pow2_scale(float amax, float &sc, float &un) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-    const bool ok = e >= 9 && e <= 254;
-    sc = ok ? __uint_as_float((unsigned)(262 - e) << 23) : 1.0f;
-    un = ok ? __uint_as_float((unsigned)(e - 8) << 23) : 1.0f;
-}
-__device__ __forceinline__ float m2_absmax4(float m, const float4 &v) {
-    return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-}
+constexpr int M2_NPL = 2;                                      // operand planes (two fp16 planes, fp_planes.h)
 
 // Two fp16 planes of a weight as [n][k] (pitch KD + 8), staged by all threads in two steps so that the global loads of BOTH weights can
 // be in flight from the start of the kernel: m2_fetch (float4 loads into registers) and m2_park (split + 8-byte LDS stores).
@@ -59,14 +37,6 @@ __device__ __forceinline__ int m2_perm4(int k, bool perm) {
     if (!perm) return k;
     const int a = (k & 15) >> 2;
     return (k & ~15) + 8 * (a & 1) + 4 * (a >> 1);
-}
-__device__ __forceinline__ void m2_store4(__bf16 *WB, int NO, int WS, int n, int kp, const float *v4, float sc) {
-    _Float16 *WH = reinterpret_cast<_Float16 *>(WB);
-    f16x4 h1, h2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const float t = v4[e] * sc; h1[e] = (_Float16)t; h2[e] = (_Float16)(t - (float)h1[e]); }
-    *reinterpret_cast<f16x4 *>(&WH[(0 * NO + n) * WS + kp]) = h1;
-    *reinterpret_cast<f16x4 *>(&WH[(1 * NO + n) * WS + kp]) = h2;
 }
 template <int NO, int KD, bool TRANS>
 struct M2Weight {
@@ -96,7 +66,7 @@ struct M2Weight {
     __device__ __forceinline__ float absmax() const {
         float m = 0.f;
 #pragma unroll
-        for (int u = 0; u < (TRANS ? PERW * 4 : PER); ++u) m = m2_absmax4(m, v[u]);
+        for (int u = 0; u < (TRANS ? PERW * 4 : PER); ++u) m = absmax4(m, v[u]);
         return m;
     }
     __device__ __forceinline__ void park(__bf16 *__restrict__ WB, int tid, bool perm, float sc = 1.0f) const {
@@ -109,7 +79,7 @@ struct M2Weight {
                 if (q >= V4) continue;
                 const int n = (4 * q) / KD, k = 4 * q - n * KD;
                 const float v4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                m2_store4(WB, NO, WS, n, m2_perm4(k, perm), v4, sc);
+                store4_planes(WB, NO, WS, n, m2_perm4(k, perm), v4, sc);
             }
         } else {
             const int n4l = (lane & 3) | ((lane >> 4) << 2), k4l = (lane >> 2) & 3;
@@ -124,7 +94,7 @@ struct M2Weight {
                                          e == 0 ? v[4 * u + 1].x : e == 1 ? v[4 * u + 1].y : e == 2 ? v[4 * u + 1].z : v[4 * u + 1].w,
                                          e == 0 ? v[4 * u + 2].x : e == 1 ? v[4 * u + 2].y : e == 2 ? v[4 * u + 2].z : v[4 * u + 2].w,
                                          e == 0 ? v[4 * u + 3].x : e == 1 ? v[4 * u + 3].y : e == 2 ? v[4 * u + 3].z : v[4 * u + 3].w};
-                    m2_store4(WB, NO, WS, n0 + e, m2_perm4(k0, perm), v4, sc);
+                    store4_planes(WB, NO, WS, n0 + e, m2_perm4(k0, perm), v4, sc);
                 }
             }
         }
@@ -195,8 +165,8 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2(const float *__restrict__ x
 #pragma unroll
     for (int w = 1; w < M2_WAVES; ++w) { a = fmaxf(a, wred[w]); b = fmaxf(b, wred[M2_WAVES + w]); }
     float scA, scB;
-    m2_pow2_scale(a, scA, unA);
-    m2_pow2_scale(b, scB, unB);
+    pow2_scale(a, scA, unA);
+    pow2_scale(b, scB, unB);
     stA.park(WB, tid, false, scA);
     stB.park(WB2, tid, true, scB);
     for (int t = tid; t < NA + NB; t += M2_THREADS) BL[t] = BWD ? 0.f : (t < NA ? bA[t] : bB[t - NA]);
@@ -226,17 +196,17 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2(const float *__restrict__ x
     {
     float am = 0.f;
 #pragma unroll
-    for (int s = 0; s < SA; ++s) { am = m2_absmax4(am, xa[s]); am = m2_absmax4(am, xb[s]); }
+    for (int s = 0; s < SA; ++s) { am = absmax4(am, xa[s]); am = absmax4(am, xb[s]); }
     am = fmaxf(am, __shfl_xor(am, 32));                    // the other half of the row sits on lane ^ 32
     float xsc, xu;
-    m2_pow2_scale(am, xsc, xu);
+    pow2_scale(am, xsc, xu);
     un1 = xu * unA;
     const _Float16 *WH = reinterpret_cast<const _Float16 *>(WB);
 #pragma unroll
     for (int s = 0; s < SA; ++s) {
         const float xv[8] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w, xb[s].x, xb[s].y, xb[s].z, xb[s].w};
         f16x8 q1, q2;
-        m2_split2h(xv, xsc, q1, q2);
+        split2h(xv, xsc, q1, q2);
         const int colp = 16 * s + 8 * h;
 #pragma unroll
         for (int nb = 0; nb < MBA; ++nb) {
@@ -302,7 +272,7 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2(const float *__restrict__ x
         for (int r = 0; r < 16; ++r) am = fmaxf(am, fabsf(acc1[nb][r]));
     am = fmaxf(am, __shfl_xor(am, 32));
     float msc, mu;
-    m2_pow2_scale(am, msc, mu);
+    pow2_scale(am, msc, mu);
     un2 = mu * unB;
     const _Float16 *WH = reinterpret_cast<const _Float16 *>(WB2);
 #pragma unroll
@@ -312,7 +282,7 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2(const float *__restrict__ x
 #pragma unroll
         for (int j = 0; j < 8; ++j) hv[j] = acc1[mb][8 * sgrp + j];
         f16x8 q1, q2;
-        m2_split2h(hv, msc, q1, q2);
+        split2h(hv, msc, q1, q2);
         const int colp = 32 * mb + 16 * sgrp + 8 * h;
 #pragma unroll
         for (int nb = 0; nb < MBB; ++nb) {

@@ -4,15 +4,9 @@
 // (Distance(add_self_loops=True), :331-347); f_ij [E,H]; d_ij [E,3] unit vectors (0 for loops); r_ij [E] (0 for loops).
 // All kernels are HBM/L2-streaming gathers; node-side projections were hoisted out of the edge loops
 // (w_trg_proj / w_src_proj commute with the gather, :657-658), so the only edge-level GEMMs left are dk/dv/s/f_proj.
-#include "common.h"
+#include "visnet_common.h"
 
 namespace {
-
-// v * sigmoid(v) with the hardware reciprocal (1 ulp) instead of an IEEE division: the message kernels apply it per loaded element now
-__device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ float cos_cutoff(float d, float cutoff) {      // CosineCutoff, :33-46
-    return d < cutoff ? 0.5f * (cosf(__fdiv_rn(d * 3.14159265358979323846f, cutoff)) + 1.0f) : 0.0f;
-}
 
 // d_ij = (pos[src]-pos[tgt]) / |.| for src != tgt, 0 for self loops   (:340-347, :864-866; Sphere(lmax=1) is the identity)
 __global__ void k_edge_unit(const float *__restrict__ pos, const int *__restrict__ col, const int *__restrict__ tgt,
@@ -40,47 +34,9 @@ __global__ void k_expnormal(const float *__restrict__ dist, const int *__restric
     }
 }
 
-// CPL consecutive channels of one row as ONE load / store (float2 for CPL = 2: c0 is even and every row starts at a multiple of H floats from a
-// 256-byte aligned allocation; the compiler cannot prove that and would issue two dword instructions)
-template <int CPL>
-__device__ __forceinline__ void vld(const float *__restrict__ p, float (&r)[CPL]) {
-    if constexpr (CPL == 4) { const float4 t = *reinterpret_cast<const float4 *>(p); r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w; }
-    else if constexpr (CPL == 2) { const float2 t = *reinterpret_cast<const float2 *>(p); r[0] = t.x; r[1] = t.y; }
-    else {
-#pragma unroll
-        for (int u = 0; u < CPL; ++u) r[u] = p[u];
-    }
-}
-template <int CPL, bool HALF>
-__device__ __forceinline__ void vfold(float (&a)[CPL]) {      // HALF: even entries (lanes 0-31) + odd entries (lanes 32-63), fixed order
-    if constexpr (HALF) {
-#pragma unroll
-        for (int u = 0; u < CPL; ++u) a[u] += __shfl_xor(a[u], 32, 64);
-    }
-}
-template <int CPL>
-__device__ __forceinline__ void vst(float *__restrict__ p, const float (&r)[CPL]) {
-    if constexpr (CPL == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1], r[2], r[3]);
-    else if constexpr (CPL == 2) *reinterpret_cast<float2 *>(p) = make_float2(r[0], r[1]);
-    else {
-#pragma unroll
-        for (int u = 0; u < CPL; ++u) p[u] = r[u];
-    }
-}
-
-#ifndef CONAN_V_EB
-#define CONAN_V_EB 4
-#endif
-constexpr bool V_HALF = true;     // H = 128: a half-wavefront per edge (32 lanes x float4 = one 512-byte row), two edges per instruction
-constexpr int VN_EB = CONAN_V_EB;      // edges in flight per wavefront
-#ifndef CONAN_VB_RUN
-#define CONAN_VB_RUN 16
-#endif
-constexpr int VN_RUN = CONAN_VB_RUN;    // edges per wavefront in the kernels that walk runs of consecutive edges (64 left too few wavefronts in flight)
-
-// The three element-wise edge kernels below walk runs of VN_RUN consecutive edges per wavefront (round 3; were one thread per element with a
+// The three element-wise edge kernels below walk runs of V_RUN consecutive edges per wavefront (round 3; were one thread per element with a
 // 64-bit division, the index loads and — in k_ne_scale — a full-precision cosine per ELEMENT): per-edge quantities are formed once, one edge
-// per lane, and handed out; lane <-> CPL channels; VN_EB edges in flight.
+// per lane, and handed out; lane <-> CPL channels; V_EB edges in flight.
 // W[e,:] *= C(r_e) * [src != tgt]      (NeighborEmbedding, :408-415: loops removed, cosine cutoff)
 template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_ne_scale(const float *Win, float *W, const float *__restrict__ dist, const int *__restrict__ col,
@@ -90,17 +46,17 @@ __global__ void __launch_bounds__(256) k_ne_scale(const float *Win, float *W, co
     const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
     constexpr int ES = HALF ? 2 : 1;
     const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int base = wave * VN_RUN; base < E; base += nw * VN_RUN) {
-        const int cnt = min(VN_RUN, E - base);
+    for (int base = wave * V_RUN; base < E; base += nw * V_RUN) {
+        const int cnt = min(V_RUN, E - base);
         const float my_s = (lane < cnt && col[base + lane] != tgt[base + lane]) ? cos_cutoff(dist[base + lane], cutoff) : 0.0f;
         for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
             const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
-            for (int tq = 0; tq < cnt; tq += ES * VN_EB) {
-                float w[VN_EB][CPL];
+            for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                float w[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) vld<CPL>(Win + (size_t)(base + min(tq + ES * b + hf, cnt - 1)) * H + cl, w[b]);
+                for (int b = 0; b < V_EB; ++b) vld<CPL>(Win + (size_t)(base + min(tq + ES * b + hf, cnt - 1)) * H + cl, w[b]);
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const float sc = __shfl(my_s, min(tq + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                     if (tq + ES * b + hf >= cnt) continue;
 #pragma unroll
@@ -130,21 +86,21 @@ __global__ void __launch_bounds__(256) k_edge_embed(const float *__restrict__ x,
     const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
     constexpr int ES = HALF ? 2 : 1;
     const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int base = wave * VN_RUN; base < E; base += nw * VN_RUN) {
-        const int cnt = min(VN_RUN, E - base);
+    for (int base = wave * V_RUN; base < E; base += nw * V_RUN) {
+        const int cnt = min(V_RUN, E - base);
         const int my_j = lane < cnt ? col[base + lane] : 0, my_i = lane < cnt ? tgt[base + lane] : 0;
         for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
             const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
-            for (int tq = 0; tq < cnt; tq += ES * VN_EB) {
-                float xi[VN_EB][CPL], xj[VN_EB][CPL], pv[VN_EB][CPL];
+            for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                float xi[V_EB][CPL], xj[V_EB][CPL], pv[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(tq + ES * b + hf, cnt - 1);
                     const size_t j = (size_t)__shfl(my_j, tt, 64), i = (size_t)__shfl(my_i, tt, 64);
                     vld<CPL>(x + i * H + cl, xi[b]); vld<CPL>(x + j * H + cl, xj[b]); vld<CPL>(p + (size_t)(base + tt) * H + cl, pv[b]);
                 }
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     if (tq + ES * b + hf >= cnt) continue;
                     float o[CPL];
 #pragma unroll
@@ -231,10 +187,10 @@ __global__ void __launch_bounds__(256) k_attn_msg(const float *__restrict__ q, c
             const int cnt = min(64, e1 - base);
             const int my_j = lane < cnt ? col[base + lane] : 0;
             const float my_c = lane < cnt ? cos_cutoff(dist[base + lane], cutoff) : 0.f;
-            for (int t = 0; t < cnt; t += ES * VN_EB) {
-                float kj[VN_EB][CPL], vj[VN_EB][CPL], dke[VN_EB][CPL], dve[VN_EB][CPL];
+            for (int t = 0; t < cnt; t += ES * V_EB) {
+                float kj[V_EB][CPL], vj[V_EB][CPL], dke[V_EB][CPL], dve[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(t + ES * b + hf, cnt - 1);                  // slots past the row repeat its last edge (not used)
                     const int j = __shfl(my_j, tt, 64);
                     const size_t e = (size_t)(base + tt);
@@ -242,7 +198,7 @@ __global__ void __launch_bounds__(256) k_attn_msg(const float *__restrict__ q, c
                     vld<CPL>(dk + e * H + cl, dke[b]); vld<CPL>(dv + e * H + cl, dve[b]);
                 }
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const float cutb = __shfl(my_c, min(t + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                     if (t + ES * b + hf >= cnt) continue;
                     float part = 0.f;
@@ -271,7 +227,7 @@ template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_vec_aggregate(const float *__restrict__ vec, const float *__restrict__ s, const float *__restrict__ dvec,
                                                        const int *__restrict__ rowptr, const int *__restrict__ col, int n, int H, int pre,
                                                        float *__restrict__ vagg) {
-    // lane <-> CPL consecutive channels (H = 64 CPL: one pass over the row); indices and unit vectors handed out per lane, VN_EB edges in flight
+    // lane <-> CPL consecutive channels (H = 64 CPL: one pass over the row); indices and unit vectors handed out per lane, V_EB edges in flight
     const int lane = threadIdx.x & 63;
     const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
     constexpr int ES = HALF ? 2 : 1;
@@ -288,10 +244,10 @@ __global__ void __launch_bounds__(256) k_vec_aggregate(const float *__restrict__
             float my_d[3];
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) my_d[sp] = lane < cnt ? dvec[(size_t)(base + lane) * 3 + sp] : 0.f;
-            for (int t = 0; t < cnt; t += ES * VN_EB) {
-                float s1[VN_EB][CPL], s2[VN_EB][CPL], vj[VN_EB][3][CPL];
+            for (int t = 0; t < cnt; t += ES * V_EB) {
+                float s1[V_EB][CPL], s2[V_EB][CPL], vj[V_EB][3][CPL];
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(t + ES * b + hf, cnt - 1);
                     const int j = __shfl(my_j, tt, 64);
                     const size_t e = (size_t)(base + tt);
@@ -300,7 +256,7 @@ __global__ void __launch_bounds__(256) k_vec_aggregate(const float *__restrict__
                     for (int sp = 0; sp < 3; ++sp) vld<CPL>(vec + ((size_t)j * 3 + sp) * H + c0, vj[b][sp]);
                 }
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const float d0 = __shfl(my_d[0], min(t + ES * b + hf, cnt - 1), 64), d1 = __shfl(my_d[1], min(t + ES * b + hf, cnt - 1), 64), d2 = __shfl(my_d[2], min(t + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                     if (t + ES * b + hf >= cnt) continue;
 #pragma unroll
@@ -361,9 +317,9 @@ __global__ void k_node_update(const float *__restrict__ x, const float *__restri
 
 // Edge update (:655-661): w1 = rej(wt[tgt], d), w2 = rej(ws[src], -d), f' = f + SiLU(f_proj(f)) * sum_sp w1*w2
 // wt = w_trg_proj(vec), ws = w_src_proj(vec) are node-level [n,3,H]; t = SiLU(f_proj(f_ij)) [E,H]
-// One wavefront per run of VN_RUN consecutive edges (round 3; was one thread per element: a 64-bit division, two index loads and six gathered
+// One wavefront per run of V_RUN consecutive edges (round 3; was one thread per element: a 64-bit division, two index loads and six gathered
 // rows per ELEMENT, each waiting for its index): sources, targets and unit vectors of the run are fetched once, one edge per lane, and
-// handed out; lane <-> CPL channels; VN_EB edges in flight (consecutive edges share their target: its rows are L1 hits).
+// handed out; lane <-> CPL channels; V_EB edges in flight (consecutive edges share their target: its rows are L1 hits).
 template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_edge_update(const float *__restrict__ wt, const float *__restrict__ ws, const float *__restrict__ t,
                                                      const float *__restrict__ dvec, const int *__restrict__ col, const int *__restrict__ tgt,
@@ -374,18 +330,18 @@ __global__ void __launch_bounds__(256) k_edge_update(const float *__restrict__ w
     const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
     constexpr int ES = HALF ? 2 : 1;
     const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int base = wave * VN_RUN; base < E; base += nw * VN_RUN) {
-        const int cnt = min(VN_RUN, E - base);
+    for (int base = wave * V_RUN; base < E; base += nw * V_RUN) {
+        const int cnt = min(V_RUN, E - base);
         const int my_j = lane < cnt ? col[base + lane] : 0, my_i = lane < cnt ? tgt[base + lane] : 0;
         float my_d[3];
 #pragma unroll
         for (int sp = 0; sp < 3; ++sp) my_d[sp] = lane < cnt ? dvec[(size_t)(base + lane) * 3 + sp] : 0.f;
         for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
             const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
-            for (int tq = 0; tq < cnt; tq += ES * VN_EB) {
-                float aa[VN_EB][3][CPL], bb[VN_EB][3][CPL], tv[VN_EB][CPL], fv[VN_EB][CPL];
+            for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                float aa[V_EB][3][CPL], bb[V_EB][3][CPL], tv[V_EB][CPL], fv[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(tq + ES * b + hf, cnt - 1);
                     const size_t j = (size_t)__shfl(my_j, tt, 64), i = (size_t)__shfl(my_i, tt, 64), e = (size_t)(base + tt);
 #pragma unroll
@@ -393,7 +349,7 @@ __global__ void __launch_bounds__(256) k_edge_update(const float *__restrict__ w
                     vld<CPL>(t + e * H + cl, tv[b]); vld<CPL>(f + e * H + cl, fv[b]);
                 }
 #pragma unroll
-                for (int b = 0; b < VN_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const float d0 = __shfl(my_d[0], min(tq + ES * b + hf, cnt - 1), 64), d1 = __shfl(my_d[1], min(tq + ES * b + hf, cnt - 1), 64), d2 = __shfl(my_d[2], min(tq + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                     if (tq + ES * b + hf >= cnt) continue;
                     const size_t e = (size_t)(base + tq + ES * b + hf);
@@ -444,31 +400,28 @@ __global__ void k_prior(const float *__restrict__ x, const int64_t *__restrict__
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < tot; t += stride) out[t] = x[t] * sd + atomref[z[t / O]];
 }
 
-inline int nblk(long long n) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
-
 }  // namespace
 
-#define VN_CHECK(cond) if (!(cond)) return CONAN_E_BADARG
 extern "C" {
 
 int conan_visnet_edge_unit(const float *pos, const int *col, const int *tgt, const int *num_edges_dev, int max_edges, float *dvec, void *stream) {
-    VN_CHECK(pos && col && tgt && num_edges_dev && dvec && max_edges >= 0);
+    V_CHECK(pos && col && tgt && num_edges_dev && dvec && max_edges >= 0);
     k_edge_unit<<<nblk(max_edges), 256, 0, as_stream(stream)>>>(pos, col, tgt, num_edges_dev, max_edges, dvec);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_expnormal(const float *dist, const int *num_edges_dev, int max_edges, const float *means, const float *betas, int num_rbf,
                            float alpha, float cutoff, float *out, void *stream) {
-    VN_CHECK(dist && num_edges_dev && means && betas && out && num_rbf > 0);
+    V_CHECK(dist && num_edges_dev && means && betas && out && num_rbf > 0);
     k_expnormal<<<nblk((long long)max_edges * num_rbf), 256, 0, as_stream(stream)>>>(dist, num_edges_dev, max_edges, means, betas, num_rbf, alpha, cutoff, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_neighbor_scale_to(const float *W, const float *dist, const int *col, const int *tgt, const int *num_edges_dev, int max_edges, int H,
                                    float cutoff, float *out, void *stream) {
-    VN_CHECK(W && out && dist && col && tgt && num_edges_dev && H > 0);
+    V_CHECK(W && out && dist && col && tgt && num_edges_dev && H > 0);
     if (max_edges <= 0) return CONAN_OK;
-    if (H == 128 && V_HALF) k_ne_scale<4, true><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
-    else if (H % 128 == 0) k_ne_scale<2><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
-    else k_ne_scale<1><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
+    if (H == 128 && V_HALF) k_ne_scale<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
+    else if (H % 128 == 0) k_ne_scale<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
+    else k_ne_scale<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_neighbor_scale(float *W, const float *dist, const int *col, const int *tgt, const int *num_edges_dev, int max_edges, int H,
@@ -476,20 +429,20 @@ int conan_visnet_neighbor_scale(float *W, const float *dist, const int *col, con
     return conan_visnet_neighbor_scale_to(W, dist, col, tgt, num_edges_dev, max_edges, H, cutoff, W, stream);
 }
 int conan_concat2(const float *a, int Ha, const float *b, int Hb, long long rows, float *out, void *stream) {
-    VN_CHECK(a && b && out && Ha > 0 && Hb > 0 && rows >= 0);
+    V_CHECK(a && b && out && Ha > 0 && Hb > 0 && rows >= 0);
     k_concat2<<<nblk(rows * (Ha + Hb)), 256, 0, as_stream(stream)>>>(a, Ha, b, Hb, rows, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_edge_embed(const float *x, const float *p, const int *col, const int *tgt, const int *num_edges_dev, int max_edges, int H,
                             float *f, void *stream) {
-    VN_CHECK(x && p && col && tgt && num_edges_dev && f && H > 0);
-    if (H == 128 && V_HALF) k_edge_embed<4, true><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
-    else if (H % 128 == 0) k_edge_embed<2><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
-    else k_edge_embed<1><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
+    V_CHECK(x && p && col && tgt && num_edges_dev && f && H > 0);
+    if (H == 128 && V_HALF) k_edge_embed<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
+    else if (H % 128 == 0) k_edge_embed<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
+    else k_edge_embed<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_layernorm_fwd(const float *x, const float *gamma, const float *beta, int rows, int H, float eps, float *out, void *stream) {
-    VN_CHECK(x && gamma && beta && out && rows >= 0 && H > 0);
+    V_CHECK(x && gamma && beta && out && rows >= 0 && H > 0);
     if (rows == 0) return CONAN_OK;
     k_layernorm<<<nblk((long long)rows * 64), 256, 0, as_stream(stream)>>>(x, gamma, beta, rows, H, eps, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
@@ -504,22 +457,22 @@ static int scale_channels_launch(const float *v, const float *w, const float *ad
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_scale_channels(const float *v, const float *w, long long rows, int H, float *out, void *stream) {
-    VN_CHECK(v && w && out && rows >= 0 && H > 0);
+    V_CHECK(v && w && out && rows >= 0 && H > 0);
     return scale_channels_launch(v, w, nullptr, rows, H, out, stream);
 }
 int conan_scale_channels_add(const float *v, const float *w, const float *add, long long rows, int H, float *out, void *stream) {
-    VN_CHECK(v && w && add && out && rows >= 0 && H > 0);
+    V_CHECK(v && w && add && out && rows >= 0 && H > 0);
     return scale_channels_launch(v, w, add, rows, H, out, stream);
 }
 int conan_visnet_vecdot(const float *vp, int n, int H, float *out, void *stream) {
-    VN_CHECK(vp && out && n >= 0 && H > 0);
+    V_CHECK(vp && out && n >= 0 && H > 0);
     k_vecdot<<<nblk((long long)n * H), 256, 0, as_stream(stream)>>>(vp, n, H, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_attn_message(const float *q, const float *k, const float *v, const float *dk, const float *dv, const int *rowptr,
                               const int *col, const float *dist, float cutoff, int n, int H, int num_heads, int pre_act, float *vmsg,
                               float *xagg, void *stream) {
-    VN_CHECK(q && k && v && dk && dv && rowptr && col && dist && vmsg && xagg && n >= 0 && H > 0 && num_heads > 0 && H % num_heads == 0);
+    V_CHECK(q && k && v && dk && dv && rowptr && col && dist && vmsg && xagg && n >= 0 && H > 0 && num_heads > 0 && H % num_heads == 0);
     const int hd = H / num_heads;
     // H a multiple of 128 (the classification backbone's 512, common.py:444-446): blocks of 128 channels on blockIdx.y, each a half-wavefront
     // per edge — heads must not straddle a block (hd divides 128) and span a power-of-two number of 4-channel lanes
@@ -537,7 +490,7 @@ int conan_visnet_attn_message(const float *q, const float *k, const float *v, co
 }
 int conan_visnet_vec_aggregate(const float *vec, const float *s, const float *dvec, const int *rowptr, const int *col, int n, int H,
                                int pre_act, float *vagg, void *stream) {
-    VN_CHECK(vec && s && dvec && rowptr && col && vagg && n >= 0 && H > 0);
+    V_CHECK(vec && s && dvec && rowptr && col && vagg && n >= 0 && H > 0);
     if (n == 0) return CONAN_OK;
     if (H == 128 && V_HALF) k_vec_aggregate<4, true><<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
     else if (H == 128) k_vec_aggregate<2><<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
@@ -547,31 +500,31 @@ int conan_visnet_vec_aggregate(const float *vec, const float *s, const float *dv
 }
 int conan_visnet_node_update(const float *x, const float *vec, const float *vdot, const float *o, const float *vp, const float *vagg, int n,
                              int H, float *x_out, float *vec_out, void *stream) {
-    VN_CHECK(x && vec && vdot && o && vp && vagg && x_out && vec_out && n >= 0 && H > 0);
+    V_CHECK(x && vec && vdot && o && vp && vagg && x_out && vec_out && n >= 0 && H > 0);
     k_node_update<<<nblk((long long)n * H), 256, 0, as_stream(stream)>>>(x, vec, vdot, o, vp, vagg, n, H, x_out, vec_out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_edge_update(const float *wt, const float *ws, const float *t, const float *dvec, const int *col, const int *tgt,
                              const int *num_edges_dev, int max_edges, int H, int pre_act, const float *f, float *f_out, void *stream) {
-    VN_CHECK(wt && ws && t && dvec && col && tgt && num_edges_dev && f && f_out && H > 0);
-    if (H == 128 && V_HALF) k_edge_update<4, true><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
-    else if (H % 128 == 0) k_edge_update<2><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
-    else k_edge_update<1><<<nblk((long long)max_edges * (64 / VN_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
+    V_CHECK(wt && ws && t && dvec && col && tgt && num_edges_dev && f && f_out && H > 0);
+    if (H == 128 && V_HALF) k_edge_update<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
+    else if (H % 128 == 0) k_edge_update<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
+    else k_edge_update<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_spatial_norm(const float *v, int n, int H, float *out, void *stream) {
-    VN_CHECK(v && out && n >= 0 && H > 0);
+    V_CHECK(v && out && n >= 0 && H > 0);
     k_spatial_norm<<<nblk((long long)n * H), 256, 0, as_stream(stream)>>>(v, n, H, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_gate(const float *u, const float *v2, int n, int out_channels, int scalar_activation, float *x_out, float *v_out, void *stream) {
-    VN_CHECK(u && v2 && x_out && v_out && n >= 0 && out_channels > 0);
+    V_CHECK(u && v2 && x_out && v_out && n >= 0 && out_channels > 0);
     k_gate<<<nblk((long long)n * out_channels), 256, 0, as_stream(stream)>>>(u, v2, n, out_channels, scalar_activation, x_out, v_out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_prior(const float *x, const int64_t *z, const float *atomref, const float *std_dev, int n, int out_channels, float *out,
                        void *stream) {
-    VN_CHECK(x && z && atomref && std_dev && out && n >= 0 && out_channels > 0);
+    V_CHECK(x && z && atomref && std_dev && out && n >= 0 && out_channels > 0);
     k_prior<<<nblk((long long)n * out_channels), 256, 0, as_stream(stream)>>>(x, z, atomref, std_dev, n, out_channels, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }

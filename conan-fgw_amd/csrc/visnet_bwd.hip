@@ -2,17 +2,9 @@
 // Node-level gradients that receive contributions from many edges are accumulated WITHOUT atomics: one wavefront per
 // node walks the node's by-target CSR row (gradients flowing to the target side) or its by-source list
 // (t_rowptr / t_eid: gradients flowing to the source side) in a fixed order => bitwise reproducible.
-#include "common.h"
+#include "visnet_common.h"
 
 namespace {
-
-__device__ __forceinline__ float sigmoid_f(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }      // hardware reciprocal, 1 ulp
-__device__ __forceinline__ float silu_f(float v) { return v * sigmoid_f(v); }
-__device__ __forceinline__ float dsilu_f(float v) { const float s = sigmoid_f(v); return s * (1.0f + v * (1.0f - s)); }
-__device__ __forceinline__ float cos_cutoff(float d, float cutoff) {
-    return d < cutoff ? 0.5f * (cosf(__fdiv_rn(d * 3.14159265358979323846f, cutoff)) + 1.0f) : 0.0f;
-}
-inline int nblk(long long n) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 
 // ---------------------------------------------------------------------------------------------- SiLU
 __global__ void k_silu_fwd(const float *__restrict__ x, int rows, int width, const int *__restrict__ m_dev, float *__restrict__ y) {
@@ -45,44 +37,7 @@ __global__ void k_rowsum(const float *__restrict__ x, int rows, int width, float
 }
 
 // ---------------------------------------------------------------------------------------------- EdgeEmbedding backward
-// CPL consecutive channels of one row as ONE load / store (float2 for CPL = 2: c0 is even and every row starts at a multiple of H floats from a
-// 256-byte aligned allocation; the compiler cannot prove that and would issue two dword instructions)
-template <int CPL>
-__device__ __forceinline__ void vld(const float *__restrict__ p, float (&r)[CPL]) {
-    if constexpr (CPL == 4) { const float4 t = *reinterpret_cast<const float4 *>(p); r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w; }
-    else if constexpr (CPL == 2) { const float2 t = *reinterpret_cast<const float2 *>(p); r[0] = t.x; r[1] = t.y; }
-    else {
-#pragma unroll
-        for (int u = 0; u < CPL; ++u) r[u] = p[u];
-    }
-}
-template <int CPL, bool HALF>
-__device__ __forceinline__ void vfold(float (&a)[CPL]) {      // HALF: even entries (lanes 0-31) + odd entries (lanes 32-63), fixed order
-    if constexpr (HALF) {
-#pragma unroll
-        for (int u = 0; u < CPL; ++u) a[u] += __shfl_xor(a[u], 32, 64);
-    }
-}
-template <int CPL>
-__device__ __forceinline__ void vst(float *__restrict__ p, const float (&r)[CPL]) {
-    if constexpr (CPL == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1], r[2], r[3]);
-    else if constexpr (CPL == 2) *reinterpret_cast<float2 *>(p) = make_float2(r[0], r[1]);
-    else {
-#pragma unroll
-        for (int u = 0; u < CPL; ++u) p[u] = r[u];
-    }
-}
-
-#ifndef CONAN_V_EB
-#define CONAN_V_EB 4
-#endif
-constexpr bool V_HALF = true;     // H = 128: a half-wavefront per edge (visnet.hip)
-constexpr int VB_EB = CONAN_V_EB;
-#ifndef CONAN_VB_RUN
-#define CONAN_VB_RUN 16
-#endif
-constexpr int VB_RUN = CONAN_VB_RUN;     // edges per wavefront in the kernels that walk runs of consecutive edges
-// dp[e] = (x_i + x_j) * df[e]      (runs of VB_RUN consecutive edges per wavefront, as k_edge_embed)
+// dp[e] = (x_i + x_j) * df[e]      (runs of V_RUN consecutive edges per wavefront, as k_edge_embed)
 template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_edge_embed_bwd_p(const float *__restrict__ x, const float *__restrict__ df, const int *__restrict__ col,
                                                           const int *__restrict__ tgt, const int *__restrict__ ne_dev, int max_edges, int H,
@@ -92,21 +47,21 @@ __global__ void __launch_bounds__(256) k_edge_embed_bwd_p(const float *__restric
     const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
     constexpr int ES = HALF ? 2 : 1;
     const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int base = wave * VB_RUN; base < E; base += nw * VB_RUN) {
-        const int cnt = min(VB_RUN, E - base);
+    for (int base = wave * V_RUN; base < E; base += nw * V_RUN) {
+        const int cnt = min(V_RUN, E - base);
         const int my_j = lane < cnt ? col[base + lane] : 0, my_i = lane < cnt ? tgt[base + lane] : 0;
         for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
             const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
-            for (int tq = 0; tq < cnt; tq += ES * VB_EB) {
-                float xi[VB_EB][CPL], xj[VB_EB][CPL], gv[VB_EB][CPL];
+            for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                float xi[V_EB][CPL], xj[V_EB][CPL], gv[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(tq + ES * b + hf, cnt - 1);
                     const size_t j = (size_t)__shfl(my_j, tt, 64), i = (size_t)__shfl(my_i, tt, 64);
                     vld<CPL>(x + i * H + cl, xi[b]); vld<CPL>(x + j * H + cl, xj[b]); vld<CPL>(df + (size_t)(base + tt) * H + cl, gv[b]);
                 }
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     if (tq + ES * b + hf >= cnt) continue;
                     float o[CPL];
 #pragma unroll
@@ -133,12 +88,12 @@ __global__ void __launch_bounds__(256) k_edge_embed_bwd_x(const float *__restric
 #pragma unroll
             for (int u = 0; u < CPL; ++u) a[u] = 0.f;
             const int e0 = rowptr[i], e1 = rowptr[i + 1];
-            for (int e = e0; e < e1; e += ES * VB_EB) {                             // the row itself: consecutive edges, no indices
-                float g[VB_EB][CPL], q[VB_EB][CPL];
+            for (int e = e0; e < e1; e += ES * V_EB) {                             // the row itself: consecutive edges, no indices
+                float g[V_EB][CPL], q[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) { const size_t ee = (size_t)min(e + ES * b + hf, e1 - 1); vld<CPL>(df + ee * H + cl, g[b]); vld<CPL>(p + ee * H + cl, q[b]); }
+                for (int b = 0; b < V_EB; ++b) { const size_t ee = (size_t)min(e + ES * b + hf, e1 - 1); vld<CPL>(df + ee * H + cl, g[b]); vld<CPL>(p + ee * H + cl, q[b]); }
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     if (e + ES * b + hf >= e1) continue;
 #pragma unroll
                     for (int u = 0; u < CPL; ++u) a[u] += g[b][u] * q[b][u];
@@ -148,15 +103,15 @@ __global__ void __launch_bounds__(256) k_edge_embed_bwd_x(const float *__restric
             for (int base = s0; base < s1; base += 64) {                            // the by-source list: edge ids handed out per lane
                 const int cnt = min(64, s1 - base);
                 const int my_e = lane < cnt ? t_eid[base + lane] : 0;
-                for (int tq = 0; tq < cnt; tq += ES * VB_EB) {
-                    float g[VB_EB][CPL], q[VB_EB][CPL];
+                for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                    float g[V_EB][CPL], q[V_EB][CPL];
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         const size_t ee = (size_t)__shfl(my_e, min(tq + ES * b + hf, cnt - 1), 64);
                         vld<CPL>(df + ee * H + cl, g[b]); vld<CPL>(p + ee * H + cl, q[b]);
                     }
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         if (tq + ES * b + hf >= cnt) continue;
 #pragma unroll
                         for (int u = 0; u < CPL; ++u) a[u] += g[b][u] * q[b][u];
@@ -256,7 +211,7 @@ __device__ __forceinline__ void attn_edge(const float *qi, const float *kj, cons
 }
 
 // Round 3 (all row-walking kernels below): a row's indices (and what hangs off them per edge: target, cutoff, unit vector) are fetched once,
-// one edge per lane, and handed out with cross-lane reads; the rows of VB_EB edges are requested before the first is used.  The loops were
+// one edge per lane, and handed out with cross-lane reads; the rows of V_EB edges are requested before the first is used.  The loops were
 // chains of two or three dependent round trips per edge (2.3-3 TB/s); the sums still run in list order (bitwise-equal results).
 
 // target side: dq[i] (sum over row i), and the edge gradients d dk[e], d dv[e]
@@ -282,10 +237,10 @@ __global__ void __launch_bounds__(256) k_attn_bwd_target(const float *__restrict
             const int cnt = min(64, e1 - base);
             const int my_j = lane < cnt ? col[base + lane] : 0;
             const float my_c = lane < cnt ? cos_cutoff(dist[base + lane], cutoff) : 0.f;
-            for (int t = 0; t < cnt; t += ES * VB_EB) {
-                float kj[VB_EB][CPL], vj[VB_EB][CPL], dke[VB_EB][CPL], dve[VB_EB][CPL], dm[VB_EB][CPL];
+            for (int t = 0; t < cnt; t += ES * V_EB) {
+                float kj[V_EB][CPL], vj[V_EB][CPL], dke[V_EB][CPL], dve[V_EB][CPL], dm[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(t + ES * b + hf, cnt - 1);
                     const int j = __shfl(my_j, tt, 64);
                     const size_t e = (size_t)(base + tt);
@@ -293,7 +248,7 @@ __global__ void __launch_bounds__(256) k_attn_bwd_target(const float *__restrict
                     vld<CPL>(dk + e * H + cl, dke[b]); vld<CPL>(dv + e * H + cl, dve[b]); vld<CPL>(dvmsg + e * H + cl, dm[b]);
                 }
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const float cutb = __shfl(my_c, min(t + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                     if (t + ES * b + hf >= cnt) continue;
                     const size_t e = (size_t)(base + t + ES * b + hf);
@@ -345,17 +300,17 @@ __global__ void __launch_bounds__(256) k_attn_bwd_source(const float *__restrict
             const int my_e = lane < cnt ? t_eid[base + lane] : 0;
             const int my_i = lane < cnt ? tgt[my_e] : 0;
             const float my_c = lane < cnt ? cos_cutoff(dist[my_e], cutoff) : 0.f;
-            for (int t = 0; t < cnt; t += ES * VB_EB) {
-                float qi[VB_EB][CPL], dke[VB_EB][CPL], dve[VB_EB][CPL], dm[VB_EB][CPL], gx[VB_EB][CPL];
+            for (int t = 0; t < cnt; t += ES * V_EB) {
+                float qi[V_EB][CPL], dke[V_EB][CPL], dve[V_EB][CPL], dm[V_EB][CPL], gx[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(t + ES * b + hf, cnt - 1);
                     const size_t e = (size_t)__shfl(my_e, tt, 64), i = (size_t)__shfl(my_i, tt, 64);
                     vld<CPL>(q + i * H + cl, qi[b]); vld<CPL>(dxagg + i * H + cl, gx[b]);
                     vld<CPL>(dk + e * H + cl, dke[b]); vld<CPL>(dv + e * H + cl, dve[b]); vld<CPL>(dvmsg + e * H + cl, dm[b]);
                 }
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const float cutb = __shfl(my_c, min(t + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                     if (t + ES * b + hf >= cnt) continue;
 #pragma unroll
@@ -382,24 +337,24 @@ template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_vec_aggregate_bwd_s(const float *__restrict__ vec, const float *__restrict__ dvagg, const float *__restrict__ dvec3,
                                                              const int *__restrict__ col, const int *__restrict__ tgt, const int *__restrict__ ne_dev,
                                                              int max_edges, int H, const float *__restrict__ s_pre, float *__restrict__ ds) {
-    // one wavefront per run of VB_RUN consecutive edges, indices and unit vectors handed out per lane, VB_EB edges in flight (see k_edge_update)
+    // one wavefront per run of V_RUN consecutive edges, indices and unit vectors handed out per lane, V_EB edges in flight (see k_edge_update)
     const int E = min(*ne_dev, max_edges);
     const int lane = threadIdx.x & 63;
     const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
     constexpr int ES = HALF ? 2 : 1;
     const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int base = wave * VB_RUN; base < E; base += nw * VB_RUN) {
-        const int cnt = min(VB_RUN, E - base);
+    for (int base = wave * V_RUN; base < E; base += nw * V_RUN) {
+        const int cnt = min(V_RUN, E - base);
         const int my_j = lane < cnt ? col[base + lane] : 0, my_i = lane < cnt ? tgt[base + lane] : 0;
         float my_d[3];
 #pragma unroll
         for (int sp = 0; sp < 3; ++sp) my_d[sp] = lane < cnt ? dvec3[(size_t)(base + lane) * 3 + sp] : 0.f;
         for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
             const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
-            for (int tq = 0; tq < cnt; tq += ES * VB_EB) {
-                float g[VB_EB][3][CPL], vj[VB_EB][3][CPL], p1[VB_EB][CPL], p2[VB_EB][CPL];
+            for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                float g[V_EB][3][CPL], vj[V_EB][3][CPL], p1[V_EB][CPL], p2[V_EB][CPL];
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const int tt = min(tq + ES * b + hf, cnt - 1);
                     const size_t j = (size_t)__shfl(my_j, tt, 64), i = (size_t)__shfl(my_i, tt, 64), e = (size_t)(base + tt);
 #pragma unroll
@@ -411,7 +366,7 @@ __global__ void __launch_bounds__(256) k_vec_aggregate_bwd_s(const float *__rest
                     }
                 }
 #pragma unroll
-                for (int b = 0; b < VB_EB; ++b) {
+                for (int b = 0; b < V_EB; ++b) {
                     const float d0 = __shfl(my_d[0], min(tq + ES * b + hf, cnt - 1), 64), d1 = __shfl(my_d[1], min(tq + ES * b + hf, cnt - 1), 64), d2 = __shfl(my_d[2], min(tq + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                     if (tq + ES * b + hf >= cnt) continue;
                     const size_t e = (size_t)(base + tq + ES * b + hf);
@@ -449,10 +404,10 @@ __global__ void __launch_bounds__(256) k_vec_aggregate_bwd_v(const float *__rest
                 const int cnt = min(64, q1 - base);
                 const int my_e = lane < cnt ? t_eid[base + lane] : 0;
                 const int my_i = lane < cnt ? tgt[my_e] : 0;
-                for (int t = 0; t < cnt; t += ES * VB_EB) {
-                    float s1[VB_EB][CPL], g[VB_EB][3][CPL];
+                for (int t = 0; t < cnt; t += ES * V_EB) {
+                    float s1[V_EB][CPL], g[V_EB][3][CPL];
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         const int tt = min(t + ES * b + hf, cnt - 1);
                         const size_t e = (size_t)__shfl(my_e, tt, 64), i = (size_t)__shfl(my_i, tt, 64);
                         vld<CPL>(s + e * 2 * H + cl, s1[b]);
@@ -460,7 +415,7 @@ __global__ void __launch_bounds__(256) k_vec_aggregate_bwd_v(const float *__rest
                         for (int sp = 0; sp < 3; ++sp) vld<CPL>(dvagg + (i * 3 + sp) * H + cl, g[b][sp]);
                     }
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         if (t + ES * b + hf >= cnt) continue;
 #pragma unroll
                         for (int u = 0; u < CPL; ++u) {
@@ -531,10 +486,10 @@ __global__ void __launch_bounds__(256) k_edge_update_bwd_t(const float *__restri
                 float my_d[3];
 #pragma unroll
                 for (int sp = 0; sp < 3; ++sp) my_d[sp] = lane < cnt ? dvec3[(size_t)(base + lane) * 3 + sp] : 0.f;
-                for (int tq = 0; tq < cnt; tq += ES * VB_EB) {
-                    float bb[VB_EB][3][CPL], gf[VB_EB][CPL], tr[VB_EB][CPL];
+                for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                    float bb[V_EB][3][CPL], gf[V_EB][CPL], tr[V_EB][CPL];
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         const int tt = min(tq + ES * b + hf, cnt - 1);
                         const size_t j = (size_t)__shfl(my_j, tt, 64), e = (size_t)(base + tt);
 #pragma unroll
@@ -542,7 +497,7 @@ __global__ void __launch_bounds__(256) k_edge_update_bwd_t(const float *__restri
                         vld<CPL>(dfo + e * H + cl, gf[b]); vld<CPL>(t + e * H + cl, tr[b]);
                     }
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         const float d0 = __shfl(my_d[0], min(tq + ES * b + hf, cnt - 1), 64), d1 = __shfl(my_d[1], min(tq + ES * b + hf, cnt - 1), 64), d2 = __shfl(my_d[2], min(tq + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                         if (tq + ES * b + hf >= cnt) continue;
                         const size_t e = (size_t)(base + tq + ES * b + hf);
@@ -591,10 +546,10 @@ __global__ void __launch_bounds__(256) k_edge_update_bwd_s(const float *__restri
                 float my_d[3];
 #pragma unroll
                 for (int sp = 0; sp < 3; ++sp) my_d[sp] = lane < cnt ? dvec3[(size_t)my_e * 3 + sp] : 0.f;
-                for (int tq = 0; tq < cnt; tq += ES * VB_EB) {
-                    float aa[VB_EB][3][CPL], gf[VB_EB][CPL], tr[VB_EB][CPL];
+                for (int tq = 0; tq < cnt; tq += ES * V_EB) {
+                    float aa[V_EB][3][CPL], gf[V_EB][CPL], tr[V_EB][CPL];
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         const int tt = min(tq + ES * b + hf, cnt - 1);
                         const size_t e = (size_t)__shfl(my_e, tt, 64), i = (size_t)__shfl(my_i, tt, 64);
 #pragma unroll
@@ -602,7 +557,7 @@ __global__ void __launch_bounds__(256) k_edge_update_bwd_s(const float *__restri
                         vld<CPL>(dfo + e * H + cl, gf[b]); vld<CPL>(t + e * H + cl, tr[b]);
                     }
 #pragma unroll
-                    for (int b = 0; b < VB_EB; ++b) {
+                    for (int b = 0; b < V_EB; ++b) {
                         const float d0 = __shfl(my_d[0], min(tq + ES * b + hf, cnt - 1), 64), d1 = __shfl(my_d[1], min(tq + ES * b + hf, cnt - 1), 64), d2 = __shfl(my_d[2], min(tq + ES * b + hf, cnt - 1), 64);      // before the halves diverge
                         if (tq + ES * b + hf >= cnt) continue;
 #pragma unroll
@@ -661,46 +616,45 @@ __global__ void k_scale_scalar(const float *__restrict__ x, const float *__restr
 
 }  // namespace
 
-#define VB_CHECK(cond) if (!(cond)) return CONAN_E_BADARG
 extern "C" {
 
 int conan_silu_fwd(const float *x, int rows, int width, const int *m_dev, float *y, void *stream) {
-    VB_CHECK(x && y && rows >= 0 && width > 0);
+    V_CHECK(x && y && rows >= 0 && width > 0);
     k_silu_fwd<<<nblk((long long)rows * width), 256, 0, as_stream(stream)>>>(x, rows, width, m_dev, y);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_silu_bwd(const float *x, const float *dy, int rows, int width, const int *m_dev, float *dx, void *stream) {
-    VB_CHECK(x && dy && dx && rows >= 0 && width > 0);
+    V_CHECK(x && dy && dx && rows >= 0 && width > 0);
     k_silu_bwd<<<nblk((long long)rows * width), 256, 0, as_stream(stream)>>>(x, dy, rows, width, m_dev, dx);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_split2(const float *in, int Ha, int Hb, long long rows, float *a, float *b, void *stream) {
-    VB_CHECK(in && a && b && Ha > 0 && Hb > 0 && rows >= 0);
+    V_CHECK(in && a && b && Ha > 0 && Hb > 0 && rows >= 0);
     k_split2<<<nblk(rows * (Ha + Hb)), 256, 0, as_stream(stream)>>>(in, Ha, Hb, rows, a, b);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_rowsum(const float *x, int rows, int width, float *out, void *stream) {
-    VB_CHECK(x && out && rows >= 0 && width > 0);
+    V_CHECK(x && out && rows >= 0 && width > 0);
     k_rowsum<<<nblk(rows), 256, 0, as_stream(stream)>>>(x, rows, width, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_scale_scalar(const float *x, const float *scale_dev, long long count, float *out, void *stream) {
-    VB_CHECK(x && scale_dev && out && count >= 0);
+    V_CHECK(x && scale_dev && out && count >= 0);
     k_scale_scalar<<<nblk(count), 256, 0, as_stream(stream)>>>(x, scale_dev, count, out);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_edge_embed_bwd(const float *x, const float *p, const float *df, const int *rowptr, const int *col, const int *tgt,
                                 const int *t_rowptr, const int *t_eid, const int *num_edges_dev, int max_edges, int n, int H, float *dp,
                                 float *dx, void *stream) {
-    VB_CHECK(x && p && df && rowptr && col && tgt && t_rowptr && t_eid && num_edges_dev && dp && dx && H > 0);
+    V_CHECK(x && p && df && rowptr && col && tgt && t_rowptr && t_eid && num_edges_dev && dp && dx && H > 0);
     hipStream_t s = as_stream(stream);
     if (H % 128 == 0) {
-        if (H == 128 && V_HALF) k_edge_embed_bwd_p<4, true><<<nblk((long long)max_edges * (64 / VB_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
-        else k_edge_embed_bwd_p<2><<<nblk((long long)max_edges * (64 / VB_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
+        if (H == 128 && V_HALF) k_edge_embed_bwd_p<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
+        else k_edge_embed_bwd_p<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
         if (H == 128 && V_HALF) k_edge_embed_bwd_x<4, true><<<nblk((long long)n * 64), 256, 0, s>>>(p, df, rowptr, t_rowptr, t_eid, n, H, dx);
         else k_edge_embed_bwd_x<2><<<nblk((long long)n * 64), 256, 0, s>>>(p, df, rowptr, t_rowptr, t_eid, n, H, dx);
     } else {
-        k_edge_embed_bwd_p<1><<<nblk((long long)max_edges * (64 / VB_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
+        k_edge_embed_bwd_p<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
         k_edge_embed_bwd_x<1><<<nblk((long long)n * 64), 256, 0, s>>>(p, df, rowptr, t_rowptr, t_eid, n, H, dx);
     }
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
@@ -710,12 +664,12 @@ static int layernorm_bwd_launch(const float *x, const float *gamma, const float 
                                 float *dbeta, float *ws, void *stream);
 int conan_layernorm_bwd(const float *x, const float *gamma, const float *dy, int rows, int H, float eps, float *dx, float *dgamma,
                         float *dbeta, float *ws, void *stream) {
-    VB_CHECK(x && gamma && dy && dx && dgamma && dbeta && ws && rows >= 0 && H > 0);
+    V_CHECK(x && gamma && dy && dx && dgamma && dbeta && ws && rows >= 0 && H > 0);
     return layernorm_bwd_launch(x, gamma, dy, nullptr, rows, H, eps, dx, dgamma, dbeta, ws, stream);
 }
 int conan_layernorm_bwd_res(const float *x, const float *gamma, const float *dy, const float *dres, int rows, int H, float eps, float *dx, float *dgamma,
                             float *dbeta, float *ws, void *stream) {
-    VB_CHECK(x && gamma && dy && dres && dx && dgamma && dbeta && ws && rows >= 0 && H > 0);
+    V_CHECK(x && gamma && dy && dres && dx && dgamma && dbeta && ws && rows >= 0 && H > 0);
     return layernorm_bwd_launch(x, gamma, dy, dres, rows, H, eps, dx, dgamma, dbeta, ws, stream);
 }
 static int layernorm_bwd_launch(const float *x, const float *gamma, const float *dy, const float *dres, int rows, int H, float eps, float *dx, float *dgamma,
@@ -731,7 +685,7 @@ static int layernorm_bwd_launch(const float *x, const float *gamma, const float 
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_vecdot_bwd(const float *vp, const float *dout, int n, int H, float *dvp, void *stream) {
-    VB_CHECK(vp && dout && dvp && n >= 0 && H > 0);
+    V_CHECK(vp && dout && dvp && n >= 0 && H > 0);
     k_vecdot_bwd<<<nblk((long long)n * 3 * H), 256, 0, as_stream(stream)>>>(vp, dout, n, H, dvp);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
@@ -739,8 +693,8 @@ int conan_visnet_attn_message_bwd(const float *q, const float *k, const float *v
                                   const float *dxagg, const int *rowptr, const int *col, const int *tgt, const int *t_rowptr,
                                   const int *t_eid, const float *dist, float cutoff, int n, int H, int num_heads, int pre_act, float *dq,
                                   float *dkn, float *dvn, float *ddk, float *ddv, void *stream) {
-    VB_CHECK(q && k && v && dk && dv && dvmsg && dxagg && rowptr && col && tgt && t_rowptr && t_eid && dist && dq && dkn && dvn && ddk && ddv);
-    VB_CHECK(n >= 0 && H > 0 && num_heads > 0 && H % num_heads == 0);
+    V_CHECK(q && k && v && dk && dv && dvmsg && dxagg && rowptr && col && tgt && t_rowptr && t_eid && dist && dq && dkn && dvn && ddk && ddv);
+    V_CHECK(n >= 0 && H > 0 && num_heads > 0 && H % num_heads == 0);
     const int hd = H / num_heads, cpl = H > 64 ? (H + 63) / 64 : 1;
     const bool blocks128 = H % 128 == 0 && V_HALF && hd % 4 == 0 && (((hd / 4) & (hd / 4 - 1)) == 0) && 128 % hd == 0;      // as conan_visnet_attn_message
     if (!blocks128 && (H > 128 || (H > 64 && H != 128) || hd % cpl != 0)) return CONAN_E_UNSUPPORTED;
@@ -765,11 +719,11 @@ int conan_visnet_attn_message_bwd(const float *q, const float *k, const float *v
 int conan_visnet_vec_aggregate_bwd(const float *vec, const float *s, const float *dvec3, const float *dvagg, const int *col, const int *tgt,
                                    const int *t_rowptr, const int *t_eid, const int *num_edges_dev, int max_edges, int n, int H, int pre_act,
                                    float *ds, float *dvec, void *stream) {
-    VB_CHECK(vec && s && dvec3 && dvagg && col && tgt && t_rowptr && t_eid && num_edges_dev && ds && dvec && H > 0);
+    V_CHECK(vec && s && dvec3 && dvagg && col && tgt && t_rowptr && t_eid && num_edges_dev && ds && dvec && H > 0);
     hipStream_t st = as_stream(stream);
-    if (H == 128 && V_HALF) k_vec_aggregate_bwd_s<4, true><<<nblk((long long)max_edges * (64 / VB_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
-    else if (H % 128 == 0) k_vec_aggregate_bwd_s<2><<<nblk((long long)max_edges * (64 / VB_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
-    else k_vec_aggregate_bwd_s<1><<<nblk((long long)max_edges * (64 / VB_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
+    if (H == 128 && V_HALF) k_vec_aggregate_bwd_s<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
+    else if (H % 128 == 0) k_vec_aggregate_bwd_s<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
+    else k_vec_aggregate_bwd_s<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
     if (n > 0) {
         if (H == 128 && V_HALF) k_vec_aggregate_bwd_v<4, true><<<nblk((long long)n * 64), 256, 0, st>>>(s, dvagg, t_rowptr, t_eid, tgt, n, H, pre_act, dvec);
         else if (H % 128 == 0) k_vec_aggregate_bwd_v<2><<<nblk((long long)n * 64), 256, 0, st>>>(s, dvagg, t_rowptr, t_eid, tgt, n, H, pre_act, dvec);
@@ -779,14 +733,14 @@ int conan_visnet_vec_aggregate_bwd(const float *vec, const float *s, const float
 }
 int conan_visnet_node_update_bwd(const float *dxo, const float *dveco, const float *vdot, const float *o, const float *vp, int n, int H,
                                  float *dvdot, float *dout_o, float *dvp, void *stream) {
-    VB_CHECK(dxo && dveco && vdot && o && vp && dout_o && dvp && n >= 0 && H > 0);
+    V_CHECK(dxo && dveco && vdot && o && vp && dout_o && dvp && n >= 0 && H > 0);
     k_node_update_bwd<<<nblk((long long)n * H), 256, 0, as_stream(stream)>>>(dxo, dveco, vdot, o, vp, n, H, dvdot, dout_o, dvp);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_edge_update_bwd(const float *wt, const float *ws, const float *t, const float *dvec3, const float *dfo, const int *rowptr,
                                  const int *col, const int *tgt, const int *t_rowptr, const int *t_eid, int n, int H, int pre_act, float *dwt,
                                  float *dws, float *dt, void *stream) {
-    VB_CHECK(wt && ws && t && dvec3 && dfo && rowptr && col && tgt && t_rowptr && t_eid && dwt && dws && dt && n >= 0 && H > 0);
+    V_CHECK(wt && ws && t && dvec3 && dfo && rowptr && col && tgt && t_rowptr && t_eid && dwt && dws && dt && n >= 0 && H > 0);
     if (n == 0) return CONAN_OK;
     hipStream_t s = as_stream(stream);
     if (H % 128 == 0) {
@@ -801,13 +755,13 @@ int conan_visnet_edge_update_bwd(const float *wt, const float *ws, const float *
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_spatial_norm_bwd(const float *v, const float *dout, int n, int H, float *dv, void *stream) {
-    VB_CHECK(v && dout && dv && n >= 0 && H > 0);
+    V_CHECK(v && dout && dv && n >= 0 && H > 0);
     k_spatial_norm_bwd<<<nblk((long long)n * H), 256, 0, as_stream(stream)>>>(v, dout, n, H, dv);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_gate_bwd(const float *u, const float *v2, const float *dxo, const float *dvo, int n, int out_channels, int scalar_activation,
                           float *du, float *dv2, void *stream) {
-    VB_CHECK(u && v2 && dxo && dvo && du && dv2 && n >= 0 && out_channels > 0);
+    V_CHECK(u && v2 && dxo && dvo && du && dv2 && n >= 0 && out_channels > 0);
     k_gate_bwd<<<nblk((long long)n * out_channels), 256, 0, as_stream(stream)>>>(u, v2, dxo, dvo, n, out_channels, scalar_activation, du, dv2);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }

@@ -189,6 +189,56 @@ def test_fused_filter_matches_oracle_fwd_bwd(F_, Gs, wmag):
     assert rel(W[:E].detach().cpu(), W2[:E].cpu()) < 1e-6
 
 
+@pytest.mark.parametrize("F_,tracked,fused", [(128, True, True), (128, True, False), (128, False, True), (32, False, True)],
+                         ids=["F128_one_pass", "F128_two_kernels", "F128_untracked", "F32"])
+def test_filter_network_with_weights_below_the_plane_scale_domain(F_, tracked, fused, monkeypatch):
+    """Both weight matrices of the filter network times 1e-37: their largest magnitude (~4e-38) lies below 2^-118, outside the domain of
+    pow2_scale (fp_planes.h), which then returns scale 1 in EVERY kernel that forms planes of them — the fused generator, the generic Linear
+    of the composed path, and the backward kernels (F = 128 with max |g| on the gradient: k_filter_bwd2 in one pass, or k_filter_bwd + the
+    scaled weight gradient; without it and at F = 32 the scale-free bf16 / fp32 kernels).  The output must be finite, equal to the composed
+    path's to the file's 1e-6 and to the fp64 formula to TOL, and every gradient finite, the second layer's within 1e-5 of fp64.  The first
+    layer's gradients are only required to be finite: at plane scale 1 such weights flush to zero in fp16, so dh1 = (g w2) ssp'(h1) is formed
+    from zero planes where the planes are fp16 (its true size, ~1e-37, is below every other term by 30 orders of magnitude either way)."""
+    Gs = 50
+    assert ops.filter_fused_supported(Gs, F_)
+    monkeypatch.setattr(ops, "FUSED_FILTER_BACKWARD", fused)
+    b = make_batch("esol", 2, 2)
+    g = _edges(b)
+    E = g.num_edges
+    torch.manual_seed(F_ + Gs)
+    gs = ps.GaussianSmearing(0.0, 10.0, Gs)
+    mlp = torch.nn.Sequential(torch.nn.Linear(Gs, F_), ps.ShiftedSoftplus(), torch.nn.Linear(F_, F_))
+    with torch.no_grad():
+        for p in mlp.parameters():
+            p.add_(0.1 * torch.randn_like(p))
+        mlp[0].weight.mul_(1e-37); mlp[2].weight.mul_(1e-37)
+    assert all(0.0 < float(mlp[q].weight.detach().abs().max()) < 2.0 ** -118 for q in (0, 2))
+    prm = [p.detach().to(dev).requires_grad_(True) for p in (mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias)]
+    W = ops.filter_generate(g, gs.offset.to(dev), gs.coeff, *prm, use_pairs=False)
+    assert bool(torch.isfinite(W[:E]).all())
+    rbf = ops.rbf_expand(g, gs.offset.to(dev), gs.coeff)
+    h1 = ops.linear(rbf, prm[0].detach(), prm[1].detach(), act=True, m_dev=g.num_edges_dev)
+    W2 = ops.cutoff_scale(ops.linear(h1, prm[2].detach(), prm[3].detach(), m_dev=g.num_edges_dev), g)
+    assert rel(W[:E].detach().cpu(), W2[:E].cpu()) < 1e-6
+    d = g.edge_weight().cpu().double()
+    m64 = mlp.double()
+    C = 0.5 * (torch.cos(d * math.pi / 10.0) + 1.0)
+    ref = m64(gs(d)) * C[:, None]
+    assert rel(W[:E].detach().cpu(), ref.detach()) < TOL
+    gy = torch.randn(E, F_)
+    gfull = torch.zeros(g.max_edges, F_); gfull[:E] = gy * C[:, None].float()      # the op consumes the PRE-cutoff gradient
+    gdev = gfull.to(dev)
+    if tracked:                                                                    # as the pair-gradient kernel hands it over: max |g| on the tensor
+        ops._tag_gmax(gdev, gdev.abs().max().reshape(1))
+    used = ops.gmax_stats["used"]
+    W.backward(gdev)
+    assert ops.gmax_stats["used"] - used == int(tracked)                           # the fp16-plane kernels ran exactly when the maximum was there
+    ref.backward(gy.double())
+    for got in prm:
+        assert bool(torch.isfinite(got.grad).all())
+    assert rel(prm[2].grad.cpu(), m64[2].weight.grad) < 1e-5 and rel(prm[3].grad.cpu(), m64[2].bias.grad) < 1e-5
+
+
 @pytest.mark.parametrize("shape,B,K,Gs", [("esol", 6, 5, 50), ("lipo", 3, 3, 50), ("esol", 3, 2, 10)])
 def test_filter_fused_into_the_gather_matches_the_two_kernels_and_fp64(shape, B, K, Gs):
     """conan_filter_cfconv_fwd (forward only): the filter rows are generated per directed edge and consumed from the accumulators — against

@@ -5,7 +5,7 @@ import ctypes, os, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 tmp = tempfile.mkdtemp(prefix="conan_prof_")
-src = os.path.join(tmp, "csrc"); shutil.copytree(os.path.join(ROOT, "conan-fgw_amd", "csrc"), src, ignore=shutil.ignore_patterns("*.o"))
+src = os.path.join(tmp, "csrc"); shutil.copytree(os.path.join(ROOT, "conan-fgw_amd", "csrc"), src, ignore=shutil.ignore_patterns("*.o", "*.d"))
 os.makedirs(os.path.join(tmp, "include")); shutil.copy(os.path.join(ROOT, "include", "conan_fgw_hip.h"), os.path.join(tmp, "include"))
 # csrc/common.h includes ../../include/...: recreate that relative layout
 os.makedirs(os.path.join(tmp, "pkg")); shutil.move(src, os.path.join(tmp, "pkg", "csrc")); src = os.path.join(tmp, "pkg", "csrc")
