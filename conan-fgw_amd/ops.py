@@ -11,6 +11,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
+from . import wgrad
 from ._lib import FgwParams, call, lib, ptr, stream_ptr
 
 f32, i32, i64 = torch.float32, torch.int32, torch.int64
@@ -153,92 +154,8 @@ def graph_ptr_from_batch(batch: Tensor, num_graphs: int) -> Tensor:
     return out
 
 
-# ------------------------------------------------------------------------------------------------ deferred weight gradients
-# A weight gradient is produced in two stages: per-slice slabs (k_wgrad_lds) and their fixed-order sum.  Inside
-# `deferred_weight_gradients()` the second stage of every Linear layer of a backward pass is postponed and run as ONE launch
-# (conan_wgrad_reduce_batch) by `flush_weight_gradients()` — FlatGradients.pack() calls it — instead of 24 launches of ~6 us each.
-# The returned dW / db tensors are only valid after the flush; a weight that appears twice in one backward (autograd would add
-# the two results right away) flushes on the spot and takes the immediate path.  Node-level layers postpone their slab kernel as well
-# (one batched launch).  With the library's slice count (LATE_SLICES_AUTO = False) results do not depend on the mode, bit for bit; by default the batch
-# cuts every job into fewer, longer slices (_late_slices): the same sums in another fixed order (1e-7 relative), 15-18 % less time for the pair of launches.
-_pending = None            # None: immediate mode; list of pending jobs (dicts) while deferring
-
-
-class deferred_weight_gradients:
-    def __enter__(self):
-        global _pending
-        self._outer = _pending
-        if _pending is None:
-            _pending = []
-        return self
-
-    def __exit__(self, *exc):
-        global _pending
-        if self._outer is None:
-            flush_weight_gradients()
-            _pending = None
-        return False
-
-
-def flush_weight_gradients():
-    """Reduce every pending slab set on the current stream (no-op when nothing is pending).  Returns {weight data_ptr: (dW data_ptr,
-    db data_ptr | None)} of what was flushed, so that the owner of the parameters can check that autograd adopted those very tensors
-    (FlatGradients._flush_deferred does, for dW and db).  The deferred mode is only sound behind that check: use it through
-    FlatGradients.backward(), not as a bare `with deferred_weight_gradients(): loss.backward()`."""
-    global _pending
-    if not _pending:
-        return {}
-    from ._lib import WgradJob, WgradSlabJob
-    jobs = (WgradJob * len(_pending))()
-    cur = torch.cuda.current_stream()
-    for st in {j["stream"] for j in _pending}:
-        if st != cur:
-            cur.wait_stream(st)                                   # slabs written on another stream (the covalent branch runs on one)
-    late = [j for j in _pending if "operands" in j]               # node-level layers: stage 1 was postponed as well (see _wgrad)
-    if late:
-        sj = (WgradSlabJob * len(late))()
-        for q, j in enumerate(late):
-            g, x, md = j["operands"]
-            sj[q].g, sj[q].x, sj[q].m_dev, sj[q].ws = ptr(g), ptr(x), ptr(md), ptr(j["ws"])
-            sl = _late_slices(len(late), j["M"])
-            sj[q].M, sj[q].K, sj[q].N, sj[q].slices = j["M"], j["K"], j["N"], sl      # 0: the library's default slice count
-            if sl:
-                j["slices"] = sl
-        call("conan_linear_wgrad_slabs_batch", sj, len(late), stream_ptr())
-        for j in late:
-            for t in j.pop("operands"):
-                if t is not None:
-                    t.record_stream(cur)
-    for q, j in enumerate(_pending):
-        jobs[q].ws, jobs[q].dW, jobs[q].dbias = ptr(j["ws"]), j["dw_ptr"], j["db_ptr"]
-        jobs[q].M, jobs[q].K, jobs[q].N, jobs[q].slices = j["M"], j["K"], j["N"], j.get("slices", 0)
-    call("conan_wgrad_reduce_batch", jobs, len(_pending), stream_ptr())
-    done = {j["weight_ptr"]: (j["dw_ptr"], j["db_ptr"]) for j in _pending}
-    for j in _pending:
-        j["ws"].record_stream(cur)
-    _pending.clear()
-    _flushed.update(done)
-    return done
-
-
-_LATE_STAGE1_ROWS = 65536   # below this row count a weight gradient's slab kernel is postponed to the batched launch
-LATE_SLICES = 0             # row slices per postponed job, forced (0 = automatic, below): tools/probe_wgrad_batch.py sweeps it
-LATE_SLICES_AUTO = True     # False: the library's default (one slice per 128 rows), i.e. the same slabs — and bits — as the immediate form
-
-
-def _late_slices(n_jobs: int, M: int) -> int:
-    """Row slices per postponed node-level job.  The library's default (one per 128 rows: 198 at cfg2) gives a 22-job batch 4 356 workgroups, each
-    writing a 64 KB slab for 8 stages of work; measured in one process (tools/probe_wgrad_batch.py, profiles/r5_wgrad_batch_slices.txt): 198 slices
-    249-261 us, 128: 218-227, 96: 212-219, 80: 217, 64: 207-209, 48: 238, 24: 270 — best where a launch (<= 24 jobs) holds ~1 400 workgroups, a
-    multiple of 8 per job (the XCD grouping of jobs that share x).  Fixed order of summation either way; not the same order as the default's."""
-    dflt = max(1, (M + 127) // 128)
-    if LATE_SLICES:
-        return LATE_SLICES if LATE_SLICES < dflt else 0           # (never more than the default: the workspace and the reducer are sized by it)
-    if not LATE_SLICES_AUTO:
-        return 0
-    s = 8 * max(1, round(1400 / max(1, min(n_jobs, 24)) / 8))
-    return s if s < dflt else 0
-_flushed = {}              # weight data_ptr -> (dW data_ptr, db data_ptr | None) of the last flushes (cleared by whoever verifies them)
+# ------------------------------------------------------------------------------------------------ weight gradients: wgrad.py (two API names stay here)
+deferred_weight_gradients, flush_weight_gradients = wgrad.deferred, wgrad.flush
 
 
 # max |g| of pair-level filter gradients: produced by conan_cfconv_bwd_w_pairs (one device float per backward of a CFConv), consumed by
@@ -260,133 +177,6 @@ def _take_gmax(t: Tensor, g: Tensor):
         return None
     gmax_stats["used"] += 1
     return tag[0]
-
-
-def _wgrad(g, x, M, K, N, md, weight, has_bias, rbf=None, gmax=None):
-    """dW [N,K] (+ db [N]) = g^T x, or g^T rbf(dist) with rbf = (dist, offset, coeff).  Immediate, or slabs now + batched sum later.
-
-    Deferred mode hands autograd tensors whose values arrive at the flush.  That is only sound if autograd ADOPTS them (it does when it
-    holds the only reference and the parameter has no .grad yet; otherwise it copies on the spot), so the pending list keeps the raw
-    pointers and the storages — never the tensors — and FlatGradients.pack() verifies the adoption."""
-    dev = g.device
-    ws = torch.empty(int(lib().conan_linear_wgrad_ws(M, K, N)), dtype=f32, device=dev)
-    dw = torch.empty(N, K, dtype=f32, device=dev)
-    db = torch.empty(N, dtype=f32, device=dev) if has_bias else None
-    wptr = weight.data_ptr()
-    defer = _pending is not None and bool(lib().conan_wgrad_batchable(K, N))
-    if defer and any(j["weight_ptr"] == wptr for j in _pending):
-        flush_weight_gradients()                                  # second use of the same weight in this backward: autograd adds the two at once
-        defer = False
-    # Node-level layers (a few ten thousand rows) are latency chains that leave most of the chip idle: in deferred mode their slab
-    # kernels are postponed too and all of them run as ONE launch at the flush (conan_linear_wgrad_slabs_batch).  g and x stay alive
-    # until then (a node-level pair is 26 MB); edge-level layers already fill the chip and keep their immediate stage 1.
-    late = defer and rbf is None and M <= _LATE_STAGE1_ROWS and not (gmax is not None and K > 64)      # (the fp16-plane form has no batched launch)
-    if rbf is None:
-        if late:
-            pass
-        elif gmax is not None and K > 64:
-            call("conan_linear_wgrad_scaled", ptr(g), ptr(x), M, K, N, ptr(md), None if defer else ptr(dw), None if defer else ptr(db), ptr(ws),
-                 ptr(gmax), stream_ptr())
-        elif defer:
-            call("conan_linear_wgrad_slabs", ptr(g), ptr(x), M, K, N, ptr(md), ptr(ws), stream_ptr())
-        else:
-            call("conan_linear_wgrad", ptr(g), ptr(x), M, K, N, ptr(md), ptr(dw), ptr(db), ptr(ws), stream_ptr())
-    else:
-        dist, offset, coeff = rbf
-        if defer:
-            call("conan_rbf_wgrad_slabs", ptr(g), ptr(dist), M, ptr(offset, f32), K, coeff, N, ptr(md), ptr(ws), stream_ptr())
-        else:
-            call("conan_rbf_wgrad", ptr(g), ptr(dist), M, ptr(offset, f32), K, coeff, N, ptr(md), ptr(dw), ptr(db), ptr(ws), stream_ptr())
-    if defer:
-        _pending.append(dict(ws=ws, dw_ptr=dw.data_ptr(), db_ptr=db.data_ptr() if db is not None else None,
-                             keep=(dw.untyped_storage(), db.untyped_storage() if db is not None else None),
-                             M=M, K=K, N=N, weight_ptr=wptr, stream=torch.cuda.current_stream()))
-        if late:
-            _pending[-1]["operands"] = (g, x, md)
-    return dw, db
-
-
-def _wgrad_shared_x(gs, x, M, K, N, md, weights, has_bias):
-    """[_wgrad(g_i, x, ...) for g_i in gs] for several Linear layers of the SAME input and the same width (dk / dv / f_proj of f; q / k / v): the
-    slab kernels of the run are ONE launch whose workgroups for one row slice sit next to each other, so x is streamed from HBM once per run
-    instead of once per layer (conan_linear_wgrad_slabs_batch; the slabs, and with them the results, are bit for bit those of the separate
-    launches).  Falls back to the separate launches where the batched kernel does not apply."""
-    n = len(gs)
-    usable = n > 1 and bool(lib().conan_wgrad_batchable(K, N)) and K > 64 and N <= 128 and M > _LATE_STAGE1_ROWS      # (node level: the late batch groups such runs itself)
-    wptrs = [w.data_ptr() for w in weights]
-    if usable and _pending is not None and (len(set(wptrs)) < n or any(j["weight_ptr"] in wptrs for j in _pending)):
-        usable = False                                            # a weight used twice in one backward: the immediate path of _wgrad handles it
-    if not usable:
-        return [_wgrad(g, x, M, K, N, md, w, hb) for g, w, hb in zip(gs, weights, has_bias)]
-    from ._lib import WgradJob, WgradSlabJob
-    dev = x.device
-    wsz = int(lib().conan_linear_wgrad_ws(M, K, N))
-    wss = [torch.empty(wsz, dtype=f32, device=dev) for _ in range(n)]
-    dws = [torch.empty(N, K, dtype=f32, device=dev) for _ in range(n)]
-    dbs = [torch.empty(N, dtype=f32, device=dev) if hb else None for hb in has_bias]
-    sj = (WgradSlabJob * n)()
-    for q in range(n):
-        sj[q].g, sj[q].x, sj[q].m_dev, sj[q].ws = ptr(gs[q]), ptr(x), ptr(md), ptr(wss[q])
-        sj[q].M, sj[q].K, sj[q].N, sj[q].slices = M, K, N, 0
-    call("conan_linear_wgrad_slabs_batch", sj, n, stream_ptr())
-    if _pending is not None:
-        for q in range(n):
-            _pending.append(dict(ws=wss[q], dw_ptr=dws[q].data_ptr(), db_ptr=dbs[q].data_ptr() if dbs[q] is not None else None,
-                                 keep=(dws[q].untyped_storage(), dbs[q].untyped_storage() if dbs[q] is not None else None),
-                                 M=M, K=K, N=N, weight_ptr=wptrs[q], stream=torch.cuda.current_stream()))
-    else:
-        jobs = (WgradJob * n)()
-        for q in range(n):
-            jobs[q].ws, jobs[q].dW, jobs[q].dbias = ptr(wss[q]), dws[q].data_ptr(), dbs[q].data_ptr() if dbs[q] is not None else None
-            jobs[q].M, jobs[q].K, jobs[q].N, jobs[q].slices = M, K, N, 0
-        call("conan_wgrad_reduce_batch", jobs, n, stream_ptr())
-    return list(zip(dws, dbs))
-
-
-def _filter_bwd(g, h1, dist, offset, coeff, w1, w2, M, md, gmax=None):
-    """dW1 [F,Gs], db1 [F] of the filter network's first Linear from the gradient g of its output, fused (conan_filter_bwd): the
-    input gradient of the second Linear times ssp'(h1) is formed tile by tile in registers and contracted with the regenerated
-    rbf(dist) on the spot.  Immediate, or slabs now + batched sum later (see _wgrad)."""
-    F, Gs = w1.shape
-    dev = g.device
-    ws = torch.empty(int(lib().conan_filter_bwd_ws(M, Gs, F)), dtype=f32, device=dev)
-    dw = torch.empty(F, Gs, dtype=f32, device=dev)
-    db = torch.empty(F, dtype=f32, device=dev)
-    wptr = w1.data_ptr()
-    defer = _pending is not None
-    if defer and any(j["weight_ptr"] == wptr for j in _pending):
-        flush_weight_gradients()
-        defer = False
-    call("conan_filter_bwd", ptr(g), ptr(h1), ptr(dist), M, ptr(offset, f32), Gs, coeff, ptr(w2), F, ptr(md),
-         None if defer else ptr(dw), None if defer else ptr(db), ptr(ws), ptr(gmax), stream_ptr())
-    if defer:
-        _pending.append(dict(ws=ws, dw_ptr=dw.data_ptr(), db_ptr=db.data_ptr(), keep=(dw.untyped_storage(), db.untyped_storage()),
-                             M=M, K=Gs, N=F, slices=int(lib().conan_filter_bwd_slices(M)), weight_ptr=wptr, stream=torch.cuda.current_stream()))
-    return dw, db
-
-
-def _filter_bwd2(g, h1, dist, offset, coeff, w1, w2, M, md, gmax):
-    """(dW1 [F,Gs], db1 [F]), (dW2 [F,F], db2 [F]) of the filter network from the gradient g of its output in ONE pass over g and h1
-    (conan_filter_bwd2: _filter_bwd and the second layer's _wgrad fused).  Immediate, or slabs now + batched sum later (see _wgrad)."""
-    F, Gs = w1.shape
-    dev = g.device
-    ws = torch.empty(int(lib().conan_filter_bwd2_ws(M, Gs, F)), dtype=f32, device=dev)
-    slices = int(lib().conan_filter_bwd2_slices(M))
-    dw1, db1 = torch.empty(F, Gs, dtype=f32, device=dev), torch.empty(F, dtype=f32, device=dev)
-    dw2, db2 = torch.empty(F, F, dtype=f32, device=dev), torch.empty(F, dtype=f32, device=dev)
-    p1, p2 = w1.data_ptr(), w2.data_ptr()
-    defer = _pending is not None
-    if defer and any(j["weight_ptr"] in (p1, p2) for j in _pending):
-        flush_weight_gradients()
-        defer = False
-    call("conan_filter_bwd2", ptr(g), ptr(h1), ptr(dist), M, ptr(offset, f32), Gs, coeff, ptr(w2), F, ptr(md), ptr(gmax),
-         None if defer else ptr(dw1), None if defer else ptr(db1), None if defer else ptr(dw2), None if defer else ptr(db2), ptr(ws), stream_ptr())
-    if defer:
-        cut = slices * (F * Gs + F)
-        for wsv, dw, db, K, wp in ((ws[:cut], dw1, db1, Gs, p1), (ws[cut:], dw2, db2, F, p2)):
-            _pending.append(dict(ws=wsv, dw_ptr=dw.data_ptr(), db_ptr=db.data_ptr(), keep=(dw.untyped_storage(), db.untyped_storage()),
-                                 M=M, K=K, N=F, slices=slices, weight_ptr=wp, stream=torch.cuda.current_stream()))
-    return (dw1, db1), (dw2, db2)
 
 
 # ------------------------------------------------------------------------------------------------ linear / activation
@@ -425,7 +215,7 @@ class _LinearFn(torch.autograd.Function):
                 dx = empty_rows(x.shape[0], x.shape[1], x.device, md)
             call("conan_linear_fwd", ptr(g), ptr(w), None, None, M, N, K, 1, 0, ptr(md), ptr(dx), stream_ptr())
         if ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
-            dw, db = _wgrad(g, x, M, K, N, md, w, ctx.has_b)
+            dw, db = wgrad.plain(g, x, M, K, N, md, w, ctx.has_b)
         return dx, dw, db, (dy if ctx.has_res else None), None, None, None
 
 
@@ -459,7 +249,7 @@ class _LinearTapFn(torch.autograd.Function):
         elif dtap is not None:
             dx = dtap
         if ctx.needs_input_grad[1]:
-            dw, _ = _wgrad(dy, x, M, K, N, None, w, False)
+            dw, _ = wgrad.plain(dy, x, M, K, N, None, w, False)
         return dx, dw
 
 
@@ -502,8 +292,8 @@ class _Mlp2Fn(torch.autograd.Function):
         dmid = torch.empty(M, N1, dtype=f32, device=x.device)
         dx = torch.empty(M, K, dtype=f32, device=x.device)
         call("conan_mlp2_bwd", ptr(dy), ptr(w2), ptr(w1), ptr(mid), M, K, N1, N2, ptr(dmid), ptr(dx), stream_ptr())
-        dw2, db2 = _wgrad(dy, mid, M, N1, N2, None, w2, True)
-        dw1, db1 = _wgrad(dmid, x, M, K, N1, None, w1, True)
+        dw2, db2 = wgrad.plain(dy, mid, M, N1, N2, None, w2, True)
+        dw1, db1 = wgrad.plain(dmid, x, M, K, N1, None, w1, True)
         return dx, dw1, db1, dw2, db2, (dy if ctx.has_res else None)
 
 
@@ -543,8 +333,8 @@ class _Mlp2OutActFn(torch.autograd.Function):
         dmid = torch.empty(M, N1, dtype=f32, device=dev)
         dx = torch.empty(M, K, dtype=f32, device=dev)
         call("conan_mlp2_outact_bwd", ptr(dy), ptr(y), ptr(w2), ptr(w1), M, K, N1, N2, ptr(g), ptr(dmid), ptr(dx), stream_ptr())
-        dw2, db2 = _wgrad(g, mid, M, N1, N2, None, w2, True)
-        dw1, db1 = _wgrad(dmid, x, M, K, N1, None, w1, True)
+        dw2, db2 = wgrad.plain(g, mid, M, N1, N2, None, w2, True)
+        dw1, db1 = wgrad.plain(dmid, x, M, K, N1, None, w1, True)
         return dx, dw1, db1, dw2, db2
 
 
@@ -641,13 +431,13 @@ class _EmbeddingFn(torch.autograd.Function):
     def backward(ctx, dout):
         z, weight = ctx.saved_tensors
         rows, H = ctx.shape
-        if _pending is not None and rows <= 128 and lib().conan_wgrad_batchable(H, rows) and not any(j["weight_ptr"] == weight.data_ptr() for j in _pending):
+        if rows <= 128 and wgrad.claim((weight.data_ptr(),), (H, rows), flush_if_pending=False):
             # inside a deferred backward pass (FlatGradients.backward): dW = onehot(z)^T dout is one more job of the batched node-level weight-gradient
             # launch (≈ 16 us at cfg2 for the one-hot build and its share of the batch, against 34 us for the two kernels of conan_embedding_bwd)
             dout = _c(dout)
             onehot = torch.empty(z.shape[0], rows, dtype=f32, device=dout.device)
             call("conan_onehot_rows", ptr(z), z.shape[0], rows, -1 if ctx.padding_idx is None else ctx.padding_idx, ptr(onehot), stream_ptr())
-            dw, _ = _wgrad(onehot, dout, z.shape[0], H, rows, None, weight, False)
+            dw, _ = wgrad.plain(onehot, dout, z.shape[0], H, rows, None, weight, False)
             return None, dw, None
         dw = torch.empty(ctx.shape, dtype=f32, device=dout.device)
         ws = torch.empty(int(lib().conan_embedding_bwd_ws(z.shape[0], ctx.shape[1], ctx.shape[0])), dtype=f32, device=dout.device)
@@ -726,15 +516,15 @@ class _FilterFn(torch.autograd.Function):
         g = _c(dW)                                   # already multiplied by C(d): cfconv(..., pre_cutoff_grad=True)
         gmax = _take_gmax(dW, g) if F == 128 else None      # max |g|, when the producer tracked it and nothing touched g since: the two kernels below run on fp16 planes
         if gmax is not None and FUSED_FILTER_BACKWARD and lib().conan_filter_bwd2_supported(Gs, F):      # both layers' gradients in one pass over g and h1
-            (dw1, db1), (dw2, db2) = _filter_bwd2(g, h1, dist, _c(offset), ctx.coeff, w1, _c(w2), ME, md, gmax)
+            (dw1, db1), (dw2, db2) = wgrad.filter_bwd2(g, h1, dist, _c(offset), ctx.coeff, w1, _c(w2), ME, md, gmax)
             return None, None, None, dw1, db1, dw2, db2, None
-        dw2, db2 = _wgrad(g, h1, ME, F, F, md, w2, True, gmax=gmax)
+        dw2, db2 = wgrad.plain(g, h1, ME, F, F, md, w2, True, gmax=gmax)
         if lib().conan_filter_bwd_supported(Gs, F):              # (g @ w2) * ssp'(h1) and its contraction with rbf(dist) in one pass
-            dw1, db1 = _filter_bwd(g, h1, dist, _c(offset), ctx.coeff, w1, _c(w2), ME, md, gmax=gmax)
+            dw1, db1 = wgrad.filter_bwd(g, h1, dist, _c(offset), ctx.coeff, w1, _c(w2), ME, md, gmax=gmax)
         else:
             dh1 = torch.empty_like(g)
             call("conan_linear_fwd", ptr(g), ptr(_c(w2)), None, ptr(h1), ME, F, F, 1, 2, ptr(md), ptr(dh1), stream_ptr())   # (g @ w2) * ssp'(h1)
-            dw1, db1 = _wgrad(dh1, None, ME, Gs, F, md, w1, True, rbf=(dist, _c(offset), ctx.coeff))      # rbf(dist) regenerated inside the GEMM
+            dw1, db1 = wgrad.plain(dh1, None, ME, Gs, F, md, w1, True, rbf=(dist, _c(offset), ctx.coeff))      # rbf(dist) regenerated inside the GEMM
         return None, None, None, dw1, db1, dw2, db2, None
 
 

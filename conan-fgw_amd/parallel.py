@@ -139,13 +139,14 @@ class FlatGradients:
         been accumulated yet — their .grad is still None, which is not a copy.  They are verified at the end of backward."""
         if not self.flat.is_cuda:
             return
-        from . import ops
+        from . import ops, wgrad
         ops.flush_weight_gradients()
-        if ops._flushed:
+        flushed = wgrad.flushed()
+        if flushed:
             grads = {p.grad.data_ptr() for p in self.params if p.grad is not None}
             for i, p in enumerate(self.params):
                 key = p.data_ptr()
-                want = ops._flushed.get(key)
+                want = flushed.get(key)
                 if want is None or (only is not None and i not in only):
                     continue
                 dw_ptr, db_ptr = want
@@ -155,9 +156,9 @@ class FlatGradients:
                     raise RuntimeError("a deferred weight gradient was copied by autograd before it was final (the parameter already had a "
                                        ".grad, or something else held the tensor): call FlatGradients.zero() before backward, or do not "
                                        "use deferred_weight_gradients here")
-                del ops._flushed[key]
+                del flushed[key]
             if only is None:
-                ops._flushed.clear()
+                flushed.clear()
 
     def backward(self, loss: torch.Tensor, grad_scale: Optional[torch.Tensor] = None):
         """loss.backward() with the slab reductions of all weight gradients batched into one launch (flushed before any gradient is

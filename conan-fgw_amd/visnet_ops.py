@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-from . import ops
+from . import ops, wgrad
 from ._lib import call, lib, ptr, stream_ptr
 
 f32 = torch.float32
@@ -85,7 +85,7 @@ class _LinearSilu(torch.autograd.Function):
             dx = _tail0_shape(M, K, x.device, md)
             call("conan_linear_fwd", ptr(g), ptr(w), None, None, M, N, K, 1, 0, ptr(md), ptr(dx), stream_ptr())
         if ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
-            dw, db = ops._wgrad(g, x, M, K, N, md, w, ctx.has_b)         # immediate, or slabs now + one batched reduction per backward pass
+            dw, db = wgrad.plain(g, x, M, K, N, md, w, ctx.has_b)         # immediate, or slabs now + one batched reduction per backward pass
         return dx, dw, db, None
 
 
@@ -175,12 +175,12 @@ class _MultiLinear(torch.autograd.Function):
                     call("conan_linear_fwd", ptr(g), ptr(w), None, None, M, N, K, 1, 0, ptr(md), ptr(tmp), stream_ptr())
                     dx = res + tmp
         if len(live) > 1 and len({ws[i].shape[0] for i in live}) == 1:      # same input, same width: one batched slab launch (x streamed once)
-            for i, (dw, db) in zip(live, ops._wgrad_shared_x([gs[i] for i in live], x, M, K, ws[live[0]].shape[0], md, [ws[i] for i in live],
+            for i, (dw, db) in zip(live, wgrad.shared_x([gs[i] for i in live], x, M, K, ws[live[0]].shape[0], md, [ws[i] for i in live],
                                                                [ctx.has_b[i] for i in live])):
                 dws[i], dbs[i] = dw, db
         else:
             for i in live:
-                dws[i], dbs[i] = ops._wgrad(gs[i], x, M, K, ws[i].shape[0], md, ws[i], ctx.has_b[i])
+                dws[i], dbs[i] = wgrad.plain(gs[i], x, M, K, ws[i].shape[0], md, ws[i], ctx.has_b[i])
         if dx is None and seed is not None:
             dx = seed
         return (dx, None, None, None) + tuple(dws) + tuple(dbs)

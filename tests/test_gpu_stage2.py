@@ -192,7 +192,7 @@ def test_deferred_weight_gradients_are_bitwise_equal_to_immediate_ones():
     """ops.deferred_weight_gradients / FlatGradients.backward: the slab reductions of all Linear layers in ONE launch and the slab kernels
     of the node-level layers in one launch too — same slices, same sums in the same order => every gradient bit-identical to the
     immediate path; a weight used twice in one backward is handled (flush + immediate)."""
-    from conan_fgw_amd import ops
+    from conan_fgw_amd import ops, wgrad
     from conan_fgw_amd.parallel import FlatGradients
     dev, b, g, m, _ = _build(B=4, K=3, seed=31)
     t = lambda a: torch.from_numpy(a).to(dev)
@@ -207,7 +207,7 @@ def test_deferred_weight_gradients_are_bitwise_equal_to_immediate_ones():
         if deferred:
             flat = FlatGradients(m.parameters())
             flat.backward(loss)
-            assert ops._pending is None                                   # context closed => everything flushed
+            assert wgrad.pending() is None                                 # context closed => everything flushed
         else:
             loss.backward()
         torch.cuda.synchronize()
@@ -216,11 +216,11 @@ def test_deferred_weight_gradients_are_bitwise_equal_to_immediate_ones():
     a, c = grads(False), grads(True)
     for k in a:                                                       # default: the batch picks its own slice count (fewer, longer slices: another order of the same sums)
         assert rel(c[k].cpu(), a[k].cpu()) < 2e-6, k
-    ops.LATE_SLICES_AUTO = False                                      # with the library's slices the deferred path reproduces the immediate one bit for bit
+    wgrad.LATE_SLICES_AUTO = False                                    # with the library's slices the deferred path reproduces the immediate one bit for bit
     try:
         c = grads(True)
     finally:
-        ops.LATE_SLICES_AUTO = True
+        wgrad.LATE_SLICES_AUTO = True
     for k in a:
         if k.endswith("embedding.weight"):
             # round 5: inside a deferred pass the embedding gradient is the weight gradient onehot(z)^T dout of the batched launch (MFMA, exact

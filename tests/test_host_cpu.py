@@ -141,27 +141,6 @@ def test_bench_plain_run_times_one_block_and_full_keeps_three():
     assert bench.parse(["--blocks", "2"]).blocks == 2 and bench.parse(["--full", "--blocks", "1"]).blocks == 1
 
 
-def test_slice_rule_of_the_batched_weight_gradients():
-    """ops._late_slices: ~1 400 workgroups per launch of <= 24 jobs, a multiple of 8 per job, never more than the library's default (one per 128
-    rows: the workspace and the reducer are sized by it); the forced knob obeys the same cap."""
-    from conan_fgw_amd import ops
-    assert ops._late_slices(22, 25275) == 64                     # cfg2's backward pass
-    assert ops._late_slices(40, 15000) == 56                     # more than 24 jobs: the launch is cut at 24
-    assert ops._late_slices(22, 1280) == 0                       # graph-level layers (default 10 slices): the default stays
-    assert ops._late_slices(1, 25275) == 0                       # a lone job: 1 400 > its default 198
-    keep = ops.LATE_SLICES
-    try:
-        ops.LATE_SLICES = 96
-        assert ops._late_slices(22, 25275) == 96 and ops._late_slices(22, 1280) == 0
-    finally:
-        ops.LATE_SLICES = keep
-    ops.LATE_SLICES_AUTO = False
-    try:
-        assert ops._late_slices(22, 25275) == 0
-    finally:
-        ops.LATE_SLICES_AUTO = True
-
-
 def test_fused_gather_is_chosen_by_the_estimated_filter_tensor_size():
     """schnet._filter_tensor_outgrows_cache: host-side estimate atoms x min(cap, atoms per conformer - 1) / 2 pair rows of 4F bytes against 192 MiB —
     cfg2 (25 k atoms in 1 280 conformers: 123 MB) keeps the two kernels, a Lipophilicity shard (29.6 k atoms in 640: 242 MB) takes the fused one."""

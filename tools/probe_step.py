@@ -9,7 +9,7 @@ if len(sys.argv) > 1 and sys.argv[1]:
     _lib._SO = sys.argv[1]
 tag = sys.argv[2] if len(sys.argv) > 2 else ""
 off = [s for s in (sys.argv[3].split(",") if len(sys.argv) > 3 else []) if s]
-from conan_fgw_amd import ops
+from conan_fgw_amd import ops, wgrad
 from conan_fgw_amd.head import EmbeddingsWithGATAggregationBaryCenter
 from conan_fgw_amd.parallel import FlatGradients
 from conan_fgw_amd.synthetic import make_batch, make_bond_graph
@@ -45,7 +45,7 @@ L = _lib.lib()
 py_off = [o for o in off if o == "late_stage1"]            # python-level switch: node-level slab kernels immediate instead of batched
 off = [o for o in off if o not in py_off]
 saved = {name: getattr(L, name) for name in off}
-late_rows = ops._LATE_STAGE1_ROWS
+late_rows = wgrad._LATE_STAGE1_ROWS
 side = torch.cuda.Stream(device=dev); side.wait_stream(torch.cuda.current_stream())
 with torch.cuda.stream(side):
     for _ in range(5): step()
@@ -54,9 +54,9 @@ with torch.cuda.stream(side):
         res["on"].append(block())
         if off or py_off:
             for name in off: setattr(L, name, lambda *a: 0)
-            if py_off: ops._LATE_STAGE1_ROWS = 0
+            if py_off: wgrad._LATE_STAGE1_ROWS = 0
             block(3); res["off"].append(block())
             for name in off: setattr(L, name, saved[name])
-            ops._LATE_STAGE1_ROWS = late_rows
+            wgrad._LATE_STAGE1_ROWS = late_rows
             block(3)
 print(tag, "step ms:", " ".join("%.3f" % t for t in res["on"]), ("| with %s off: " % ",".join(off + py_off) + " ".join("%.3f" % t for t in res["off"])) if (off or py_off) else "")
