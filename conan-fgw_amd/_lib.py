@@ -95,6 +95,9 @@ SIGNATURES = {
     "conan_bce_loss_fwd": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
     "conan_stage2_head_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "conan_stage2_head_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "conan_stage2_head_sums_supported": (c_int, [c_int, c_int, c_int]),
+    "conan_stage2_head_sums_fwd": (c_int, [_P] * 10 + [c_float] + [c_int] * 5 + [_P] * 5),
+    "conan_stage2_head_sums_bwd": (c_int, [_P] * 8 + [c_float] + [c_int] * 5 + [_P] * 10),
     "conan_adam_flat_step": (c_int, [_P, _P, _P, _P, _P, _P, c_ll] + [ctypes.c_double] * 5 + [_P, _P]),
     "conan_grad_clip_flat": (c_int, [_P, c_ll, ctypes.c_double, _P, _P, _P, _P]),
     "conan_mlp2_supported": (c_int, [c_int, c_int, c_int, c_int]),
@@ -103,6 +106,8 @@ SIGNATURES = {
     "conan_mlp2_outact_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "conan_mlp2_outact_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "conan_mlp2_outact_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "conan_mlp2_outact_dual_fwd": (c_int, [_P] * 9 + [c_int] * 4 + [_P, c_int, _P, _P, _P, _P, _P]),
+    "conan_mlp2_outact_dual_bwd": (c_int, [_P] * 8 + [c_int] * 4 + [_P, _P, _P, _P, _P, _P, _P]),
     "conan_filter_fused_supported": (c_int, [c_int, c_int]),
     "conan_filter_fwd": (c_int, [_P, _P, c_int, _P, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "conan_filter_cfconv_fwd_supported": (c_int, [c_int, c_int]),

@@ -54,6 +54,28 @@ __device__ __forceinline__ void wave_lds_fence() {
 }
 __device__ __forceinline__ float exp_neg_f(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
+// Column c of rows [lo, hi) of a [.,W] matrix, summed in row order with 8 loads in flight (a serial loop is one round trip per row): the sum of
+// k_segment_sum, and of whoever has to reproduce it bit for bit (the stage-2 head that does its own per-graph sums, head.hip).
+__device__ __forceinline__ float col_sum_rows(const float *__restrict__ x, int lo, int hi, int W, int c) {
+    float s = 0.f;
+    int a = lo;
+    for (; a + 8 <= hi; a += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = x[(size_t)(a + u) * W + c];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    if (a < hi) {                                                // tail: clamped loads, masked adds
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = x[(size_t)min(a + u, hi - 1) * W + c];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += a + u < hi ? v[u] : 0.f;
+    }
+    return s;
+}
+
 // Workgroups are dispatched round-robin over the 8 XCDs (blockIdx % 8) and every XCD has a private 4 MB L2.  The gather
 // kernels remap the block index so that XCD k works on the k-th contiguous eighth of the index space: rows that are
 // re-read by neighbouring items (a conformer's atoms, the two directions of a pair) then meet in ONE L2 instead of being

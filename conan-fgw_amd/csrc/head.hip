@@ -8,11 +8,16 @@
 // 5-15 us each on 1 280 x 64 operands — pure launch cost in a 3.2 ms step.  D <= 64 (one lane per channel), one wavefront per molecule.
 // Backward: blocks [0, nmol/4) write the input gradients (broadcast over K), the remaining blocks form the parameter gradients with a
 // fixed-order loop over the molecules (bitwise reproducible, no atomics): 2 x D/4 blocks of 4 rows of dW3 / dWb, one block for the vectors.
+//
+// The *_sums form takes what the model has in front of the head instead of x3 and xb: the per-atom h_3d with the graph pointer (x3 = its sum per
+// conformer graph, k_segment_sum) and the barycenter features Y [nmol, N, D] (xb = their sum over the N nodes, repeated K times, k_readout_fwd
+// mode 0), and forms both inside the launch — same sums in the same order, so every output and gradient has the bits of the three launches.
 #include "common.h"
 
 namespace {
 
 constexpr int HD_THREADS = 256, HD_WAVES = 4, HD_MAXD = 64, HD_PITCH = HD_MAXD + 1, HD_U = 16;
+constexpr int HS_THREADS = 512, HS_WAVES = 8, HS_MAXK = 32;      // the *_sums forward: one workgroup per molecule, a wavefront per row sum
 
 __global__ void __launch_bounds__(HD_THREADS) k_stage2_head_fwd(const float *__restrict__ x3, const float *__restrict__ xc, const float *__restrict__ xb,
                                                                 const float *__restrict__ W3, const float *__restrict__ b3,
@@ -46,12 +51,55 @@ __global__ void __launch_bounds__(HD_THREADS) k_stage2_head_fwd(const float *__r
     if (b < nmol && lane == 0) out[b] = o + breg[0];
 }
 
+// One workgroup per molecule b.  The K per-graph sums of h3 and the node sum of Y are K + 1 independent chains of dependent loads: a wavefront
+// each (lane = channel), into LDS; wavefront 0 then does what a wavefront of k_stage2_head_fwd does, reading them where that one reads x3 / xb.
+__global__ void __launch_bounds__(HS_THREADS) k_stage2_head_sums_fwd(const float *__restrict__ Y, const float *__restrict__ h3, const int *__restrict__ gptr,
+                                                                     const float *__restrict__ xc, const float *__restrict__ W3, const float *__restrict__ b3,
+                                                                     const float *__restrict__ Wb, const float *__restrict__ bb,
+                                                                     const float *__restrict__ wreg, const float *__restrict__ breg, float aw, int K, int N,
+                                                                     int D, float *__restrict__ out, float *__restrict__ m3s, float *__restrict__ mbs,
+                                                                     float *__restrict__ ts) {
+    __shared__ float W3L[HD_MAXD * HD_PITCH], WbL[HD_MAXD * HD_PITCH], rows[HS_MAXK + 1][HD_MAXD], vec[2][HD_MAXD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    for (int u = wave; u <= K; u += HS_WAVES)
+        if (lane < D)
+            rows[u][lane] = u < K ? col_sum_rows(h3, gptr[b * K + u], gptr[b * K + u + 1], D, lane)      // x3 of conformer graph b K + u
+                                  : col_sum_rows(Y, b * N, (b + 1) * N, D, lane);                       // xb of every conformer of b
+    for (int t = tid; t < D * D; t += HS_THREADS) { const int c = t / D, j = t - c * D; W3L[c * HD_PITCH + j] = W3[t]; WbL[c * HD_PITCH + j] = Wb[t]; }
+    __syncthreads();
+    const bool on = wave == 0 && lane < D;
+    float m3 = 0.f, mc = 0.f, mb = 0.f;
+    if (on) {
+        const size_t base = (size_t)b * K * D + lane;
+        for (int k = 0; k < K; ++k) { m3 += rows[k][lane]; mc += xc[base + (size_t)k * D]; mb += rows[K][lane]; }
+        const float inv = 1.0f / (float)K;
+        m3 *= inv; mc *= inv; mb *= inv;
+        vec[0][lane] = m3; vec[1][lane] = mb;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    float t = 0.f, o = 0.f;
+    if (on) {
+        float a = b3[lane], c = bb[lane];
+        for (int j = 0; j < D; ++j) { a += W3L[lane * HD_PITCH + j] * vec[0][j]; c += WbL[lane * HD_PITCH + j] * vec[1][j]; }
+        t = a + mc + aw * c;
+        o = wreg[lane] * t;
+        m3s[(size_t)b * D + lane] = m3; mbs[(size_t)b * D + lane] = mb; ts[(size_t)b * D + lane] = t;
+    }
+    o = wave_sum(o);
+    if (lane == 0) out[b] = o + breg[0];
+}
+
+// SUMS: dx3 is the per-atom gradient of h_3d (the molecule's atoms are rows gptr[b K] .. gptr[(b + 1) K]: k_segment_bcast of the K graphs) and dxb the
+// gradient of Y [nmol, N, D] (every node gets the sum over the K copies, k_readout_bwd mode 0).
+template <bool SUMS>
 __global__ void __launch_bounds__(HD_THREADS) k_stage2_head_bwd(const float *__restrict__ dout, const float *__restrict__ W3, const float *__restrict__ Wb,
                                                                 const float *__restrict__ wreg, const float *__restrict__ m3s,
                                                                 const float *__restrict__ mbs, const float *__restrict__ ts, float aw, int nmol, int K, int D,
                                                                 float *__restrict__ dx3, float *__restrict__ dxc, float *__restrict__ dxb,
                                                                 float *__restrict__ dW3, float *__restrict__ db3, float *__restrict__ dWb,
-                                                                float *__restrict__ dbb, float *__restrict__ dwreg, float *__restrict__ dbreg) {
+                                                                float *__restrict__ dbb, float *__restrict__ dwreg, float *__restrict__ dbreg,
+                                                                const int *__restrict__ gptr, int N) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nblk_x = (nmol + HD_WAVES - 1) / HD_WAVES, rows4 = (D + 3) / 4;
     if ((int)blockIdx.x < nblk_x) {
@@ -70,7 +118,15 @@ __global__ void __launch_bounds__(HD_THREADS) k_stage2_head_bwd(const float *__r
             g3 *= inv; gb *= aw * inv;
             const float gc = uo * inv;
             const size_t base = (size_t)b * K * D + lane;
-            for (int k = 0; k < K; ++k) { dx3[base + (size_t)k * D] = g3; dxc[base + (size_t)k * D] = gc; dxb[base + (size_t)k * D] = gb; }
+            if (!SUMS) {
+                for (int k = 0; k < K; ++k) { dx3[base + (size_t)k * D] = g3; dxc[base + (size_t)k * D] = gc; dxb[base + (size_t)k * D] = gb; }
+            } else {
+                float gy = 0.f;
+                for (int k = 0; k < K; ++k) { dxc[base + (size_t)k * D] = gc; gy += gb; }
+                const int lo = gptr[b * K], hi = gptr[(b + 1) * K];
+                for (int a = lo; a < hi; ++a) dx3[(size_t)a * D + lane] = g3;
+                for (int i = 0; i < N; ++i) dxb[((size_t)b * N + i) * D + lane] = gy;
+            }
         }
         return;
     }
@@ -342,8 +398,39 @@ int conan_stage2_head_bwd(const float *dout, const float *W3, const float *Wb, c
         return CONAN_E_BADARG;
     if (!conan_stage2_head_supported(D)) return CONAN_E_UNSUPPORTED;
     const int blocks = (num_molecules + HD_WAVES - 1) / HD_WAVES + 2 * ((D + 3) / 4) + 1;
-    k_stage2_head_bwd<<<blocks, HD_THREADS, 0, as_stream(stream)>>>(dout, W3, Wb, wreg, m3, mb, t, agg_weight, num_molecules, K, D, dx3, dxc, dxb, dW3,
-                                                                    db3, dWb, dbb, dwreg, dbreg);
+    k_stage2_head_bwd<false><<<blocks, HD_THREADS, 0, as_stream(stream)>>>(dout, W3, Wb, wreg, m3, mb, t, agg_weight, num_molecules, K, D, dx3, dxc, dxb,
+                                                                           dW3, db3, dWb, dbb, dwreg, dbreg, nullptr, 0);
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+int conan_stage2_head_sums_supported(int D, int K, int readout_mode) {
+    return (conan_stage2_head_supported(D) && K >= 1 && K <= HS_MAXK && readout_mode == 0) ? 1 : 0;
+}
+
+int conan_stage2_head_sums_fwd(const float *Y, const float *h3, const int *graph_ptr, const float *xc, const float *W3, const float *b3, const float *Wb,
+                               const float *bb, const float *wreg, const float *breg, float agg_weight, int num_molecules, int K, int N, int D,
+                               int readout_mode, float *out, float *m3, float *mb, float *t, void *stream) {
+    if (!Y || !h3 || !graph_ptr || !xc || !W3 || !b3 || !Wb || !bb || !wreg || !breg || !out || !m3 || !mb || !t || num_molecules < 0 || K <= 0 || N <= 0)
+        return CONAN_E_BADARG;
+    if (!conan_stage2_head_sums_supported(D, K, readout_mode)) return CONAN_E_UNSUPPORTED;
+    if (num_molecules == 0) return CONAN_OK;
+    k_stage2_head_sums_fwd<<<num_molecules, HS_THREADS, 0, as_stream(stream)>>>(Y, h3, graph_ptr, xc, W3, b3, Wb, bb, wreg, breg, agg_weight, K, N, D, out,
+                                                                                m3, mb, t);
+    CONAN_LAUNCH_CHECK();
+    return CONAN_OK;
+}
+
+int conan_stage2_head_sums_bwd(const float *dout, const float *W3, const float *Wb, const float *wreg, const float *m3, const float *mb, const float *t,
+                               const int *graph_ptr, float agg_weight, int num_molecules, int K, int N, int D, int readout_mode, float *dh3, float *dxc,
+                               float *dY, float *dW3, float *db3, float *dWb, float *dbb, float *dwreg, float *dbreg, void *stream) {
+    if (!dout || !W3 || !Wb || !wreg || !m3 || !mb || !t || !graph_ptr || !dh3 || !dxc || !dY || !dW3 || !db3 || !dWb || !dbb || !dwreg || !dbreg ||
+        num_molecules <= 0 || K <= 0 || N <= 0)
+        return CONAN_E_BADARG;
+    if (!conan_stage2_head_sums_supported(D, K, readout_mode)) return CONAN_E_UNSUPPORTED;
+    const int blocks = (num_molecules + HD_WAVES - 1) / HD_WAVES + 2 * ((D + 3) / 4) + 1;
+    k_stage2_head_bwd<true><<<blocks, HD_THREADS, 0, as_stream(stream)>>>(dout, W3, Wb, wreg, m3, mb, t, agg_weight, num_molecules, K, D, dh3, dxc, dY, dW3,
+                                                                          db3, dWb, dbb, dwreg, dbreg, graph_ptr, N);
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;
 }

@@ -115,6 +115,18 @@ class EmbeddingsWithGATAggregationBaryCenter(torch.nn.Module):
             x_cov = self.gat_embeddings_model(batch.x, batch.edge_index, batch.edge_attr, batch.batch,
                                               **({"num_graphs": num_graphs} if num_graphs is not None else {}))     # :165-167
             x_cov = ops.linear(x_cov, self.transformation_matrix_cov.weight, self.transformation_matrix_cov.bias)   # :168
+        nm = self.node_embeddings_model
+        if (ops.HEAD_SUMS_FUSED and isinstance(self.molecular_regression_lin, Linear) and hasattr(nm, "forward_w_barycenter_parts")
+                and ops.stage2_head_sums_supported(nm.hidden_channels // 2, K, nm.READOUT_MODE)):
+            # the sum readout of h_3d (:353 of schnet_no_sum.py), the barycenter readout (:308-312) and :163-171 in one launch
+            h_3d, gptr, Y = nm.forward_w_barycenter_parts(batch.z, batch.pos, K, node_index,
+                                                          **({"num_graphs": num_graphs, "max_nodes": max_nodes} if num_graphs is not None else {}))
+            if conformers_index is not None and conformers_index.numel() != gptr.numel() - 1:
+                raise ValueError("conformers_index must have one entry per conformer graph")
+            main.wait_stream(side)
+            x_cov.record_stream(main)
+            return ops.stage2_head_sums(Y, h_3d, gptr, x_cov, self.transformation_matrix_3d, self.transformation_matrix_bary,
+                                        self.molecular_regression_lin, self.agg_weight, K)
         x_3d, x_bary = self.node_embeddings_model.forward_w_barycenter(
             z=batch.z, pos=batch.pos, num_conformers=K, batch=node_index, max_iter=self.numItermax, epsilon=self.epsilon,
             **({"num_graphs": num_graphs, "max_nodes": max_nodes} if num_graphs is not None else {}))             # :153-160

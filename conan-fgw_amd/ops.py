@@ -345,6 +345,68 @@ def mlp2_outact(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor) -> Te
     return linear(linear(x, w1, b1), w2, b2, act=True)
 
 
+DUAL_HEAD = True              # both heads of the shared trunk in one launch each way (conan_mlp2_outact_dual_fwd / _bwd); tools / tests switch the two
+                              # single-head functions back on to compare (never read from the environment)
+DUAL_HEAD_FORWARD_FORM = 0    # how the forward launch shares the heads: 0 = a second grid dimension, 1 = every workgroup runs both on one load of its rows
+                              # (not distinguishable in the captured cfg2 step: DESIGN.md §8 item 4)
+
+
+class _Mlp2OutActDualFn(torch.autograd.Function):
+    """(y_a, y_b) = two _Mlp2OutActFn of ONE x, one launch each way; the backward writes dx = dx_a + dx_b once, in the kernel's epilogue, instead of
+    leaving the add of two [M,K] tensors to autograd.  Saves what the two functions save and queues the same four weight gradients, in the order in
+    which autograd runs the two (the later head's first)."""
+
+    @staticmethod
+    def forward(ctx, x, w1a, b1a, w2a, b2a, w1b, b1b, w2b, b2b, m_dev):
+        x, w1a, w2a, w1b, w2b = _c(x), _c(w1a), _c(w2a), _c(w1b), _c(w2b)
+        M, K = x.shape
+        N1, N2 = w1a.shape[0], w2a.shape[0]
+        dev = x.device
+        need = any(ctx.needs_input_grad)
+        mid_a, mid_b = (torch.empty(M, N1, dtype=f32, device=dev) if need else None for _ in range(2))
+        y_a, y_b = (torch.empty(M, N2, dtype=f32, device=dev) for _ in range(2))
+        call("conan_mlp2_outact_dual_fwd", ptr(x, f32), ptr(w1a, f32), ptr(_c(b1a), f32), ptr(w2a, f32), ptr(_c(b2a), f32), ptr(w1b, f32),
+             ptr(_c(b1b), f32), ptr(w2b, f32), ptr(_c(b2b), f32), M, K, N1, N2, ptr(m_dev), DUAL_HEAD_FORWARD_FORM, ptr(mid_a), ptr(y_a), ptr(mid_b),
+             ptr(y_b), stream_ptr())
+        ctx.m_dev = m_dev
+        ctx.save_for_backward(x, w1a, w2a, mid_a, y_a, w1b, w2b, mid_b, y_b)
+        return y_a, y_b
+
+    @staticmethod
+    def backward(ctx, dy_a, dy_b):
+        x, w1a, w2a, mid_a, y_a, w1b, w2b, mid_b, y_b = ctx.saved_tensors
+        M, K = x.shape
+        N1, N2 = w1a.shape[0], w2a.shape[0]
+        dev, md = x.device, ctx.m_dev
+        dy_a, dy_b = _c(dy_a), _c(dy_b)
+        g_a, g_b = (torch.empty(M, N2, dtype=f32, device=dev) for _ in range(2))
+        dmid_a, dmid_b = (torch.empty(M, N1, dtype=f32, device=dev) for _ in range(2))
+        dx = empty_rows(M, K, dev, md)
+        call("conan_mlp2_outact_dual_bwd", ptr(dy_a), ptr(y_a), ptr(w2a), ptr(w1a), ptr(dy_b), ptr(y_b), ptr(w2b), ptr(w1b), M, K, N1, N2, ptr(md),
+             ptr(g_a), ptr(dmid_a), ptr(g_b), ptr(dmid_b), ptr(dx), stream_ptr())
+        dw2b, db2b = wgrad.plain(g_b, mid_b, M, N1, N2, md, w2b, True)
+        dw1b, db1b = wgrad.plain(dmid_b, x, M, K, N1, md, w1b, True)
+        dw2a, db2a = wgrad.plain(g_a, mid_a, M, N1, N2, md, w2a, True)
+        dw1a, db1a = wgrad.plain(dmid_a, x, M, K, N1, md, w1a, True)
+        return dx, dw1a, db1a, dw2a, db2a, dw1b, db1b, dw2b, db2b, None
+
+
+def mlp2_outact_dual_supported(M: int, K: int, N1: int, N2: int) -> bool:
+    return bool(lib().conan_mlp2_outact_supported(int(M), int(K), int(N1), int(N2)))
+
+
+def mlp2_outact_dual(x: Tensor, head_a, head_b, m_dev: Optional[Tensor] = None):
+    """(mlp2_outact(x, *head_a), mlp2_outact(x, *head_b)) for two weight sets (w1, b1, w2, b2) of the same widths, one launch each way where DUAL_HEAD
+    and mlp2_outact_dual_supported; else the two single-head calls (`m_dev`, a device-side row count, is for the one-launch form only)."""
+    (w1a, b1a, w2a, b2a), (w1b, b1b, w2b, b2b) = head_a, head_b
+    if (DUAL_HEAD and x.is_cuda and all(b is not None for b in (b1a, b2a, b1b, b2b)) and w1a.shape == w1b.shape and w2a.shape == w2b.shape
+            and mlp2_outact_dual_supported(x.shape[0], x.shape[1], w1a.shape[0], w2a.shape[0])):
+        return _Mlp2OutActDualFn.apply(x, w1a, b1a, w2a, b2a, w1b, b1b, w2b, b2b, m_dev)
+    if m_dev is not None:
+        raise ValueError("mlp2_outact_dual: a device-side row count needs the one-launch form")
+    return mlp2_outact(x, w1a, b1a, w2a, b2a), mlp2_outact(x, w1b, b1b, w2b, b2b)
+
+
 class _Stage2HeadFn(torch.autograd.Function):
     """out = Linreg(mean_K(Lin3d(x3) + xc + aw * Linbary(xb))): one launch each way (conan_stage2_head_fwd / _bwd)."""
 
@@ -385,6 +447,54 @@ def stage2_head(x3: Tensor, xc: Tensor, xb: Tensor, lin3d, linbary, linreg, agg_
 
 def stage2_head_supported(D: int) -> bool:
     return bool(lib().conan_stage2_head_supported(int(D)))
+
+
+HEAD_SUMS_FUSED = True        # the stage-2 head forms the per-graph sums of h_3d and the readout of Y itself (conan_stage2_head_sums_fwd / _bwd: one launch
+                              # each way instead of three); tools / tests switch it off to compare (never read from the environment)
+
+
+class _Stage2HeadSumsFn(torch.autograd.Function):
+    """_Stage2HeadFn(segment_sum(h3, gptr), xc, fgw_readout(Y, K, 0), ...) in one launch each way: the backward writes the per-atom gradient of h3 and
+    dY directly."""
+
+    @staticmethod
+    def forward(ctx, Y, h3, gptr, xc, W3, b3, Wb, bb, wreg, breg, aw, K):
+        Y, h3, xc = _c(Y), _c(h3), _c(xc)
+        B, N, D = Y.shape
+        if gptr.numel() != B * K + 1 or xc.shape != (B * K, D) or h3.shape[1] != D:
+            raise ValueError(f"stage2_head_sums: Y {tuple(Y.shape)}, h3 {tuple(h3.shape)}, xc {tuple(xc.shape)} and {gptr.numel() - 1} graphs do not "
+                             f"belong to {B} molecules of {K} conformers")
+        dev = Y.device
+        out = torch.empty(B, 1, dtype=f32, device=dev)
+        m3, mb, t = (torch.empty(B, D, dtype=f32, device=dev) for _ in range(3))
+        call("conan_stage2_head_sums_fwd", ptr(Y, f32), ptr(h3, f32), ptr(gptr, i32), ptr(xc, f32), ptr(_c(W3), f32), ptr(_c(b3), f32), ptr(_c(Wb), f32),
+             ptr(_c(bb), f32), ptr(_c(wreg), f32), ptr(_c(breg), f32), float(aw), B, K, N, D, 0, ptr(out), ptr(m3), ptr(mb), ptr(t), stream_ptr())
+        ctx.save_for_backward(W3, Wb, wreg, m3, mb, t, gptr)
+        ctx.dims, ctx.aw, ctx.atoms = (B, K, N, D), float(aw), h3.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        W3, Wb, wreg, m3, mb, t, gptr = ctx.saved_tensors
+        B, K, N, D = ctx.dims
+        dev = dout.device
+        dh3, dxc, dY = (torch.empty(s, dtype=f32, device=dev) for s in ((ctx.atoms, D), (B * K, D), (B, N, D)))
+        dW3, dWb = torch.empty(D, D, dtype=f32, device=dev), torch.empty(D, D, dtype=f32, device=dev)
+        db3, dbb = torch.empty(D, dtype=f32, device=dev), torch.empty(D, dtype=f32, device=dev)
+        dwreg, dbreg = torch.empty(1, D, dtype=f32, device=dev), torch.empty(1, dtype=f32, device=dev)
+        call("conan_stage2_head_sums_bwd", ptr(_c(dout)), ptr(_c(W3)), ptr(_c(Wb)), ptr(_c(wreg)), ptr(m3), ptr(mb), ptr(t), ptr(gptr), ctx.aw, B, K, N, D, 0,
+             ptr(dh3), ptr(dxc), ptr(dY), ptr(dW3), ptr(db3), ptr(dWb), ptr(dbb), ptr(dwreg), ptr(dbreg), stream_ptr())
+        return dY, dh3, None, dxc, dW3, db3, dWb, dbb, dwreg, dbreg, None, None
+
+
+def stage2_head_sums(Y: Tensor, h3: Tensor, graph_ptr: Tensor, xc: Tensor, lin3d, linbary, linreg, agg_weight: float, K: int) -> Tensor:
+    """stage2_head(segment_sum(h3, graph_ptr, G), xc, fgw_readout(Y, K, 0), ...) with both sums inside the head's launches: Y [B,N,D] the solver's
+    barycenter features, h3 [atoms,D] per atom, xc [B*K,D] -> [B,1].  Callers check stage2_head_sums_supported."""
+    return _Stage2HeadSumsFn.apply(Y, h3, graph_ptr, xc, lin3d.weight, lin3d.bias, linbary.weight, linbary.bias, linreg.weight, linreg.bias, agg_weight, K)
+
+
+def stage2_head_sums_supported(D: int, K: int, readout_mode: int) -> bool:
+    return bool(lib().conan_stage2_head_sums_supported(int(D), int(K), int(readout_mode)))
 
 
 class _UnaryFn(torch.autograd.Function):

@@ -239,15 +239,13 @@ class SchNetNoSum(torch.nn.Module):
         else:
             graph = _graph
         h_shared = self._trunk(z, graph)
-        h = self._head(h_shared, self.lin1, self.lin2)                     # :225-227
-        h_bary = self._head(h_shared, self.lin1_bary, self.lin2_bary)      # :229-231
-        return h, h_bary
+        # :225-227 and :229-231, lin1 -> lin2 -> act twice on h_shared: one launch for both heads at node level (ops.mlp2_outact_dual), else one each
+        return ops.mlp2_outact_dual(h_shared, *((l1.weight, l1.bias, l2.weight, l2.bias)
+                                                for l1, l2 in ((self.lin1, self.lin2), (self.lin1_bary, self.lin2_bary))))
 
-    def _compute_barycenter(self, node_feature: Tensor, edge_index, batch: Tensor, batch_size: int, num_conformers: int,
-                            max_nodes: Optional[int] = None, _want_node_out: bool = True):
-        """schnet_no_sum.py:234-315.  `edge_index` may be the reference's int64 [2,E] tensor or an ops.RadiusGraph.
-        `_want_node_out=False` (forward_w_barycenter, which discards it like the reference does at :346) skips the readout of the
-        node features: the first return value is then None."""
+    def _solve_barycenter(self, node_feature: Tensor, edge_index, batch: Tensor, batch_size: int, num_conformers: int,
+                          max_nodes: Optional[int] = None):
+        """schnet_no_sum.py:234-306: the barycenter features Y [batch_size, max_nodes, d] of every molecule's conformers, and the graph."""
         K = num_conformers
         G = batch_size * K
         if isinstance(edge_index, ops.RadiusGraph):
@@ -263,21 +261,36 @@ class SchNetNoSum(torch.nn.Module):
         N, d = max_nodes, node_feature.shape[1]
         Y, C, T, info, errs = ops.fgw_barycenter_batched(Ys.view(batch_size, K, N, d), None, adjacency=graph)   # :259-306
         self.last_fgw = dict(Y=Y, C=C, T=T, info=info, errs=errs, Ys=Ys)
-        F_bary_batch = ops.fgw_readout(Y, K, self.READOUT_MODE)                            # :308-312
-        node_out = ops.segment_sum(node_feature, graph.graph_ptr, G) if _want_node_out else None    # :314
+        return Y, graph
+
+    def _compute_barycenter(self, node_feature: Tensor, edge_index, batch: Tensor, batch_size: int, num_conformers: int,
+                            max_nodes: Optional[int] = None, _want_node_out: bool = True):
+        """schnet_no_sum.py:234-315.  `edge_index` may be the reference's int64 [2,E] tensor or an ops.RadiusGraph.
+        `_want_node_out=False` (forward_w_barycenter, which discards it like the reference does at :346) skips the readout of the
+        node features: the first return value is then None."""
+        Y, graph = self._solve_barycenter(node_feature, edge_index, batch, batch_size, num_conformers, max_nodes)
+        F_bary_batch = ops.fgw_readout(Y, num_conformers, self.READOUT_MODE)               # :308-312
+        node_out = ops.segment_sum(node_feature, graph.graph_ptr, batch_size * num_conformers) if _want_node_out else None    # :314
         return node_out, F_bary_batch
+
+    def forward_w_barycenter_parts(self, z: Tensor, pos: Tensor, num_conformers: int, batch: OptTensor = None, num_graphs: Optional[int] = None,
+                                   max_nodes: Optional[int] = None):
+        """forward_w_barycenter in front of its two readouts: (h_3d per atom, graph_ptr, Y) with
+        forward_w_barycenter = (segment_sum(h_3d, graph_ptr, G), fgw_readout(Y, K, READOUT_MODE)) — for a head that forms the two itself
+        (ops.stage2_head_sums)."""
+        batch, gptr, graph, G = self._graphs(z, pos, batch, num_graphs)
+        h_3d, h_bary = self.forward_3d_bary(z, pos, batch, _graph=graph)                   # :341
+        Y, _ = self._solve_barycenter(h_bary, graph, batch, G // num_conformers, num_conformers, max_nodes=max_nodes)      # :345-352
+        return h_3d, gptr, Y
 
     def forward_w_barycenter(self, z: Tensor, pos: Tensor, num_conformers: int, batch: OptTensor = None, data_batch=None,
                              max_iter: int = 100, epsilon: float = 0.1, num_graphs: Optional[int] = None,
                              max_nodes: Optional[int] = None):
         """schnet_no_sum.py:317-354.  `max_iter` / `epsilon` are accepted and ignored exactly like the reference
         (the FGW hyper-parameters are the literals of :281-306)."""
-        batch, gptr, graph, G = self._graphs(z, pos, batch, num_graphs)
-        h_3d, h_bary = self.forward_3d_bary(z, pos, batch, _graph=graph)                   # :341
-        batch_size = G // num_conformers                                                  # :345
-        _, h_bary = self._compute_barycenter(h_bary, graph, batch, batch_size, num_conformers, max_nodes=max_nodes,
-                                             _want_node_out=False)                            # :346-352 (its first result is dropped there too)
-        h_3d = ops.segment_sum(h_3d, gptr, G)                                              # :353
+        h_3d, gptr, Y = self.forward_w_barycenter_parts(z, pos, num_conformers, batch, num_graphs=num_graphs, max_nodes=max_nodes)
+        h_bary = ops.fgw_readout(Y, num_conformers, self.READOUT_MODE)                     # :346-352 (the node readout of :314 is dropped there too)
+        h_3d = ops.segment_sum(h_3d, gptr, gptr.numel() - 1)                               # :353
         return h_3d, h_bary
 
 

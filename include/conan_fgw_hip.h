@@ -289,6 +289,19 @@ int conan_stage2_head_fwd(const float *x3, const float *xc, const float *xb, con
 int conan_stage2_head_bwd(const float *dout, const float *W3, const float *Wb, const float *wreg, const float *m3, const float *mb, const float *t,
                           float agg_weight, int num_molecules, int K, int D, float *dx3, float *dxc, float *dxb, float *dW3, float *db3, float *dWb,
                           float *dbb, float *dwreg, float *dbreg, void *stream);
+/* The same head from what the model has in front of it — the launches that form x3 and xb are part of it:
+ *   x3 = conan_segment_sum_fwd(h3, graph_ptr)   (h3 [atoms, D] per-atom features, graph_ptr [G + 1])
+ *   xb = conan_fgw_readout_fwd(Y, mode 0)       (Y [num_molecules, N, D] barycenter features: their sum over the N nodes, for each of the K conformers)
+ * with the same sums in the same order: out, m3, mb, t and every gradient have the bits of the composed calls.  The backward writes dh3 [atoms, D]
+ * (= conan_segment_sum_bwd of dx3), dxc [G, D] and dY [num_molecules, N, D] (= conan_fgw_readout_bwd of dxb).
+ * Supported: conan_stage2_head_sums_supported(D, K, readout_mode) (D <= 64, K <= 32, readout_mode 0); otherwise CONAN_E_UNSUPPORTED (compose). */
+int conan_stage2_head_sums_supported(int D, int K, int readout_mode);
+int conan_stage2_head_sums_fwd(const float *Y, const float *h3, const int *graph_ptr, const float *xc, const float *W3, const float *b3, const float *Wb,
+                               const float *bb, const float *wreg, const float *breg, float agg_weight, int num_molecules, int K, int N, int D,
+                               int readout_mode, float *out, float *m3, float *mb, float *t, void *stream);
+int conan_stage2_head_sums_bwd(const float *dout, const float *W3, const float *Wb, const float *wreg, const float *m3, const float *mb, const float *t,
+                               const int *graph_ptr, float agg_weight, int num_molecules, int K, int N, int D, int readout_mode, float *dh3, float *dxc,
+                               float *dY, float *dW3, float *db3, float *dWb, float *dbb, float *dwreg, float *dbreg, void *stream);
 
 /* Regression criterion of the training step and its gradient in one launch: loss[0] = mean((pred - target)^2), dpred[i] = 2 (pred[i] -
  * target[i]) / n.  Replaces torch.nn.functional.mse_loss + its backward (nn.MSELoss of the reference's Lightning module, common.py) — five
@@ -348,6 +361,20 @@ int conan_mlp2_outact_fwd(const float *x, const float *w1, const float *b1, cons
                           float *mid_out, float *y, void *stream);
 int conan_mlp2_outact_bwd(const float *dy, const float *y, const float *w2, const float *w1, int M, int K, int N1, int N2, float *g_out,
                           float *dmid_out, float *dx, void *stream);
+/* Two such heads (weight sets a and b) of ONE input x in one launch each way — lin1 / lin2 and lin1_bary / lin2_bary of the shared trunk
+ * (schnet_no_sum.py:225-231).  Per head the arithmetic is that of the single-head entry points, bit for bit.
+ *   forward : mid_a, y_a, mid_b, y_b as two conan_mlp2_outact_fwd calls on x.  form 0: the head is a second grid dimension; form 1: every
+ *             workgroup runs both heads on one load of its rows.
+ *   backward: g_a, dmid_a, g_b, dmid_b as two conan_mlp2_outact_bwd calls;  dx = dx_a + dx_b [M,K], each addend finalised to fp32 as on its own,
+ *             then added and written once.
+ * m_dev (nullable): device-side row count; rows from min(M, *m_dev) on are neither read nor written.  mid_* / g_* / dmid_* nullable.
+ * Supported where conan_mlp2_outact_supported(M, K, N1, N2). */
+int conan_mlp2_outact_dual_fwd(const float *x, const float *w1a, const float *b1a, const float *w2a, const float *b2a, const float *w1b, const float *b1b,
+                               const float *w2b, const float *b2b, int M, int K, int N1, int N2, const int *m_dev, int form, float *mid_a, float *y_a,
+                               float *mid_b, float *y_b, void *stream);
+int conan_mlp2_outact_dual_bwd(const float *dy_a, const float *y_a, const float *w2a, const float *w1a, const float *dy_b, const float *y_b,
+                               const float *w2b, const float *w1b, int M, int K, int N1, int N2, const int *m_dev, float *g_a, float *dmid_a, float *g_b,
+                               float *dmid_b, float *dx, void *stream);
 
 /* Fused continuous-filter generator: for every edge e
  *   W[e,:] = ( mlp2( ssp( mlp0( rbf(dist[e]) ) ) ) ) * 0.5*(cos(dist[e]*pi/cutoff)+1)
