@@ -80,10 +80,16 @@ __global__ void __launch_bounds__(256) k_gat_aggregate_fwd(const float *__restri
         const float a = ex * inv, as = ex_self * inv;
         if (on) alpha[e0 + lane] = a;
         if (lane == 0) alpha_self[i] = as;
-        for (int c = lane; c < C; c += 64) {
-            float acc = as * h[(size_t)i * C + c];
-            for (int k = 0; k < deg; ++k) acc += __shfl(a, k, 64) * h[(size_t)__shfl(j, k, 64) * C + c];
-            out[(size_t)i * C + c] = acc + (bias ? bias[c] : 0.f);
+        // The channel loop has the same trip count in every lane: a cross-lane read returns nothing from a lane that has left the loop, and the row's
+        // edges sit in lanes 0 .. deg - 1 whether or not those lanes own a channel in the last pass (C % 64 != 0).  Lanes beyond C read channel C - 1
+        // and store nothing.
+        for (int c0 = 0; c0 < C; c0 += 64) {
+            const int c = c0 + lane;
+            const bool live = c < C;
+            const int cc = live ? c : C - 1;
+            float acc = as * h[(size_t)i * C + cc];
+            for (int k = 0; k < deg; ++k) acc += __shfl(a, k, 64) * h[(size_t)__shfl(j, k, 64) * C + cc];
+            if (live) out[(size_t)i * C + c] = acc + (bias ? bias[c] : 0.f);
         }
         return;
     }
@@ -248,13 +254,17 @@ __global__ void __launch_bounds__(256) k_gat_bwd_source(const float *__restrict_
             das += wave_sum(on ? dpre[pos] : 0.f);
 #pragma unroll
             for (int u = 0; u < MAXV; ++u) {
+                if (64 * u >= C) break;                           // the same for every lane: the cross-lane reads below need the whole wavefront
                 const int c = lane + 64 * u;
-                if (c >= C) break;
-                const float dj = dout[(size_t)j * C + c], hj = h[(size_t)j * C + c];
+                const bool live = c < C;
+                const int cc = live ? c : C - 1;                  // lanes beyond C read channel C - 1 and keep nothing
+                const float dj = dout[(size_t)j * C + cc], hj = h[(size_t)j * C + cc];
                 float acc = as * dj;
-                for (int k = 0; k < deg; ++k) acc += __shfl(al, k, 64) * dout[(size_t)__shfl(tg, k, 64) * C + c];
-                dh[(size_t)j * C + c] = acc + das * att_src[c] + dad * att_dst[c];
-                p_as[u] += das * hj; p_ad[u] += dad * hj; p_b[u] += dj;
+                for (int k = 0; k < deg; ++k) acc += __shfl(al, k, 64) * dout[(size_t)__shfl(tg, k, 64) * C + cc];
+                if (live) {
+                    dh[(size_t)j * C + c] = acc + das * att_src[c] + dad * att_dst[c];
+                    p_as[u] += das * hj; p_ad[u] += dad * hj; p_b[u] += dj;
+                }
             }
         } else {
             for (int q = q0; q < q1; ++q) das += dpre[t_pos[q]];

@@ -745,9 +745,12 @@ int conan_zero_tail(float *buf, const int *m_dev, int rows, int width, void *str
  * add_self_loops with fill_value "mean", negative_slope 0.2) on the 2-D bond graph + sum readout; called from
  * EmbeddingsWithGATAggregationBaryCenter.forward (schnet_based_models.py:166-168).  SURVEY.md 8(f) rank 1. */
 
-/* Bond graph from PyG's edge_index[2,E] (int64; row 0 = source, row 1 = target; any order; self loops dropped):
+/* Bond graph from PyG's edge_index[2,E] (int64; row 0 = source, row 1 = target; any order):
  * CSR by target (rowptr[n+1], col[E] = source, eid[E] = original edge id) and by source (t_rowptr[n+1], t_pos[E] = position of
- * the edge in the by-target arrays, t_tgt[E] = its target); rows sorted => deterministic layout.  ws: 2*(n+1) ints. */
+ * the edge in the by-target arrays, t_tgt[E] = its target); rows sorted => deterministic layout.  ws: 2*(n+1) ints.
+ * Dropped, not reported: self loops (GATConv removes them before it adds its own) and edges with an endpoint outside [0, n).
+ * K = rowptr[n] <= E edges are kept; entries K .. E-1 of col / eid / t_pos / t_tgt (and of the alpha of conan_gat_aggregate_fwd)
+ * are not written.  Per target: (source, edge id) ascending; per source: by-target position ascending. */
 int conan_bond_graph_csr(const int64_t *edge_index, int num_edges, int num_nodes, int *ws, int *rowptr, int *col, int *eid,
                          int *t_rowptr, int *t_pos, int *t_tgt, void *stream);
 /* v[edge_dim] = lin_edge.weight^T att_edge, so that <lin_edge(ea), att_edge> = <ea, v> (GATConv.edge_update). */
@@ -758,7 +761,8 @@ int conan_gat_edge_vec_bwd(const float *w_edge, const float *att_edge, const flo
 int conan_gat_node_alpha(const float *h, const float *att_src, const float *att_dst, int n, int channels, float *a_src,
                          float *a_dst, void *stream);
 /* out_i = sum_{j in N(i) + {i}} alpha_ji h_j + bias; alpha = softmax_i(leaky_relu(a_src[j] + a_dst[i] + <ea_ji, v>)), the self
- * loop's ea is the mean of the incoming edge attributes.  alpha[E] (by-target order) and alpha_self[n] are saved for backward. */
+ * loop's ea is the mean of the incoming edge attributes.  alpha[E] (by-target order) and alpha_self[n] are saved for backward.
+ * Any channels > 0 (widths that are no multiple of 64 included), 1 <= edge_dim <= 8, rows of any length; bias may be NULL. */
 int conan_gat_aggregate_fwd(const float *h, const float *a_src, const float *a_dst, const int *rowptr, const int *col,
                             const int *eid, const float *edge_attr, int edge_dim, const float *v, const float *bias,
                             float negative_slope, int n, int channels, float *out, float *alpha, float *alpha_self, void *stream);
