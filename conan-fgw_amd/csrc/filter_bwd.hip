@@ -62,51 +62,17 @@ __global__ void __launch_bounds__(FB_THREADS) k_filter_bwd(const float *__restri
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
 
-    // ---- stage the three bf16 images of w2, transposed: a thread owns a 4(n) x 4(k) block (see gemm_t.hip) -------------
+    // ---- stage the images of w2, transposed (WeightPlanes, fp_planes.h): two fp16 planes, or the three bf16 planes unscaled ----------
     {
-        constexpr int PATCHES = (F / 16) * (F / 64), PERW = (PATCHES + FB_WAVES - 1) / FB_WAVES;
-        float4 wv[PERW][4];
-        const int n4l = (lane & 3) | ((lane >> 4) << 2), k4l = (lane >> 2) & 3;
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * FB_WAVES;
-            const int r0 = (pt / (F / 64)) * 16 + 4 * k4l, c0 = (pt % (F / 64)) * 64 + 4 * n4l;       // w2 rows r0.., columns c0..
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                wv[u][j] = pt < PATCHES ? *reinterpret_cast<const float4 *>(w2 + (size_t)(r0 + j) * F + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        WeightPlanes<F, F, FB_THREADS, true> st;
+        st.fetch(w2);
         if constexpr (H16) {
-            float am = 0.f;
-#pragma unroll
-            for (int u = 0; u < PERW; ++u)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) am = absmax4(am, wv[u][j]);
-            const float wmax = block_absmax<FB_THREADS>(am, wred);
+            const float wmax = block_absmax<FB_THREADS>(st.absmax(), wred);
             pow2_scale(wmax, wsc, wun);                              // the plane scale of w2; its inverse is applied where dh1 is formed
             grad_scale(*gmax, 32.0f * F * wmax, gsc, gun);           // bound: |s * dh1| <= 32 * F * max |w2| at the nominal scale
-        }
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * FB_WAVES;
-            if (pt >= PATCHES) continue;
-            const int r0 = (pt / (F / 64)) * 16 + 4 * k4l, c0 = (pt % (F / 64)) * 64 + 4 * n4l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {                     // image row c0 + e: elements r0 .. r0 + 3
-                const float v4[4] = {e == 0 ? wv[u][0].x : e == 1 ? wv[u][0].y : e == 2 ? wv[u][0].z : wv[u][0].w,
-                                     e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
-                                     e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
-                                     e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                if constexpr (H16) { store4_planes(WH, F, WS, c0 + e, r0, v4, wsc); continue; }
-                bf16x4 q1, q2, q3;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    q1[j] = (__bf16)v4[j]; const float r1 = v4[j] - (float)q1[j];
-                    q2[j] = (__bf16)r1; q3[j] = (__bf16)(r1 - (float)q2[j]);
-                }
-                *reinterpret_cast<bf16x4 *>(&WB[(0 * F + c0 + e) * WS + r0]) = q1;
-                *reinterpret_cast<bf16x4 *>(&WB[(1 * F + c0 + e) * WS + r0]) = q2;
-                *reinterpret_cast<bf16x4 *>(&WB[(2 * F + c0 + e) * WS + r0]) = q3;
-            }
+            st.park(WH, wsc);
+        } else {
+            st.each4([&](int n, int k, const float *v4) { store4_planes3(WB, F, WS, n, k, v4); });
         }
     }
     __syncthreads();

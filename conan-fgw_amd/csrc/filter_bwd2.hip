@@ -52,7 +52,7 @@ namespace {
 typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 
 constexpr int F2_RING = 1;                                     // tiles in flight per workgroup beyond the one being stored (staging registers: 16 + 8 per tile and thread; 2 measured no faster)
-constexpr int F2_THREADS = 512, F2_WAVES = 8, F2_F = 128, F2_WS = F2_F + 8, F2_JP = 64, F2_GRID_MAX = 256;
+constexpr int F2_THREADS = 512, F2_F = 128, F2_WS = F2_F + 8, F2_JP = 64, F2_GRID_MAX = 256;
 constexpr int F2_WH_BYTES = 2 * F2_F * F2_WS * 2;            // w2 planes [2][k][WS] fp16
 constexpr int F2_IMG_PLANE = 32 * 256;                         // one plane of a tile image
 constexpr int F2_IMG_BYTES = 2 * F2_IMG_PLANE;                 // both planes
@@ -100,41 +100,14 @@ __global__ void __launch_bounds__(F2_THREADS, 1) k_filter_bwd2(const float *__re
     const int l31 = lane & 31, h = lane >> 5, li = lane & 15, gidx = (lane >> 4) & 1;
     float gsc = 1.0f, gun = 1.0f, wsc = 1.0f, wun = 1.0f;
 
-    // ---- stage the two fp16 planes of w2, transposed: a thread owns a 4(n) x 4(k) block (filter_bwd.hip / gemm_t.hip) --------------
+    // ---- stage the two fp16 planes of w2, transposed (WeightPlanes, fp_planes.h) ------------------------------------------------------
     {
-        constexpr int PATCHES = (F / 16) * (F / 64), PERW = (PATCHES + F2_WAVES - 1) / F2_WAVES;
-        float4 wv[PERW][4];
-        const int n4l = (lane & 3) | ((lane >> 4) << 2), k4l = (lane >> 2) & 3;
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * F2_WAVES;
-            const int r0 = (pt / (F / 64)) * 16 + 4 * k4l, c0 = (pt % (F / 64)) * 64 + 4 * n4l;       // w2 rows r0.., columns c0..
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                wv[u][j] = pt < PATCHES ? *reinterpret_cast<const float4 *>(w2 + (size_t)(r0 + j) * F + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        float am = 0.f;
-#pragma unroll
-        for (int u = 0; u < PERW; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) am = absmax4(am, wv[u][j]);
-        const float wmax = block_absmax<F2_THREADS>(am, wred);
+        WeightPlanes<F, F, F2_THREADS, true> st;
+        st.fetch(w2);
+        const float wmax = block_absmax<F2_THREADS>(st.absmax(), wred);
         pow2_scale(wmax, wsc, wun);
         grad_scale(*gmax, 32.0f * F * wmax, gsc, gun);           // the same scales as k_filter_bwd (filter_bwd.hip): bound of |s * dh1| at the nominal scale
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * F2_WAVES;
-            if (pt >= PATCHES) continue;
-            const int r0 = (pt / (F / 64)) * 16 + 4 * k4l, c0 = (pt % (F / 64)) * 64 + 4 * n4l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {                     // plane row c0 + e: elements r0 .. r0 + 3
-                const float v4[4] = {e == 0 ? wv[u][0].x : e == 1 ? wv[u][0].y : e == 2 ? wv[u][0].z : wv[u][0].w,
-                                     e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
-                                     e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
-                                     e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                store4_planes(WH, F, WS, c0 + e, r0, v4, wsc);
-            }
-        }
+        st.park(WH, wsc);
     }
 
     // Rows are walked from the END (filter_bwd.hip: the kernel that produced g streamed it front to back through the Infinity Cache, so

@@ -80,78 +80,16 @@ __global__ void __launch_bounds__(NT) k_linear_t16(const float *__restrict__ x, 
     const int l31 = lane & 31, h = lane >> 5;
     const int wave_stride = nslots * (NT / 64);
     float4 xa[S], xb[S];
-    auto load_x = [&](int t) {
-        const int mr = min((t << 5) + l31, M - 1);
-        const float *xr = x + (size_t)mr * ldx + 8 * h;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {                          // lane-half h owns k = 16s + 8h .. +7 of its row
-            xa[s] = *reinterpret_cast<const float4 *>(xr + 16 * s);
-            xb[s] = *reinterpret_cast<const float4 *>(xr + 16 * s + 4);
-        }
-    };
+    auto load_x = [&](int t) { row_load<S>(x, min((t << 5) + l31, M - 1), ldx, h, xa, xb); };
     if (slot * (NT / 64) + wave < tiles) load_x(slot * (NT / 64) + wave);
-    // Staging of the two fp16 planes of W as [n][k]; all of a thread's loads are in flight before the first use.
-    if (!w_kn) {                                              // w is [N][K]: float4 = 4 consecutive k -> one 8-byte store per image
-        constexpr int V4 = N * K / 4, PER = (V4 + NT - 1) / NT;
-        float4 wv[PER];
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int q = tid + u * NT;
-            const int n = (4 * q) / K, k = 4 * q - n * K;
-            wv[u] = q < V4 ? *reinterpret_cast<const float4 *>(w + (size_t)n * ldw + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        float wsc = 1.0f;
-        float am = 0.f;
-#pragma unroll
-        for (int u = 0; u < PER; ++u) am = absmax4(am, wv[u]);
-        pow2_scale(block_absmax<NT>(am, wred), wsc, wun);
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int q = tid + u * NT;
-            if (q >= V4) continue;
-            const float v4[4] = {wv[u].x, wv[u].y, wv[u].z, wv[u].w};
-            const int n = (4 * q) / K, k = 4 * q - n * K;
-            store4_planes(WB, N, WS, n, k, v4, wsc);
-        }
-    } else {
-        // w is [K][N] (the dx GEMM of the backward reads the forward weight transposed).  A thread owns a 4(k) x 4(n) block:
-        // four float4 loads along n, transposed in registers, 8-byte stores along k.  Inside a wavefront the blocks form a
-        // 4(k4) x 16(n4) patch with lane = (n4 & 3) | (k4 << 2) | ((n4 >> 2) << 4): every 16-lane group then covers 4 rows x
-        // 4 k-blocks = 16 distinct 8-byte bank slots (rows 4 apart sit 64 B apart modulo the 256-B bank cycle).
-        constexpr int PATCHES = (K / 16) * (N / 64), PERW = (PATCHES + NT / 64 - 1) / (NT / 64);
-        float4 wv[PERW][4];
-        const int n4l = (lane & 3) | ((lane >> 4) << 2), k4l = (lane >> 2) & 3;
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * (NT / 64);
-            const int k0 = (pt / (N / 64)) * 16 + 4 * k4l, n0 = (pt % (N / 64)) * 64 + 4 * n4l;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                wv[u][j] = pt < PATCHES ? *reinterpret_cast<const float4 *>(w + (size_t)(k0 + j) * ldw + n0) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        float wsc = 1.0f;
-        float am = 0.f;
-#pragma unroll
-        for (int u = 0; u < PERW; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                am = absmax4(am, wv[u][j]);
-        pow2_scale(block_absmax<NT>(am, wred), wsc, wun);
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * (NT / 64);
-            if (pt >= PATCHES) continue;
-            const int k0 = (pt / (N / 64)) * 16 + 4 * k4l, n0 = (pt % (N / 64)) * 64 + 4 * n4l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {                     // row n0 + e of the image: k0 .. k0 + 3
-                const float v4[4] = {e == 0 ? wv[u][0].x : e == 1 ? wv[u][0].y : e == 2 ? wv[u][0].z : wv[u][0].w,
-                                     e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
-                                     e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
-                                     e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                store4_planes(WB, N, WS, n0 + e, k0, v4, wsc);
-            }
-        }
-    }
+    // the two fp16 planes of W as [n][k] (WeightPlanes, fp_planes.h), from w [N][K] or, for the dx GEMM of the backward, the forward weight [K][N]
+    auto stage = [&](auto &st) {
+        st.fetch(w, ldw);
+        float wsc;
+        pow2_scale(block_absmax<NT>(st.absmax(), wred), wsc, wun);
+        st.park(WB, wsc);
+    };
+    if (!w_kn) { WeightPlanes<N, K, NT, false> st; stage(st); } else { WeightPlanes<N, K, NT, true> st; stage(st); }
     for (int t = tid; t < N; t += NT) BL[t] = bias ? bias[t] : 0.f;
     __syncthreads();
 
@@ -163,39 +101,18 @@ __global__ void __launch_bounds__(NT) k_linear_t16(const float *__restrict__ x, 
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-        float xun = 1.0f;                                      // inverse of this lane's row scale x inverse weight scale
-        float am = 0.f;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            am = absmax4(am, xa[s]);
-            am = absmax4(am, xb[s]);
-        }
-        am = fmaxf(am, __shfl_xor(am, 32));                // the other half of the row sits on lane ^ 32
         float xsc, xu;
-        pow2_scale(am, xsc, xu);
-        xun = xu * wun;
-        const _Float16 *WH = reinterpret_cast<const _Float16 *>(WB);
+        pow2_scale(row_absmax<S>(xa, xb), xsc, xu);
+        const float xun = xu * wun;                            // inverse of this lane's row scale x inverse weight scale
         // the whole tile becomes fp16 planes first (same register count as the fp32 rows): the fp32 registers are then free for the
         // NEXT tile's rows, whose loads fly during this tile's MFMA loop and epilogue instead of during the epilogue alone
         f16x8 q1[S], q2[S];
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const float xv[8] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w, xb[s].x, xb[s].y, xb[s].z, xb[s].w};
-            split2h(xv, xsc, q1[s], q2[s]);
-        }
+        for (int s = 0; s < S; ++s) row_split(xa[s], xb[s], xsc, q1[s], q2[s]);
         if (tile + wave_stride < tiles) load_x(tile + wave_stride);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const int colp = 16 * s + 8 * h;
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const int row = 32 * nb + l31;
-                const f16x8 p1 = *reinterpret_cast<const f16x8 *>(&WH[(0 * N + row) * WS + colp]);
-                const f16x8 p2 = *reinterpret_cast<const f16x8 *>(&WH[(1 * N + row) * WS + colp]);
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p2, q1[s], acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q2[s], acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q1[s], acc[nb], 0, 0, 0);
-            }
+            planes_kstep<N, WS>(WB, 16 * s + 8 * h, l31, q1[s], q2[s], acc);
             __builtin_amdgcn_sched_barrier(0);
         }
         const int mc = valid ? m : M - 1;                      // rows beyond M compute on a clamped row and are not stored
@@ -309,69 +226,16 @@ __device__ __forceinline__ int pow2_exp(float amax) {          // e with amax * 
     const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
     return (e >= 9 && e <= 254) ? e - 135 : LT_NOEXP;
 }
-// the two fp16 planes of one [N][K] weight image (k_linear_t16's staging as a function); returns the image's unit exponent
+// the two fp16 planes of one [N][K] weight image (WeightPlanes, fp_planes.h); returns the image's unit exponent
 template <int K, int N, int NT>
 __device__ __forceinline__ int lt_stage_planes(const float *__restrict__ w, int w_kn, int ldw, _Float16 *WB, float *wred) {
-    constexpr int WS = K + 8;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int ew;
-    if (!w_kn) {
-        constexpr int V4 = N * K / 4, PER = (V4 + NT - 1) / NT;
-        float4 wv[PER];
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int q = tid + u * NT;
-            const int n = (4 * q) / K, k = 4 * q - n * K;
-            wv[u] = q < V4 ? *reinterpret_cast<const float4 *>(w + (size_t)n * ldw + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        float am = 0.f;
-#pragma unroll
-        for (int u = 0; u < PER; ++u) am = absmax4(am, wv[u]);
-        ew = pow2_exp(block_absmax<NT>(am, wred));
-        const float wsc = ew == LT_NOEXP ? 1.0f : pow2i(-ew);
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int q = tid + u * NT;
-            if (q >= V4) continue;
-            const float v4[4] = {wv[u].x, wv[u].y, wv[u].z, wv[u].w};
-            const int n = (4 * q) / K, k = 4 * q - n * K;
-            store4_planes(WB, N, WS, n, k, v4, wsc);
-        }
-    } else {
-        constexpr int PATCHES = (K / 16) * (N / 64), PERW = (PATCHES + NT / 64 - 1) / (NT / 64);
-        float4 wv[PERW][4];
-        const int n4l = (lane & 3) | ((lane >> 4) << 2), k4l = (lane >> 2) & 3;
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * (NT / 64);
-            const int k0 = (pt / (N / 64)) * 16 + 4 * k4l, n0 = (pt % (N / 64)) * 64 + 4 * n4l;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                wv[u][j] = pt < PATCHES ? *reinterpret_cast<const float4 *>(w + (size_t)(k0 + j) * ldw + n0) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        float am = 0.f;
-#pragma unroll
-        for (int u = 0; u < PERW; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                am = absmax4(am, wv[u][j]);
-        ew = pow2_exp(block_absmax<NT>(am, wred));
-        const float wsc = ew == LT_NOEXP ? 1.0f : pow2i(-ew);
-#pragma unroll
-        for (int u = 0; u < PERW; ++u) {
-            const int pt = wave + u * (NT / 64);
-            if (pt >= PATCHES) continue;
-            const int k0 = (pt / (N / 64)) * 16 + 4 * k4l, n0 = (pt % (N / 64)) * 64 + 4 * n4l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float v4[4] = {e == 0 ? wv[u][0].x : e == 1 ? wv[u][0].y : e == 2 ? wv[u][0].z : wv[u][0].w,
-                                     e == 0 ? wv[u][1].x : e == 1 ? wv[u][1].y : e == 2 ? wv[u][1].z : wv[u][1].w,
-                                     e == 0 ? wv[u][2].x : e == 1 ? wv[u][2].y : e == 2 ? wv[u][2].z : wv[u][2].w,
-                                     e == 0 ? wv[u][3].x : e == 1 ? wv[u][3].y : e == 2 ? wv[u][3].z : wv[u][3].w};
-                store4_planes(WB, N, WS, n0 + e, k0, v4, wsc);
-            }
-        }
-    }
+    auto stage = [&](auto &st) {
+        st.fetch(w, ldw);
+        ew = pow2_exp(block_absmax<NT>(st.absmax(), wred));
+        st.park(WB, ew == LT_NOEXP ? 1.0f : pow2i(-ew));
+    };
+    if (!w_kn) { WeightPlanes<N, K, NT, false> st; stage(st); } else { WeightPlanes<N, K, NT, true> st; stage(st); }
     __syncthreads();                                           // wred is reused by the next image
     return ew == LT_NOEXP ? 0 : ew;                            // (an all-zero image: unit 1, planes 0)
 }
@@ -427,15 +291,7 @@ __global__ void __launch_bounds__(NT) k_linear_sum16(const LtSrcs Sx, const floa
     const int l31 = lane & 31, h = lane >> 5;
     const int wave_stride = nslots * (NT / 64);
     float4 xa[S], xb[S];
-    auto load_x = [&](int t, int c) {
-        const int mr = min((t << 5) + l31, M - 1);
-        const float *xr = Sx.x[c] + (size_t)mr * Sx.ldx[c] + 8 * h;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            xa[s] = *reinterpret_cast<const float4 *>(xr + 16 * s);
-            xb[s] = *reinterpret_cast<const float4 *>(xr + 16 * s + 4);
-        }
-    };
+    auto load_x = [&](int t, int c) { row_load<S>(Sx.x[c], min((t << 5) + l31, M - 1), Sx.ldx[c], h, xa, xb); };
     if (slot * (NT / 64) + wave < tiles) load_x(slot * (NT / 64) + wave, 0);
     int ew[NCH];
 #pragma unroll
@@ -455,14 +311,7 @@ __global__ void __launch_bounds__(NT) k_linear_sum16(const LtSrcs Sx, const floa
         int r = LT_NOEXP;                                      // unit exponent of the accumulators
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            float am = 0.f;
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                am = absmax4(am, xa[s]);
-                am = absmax4(am, xb[s]);
-            }
-            am = fmaxf(am, __shfl_xor(am, 32));
-            const int ex = pow2_exp(am);
+            const int ex = pow2_exp(row_absmax<S>(xa, xb));
             const int u = ex == LT_NOEXP ? LT_NOEXP : ex + ew[c];
             const int rn = max(r, u);
             if (c > 0) {
@@ -476,25 +325,12 @@ __global__ void __launch_bounds__(NT) k_linear_sum16(const LtSrcs Sx, const floa
             const float xsc = r == LT_NOEXP ? 1.0f : pow2i(ew[c] - r);
             f16x8 q1[S], q2[S];
 #pragma unroll
-            for (int s = 0; s < S; ++s) {
-                const float xv[8] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w, xb[s].x, xb[s].y, xb[s].z, xb[s].w};
-                split2h(xv, xsc, q1[s], q2[s]);
-            }
+            for (int s = 0; s < S; ++s) row_split(xa[s], xb[s], xsc, q1[s], q2[s]);
             if (c + 1 < NCH) load_x(tile, c + 1);
             else if (tile + wave_stride < tiles) load_x(tile + wave_stride, 0);
-            const _Float16 *Wc = WH + c * PL;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                const int colp = 16 * s + 8 * h;
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    const int row = 32 * nb + l31;
-                    const f16x8 p1 = *reinterpret_cast<const f16x8 *>(&Wc[(0 * N + row) * WS + colp]);
-                    const f16x8 p2 = *reinterpret_cast<const f16x8 *>(&Wc[(1 * N + row) * WS + colp]);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p2, q1[s], acc[nb], 0, 0, 0);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q2[s], acc[nb], 0, 0, 0);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q1[s], acc[nb], 0, 0, 0);
-                }
+                planes_kstep<N, WS>(WH + c * PL, 16 * s + 8 * h, l31, q1[s], q2[s], acc);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -549,15 +385,7 @@ __global__ void __launch_bounds__(NT) k_linear_fan16(const float *__restrict__ x
     const int l31 = lane & 31, h = lane >> 5;
     const int wave_stride = nslots * (NT / 64);
     float4 xa[S], xb[S];
-    auto load_x = [&](int t) {
-        const int mr = min((t << 5) + l31, M - 1);
-        const float *xr = x + (size_t)mr * ldx + 8 * h;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            xa[s] = *reinterpret_cast<const float4 *>(xr + 16 * s);
-            xb[s] = *reinterpret_cast<const float4 *>(xr + 16 * s + 4);
-        }
-    };
+    auto load_x = [&](int t) { row_load<S>(x, min((t << 5) + l31, M - 1), ldx, h, xa, xb); };
     if (slot * (NT / 64) + wave < tiles) load_x(slot * (NT / 64) + wave);
     int ew[NL];
 #pragma unroll
@@ -566,21 +394,11 @@ __global__ void __launch_bounds__(NT) k_linear_fan16(const float *__restrict__ x
     __syncthreads();
 
     for (int tile = slot * (NT / 64) + wave; tile < tiles; tile += wave_stride) {
-        float am = 0.f;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            am = absmax4(am, xa[s]);
-            am = absmax4(am, xb[s]);
-        }
-        am = fmaxf(am, __shfl_xor(am, 32));
         float xsc, xu;
-        pow2_scale(am, xsc, xu);
+        pow2_scale(row_absmax<S>(xa, xb), xsc, xu);
         f16x8 q1[S], q2[S];
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const float xv[8] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w, xb[s].x, xb[s].y, xb[s].z, xb[s].w};
-            split2h(xv, xsc, q1[s], q2[s]);
-        }
+        for (int s = 0; s < S; ++s) row_split(xa[s], xb[s], xsc, q1[s], q2[s]);
         if (tile + wave_stride < tiles) load_x(tile + wave_stride);
         const int rbase = tile << 5;
 #pragma unroll
@@ -590,19 +408,9 @@ __global__ void __launch_bounds__(NT) k_linear_fan16(const float *__restrict__ x
             for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-            const _Float16 *Wl = WH + l * PL;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                const int colp = 16 * s + 8 * h;
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    const int row = 32 * nb + l31;
-                    const f16x8 p1 = *reinterpret_cast<const f16x8 *>(&Wl[(0 * N + row) * WS + colp]);
-                    const f16x8 p2 = *reinterpret_cast<const f16x8 *>(&Wl[(1 * N + row) * WS + colp]);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p2, q1[s], acc[nb], 0, 0, 0);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q2[s], acc[nb], 0, 0, 0);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q1[s], acc[nb], 0, 0, 0);
-                }
+                planes_kstep<N, WS>(WH + l * PL, 16 * s + 8 * h, l31, q1[s], q2[s], acc);
                 __builtin_amdgcn_sched_barrier(0);
             }
             const float xun = xu * pow2i(ew[l]);               // (pow2_scale's inverse row scale x the layer's weight unit)

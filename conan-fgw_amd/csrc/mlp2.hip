@@ -27,80 +27,16 @@ namespace {
 constexpr int M2_THREADS = 256, M2_WAVES = 4;
 constexpr int M2_NPL = 2;                                      // operand planes (two fp16 planes, fp_planes.h)
 
-// Two fp16 planes of a weight as [n][k] (pitch KD + 8), staged by all threads in two steps so that the global loads of BOTH weights can
-// be in flight from the start of the kernel: m2_fetch (float4 loads into registers) and m2_park (split + 8-byte LDS stores).
-// src is [n][k] (TRANS = false: forward; a float4 = 4 consecutive k of one row) or [k][n] (TRANS = true: the backward reads the forward
-// weights transposed; a thread owns a 4(k) x 4(n) block, transposed in registers — lane mapping as gemm_t.hip: every 16-lane group covers
-// 16 distinct 8-byte bank slots).  PERM: inside every group of 16 k's the columns are stored in the order in which a lane-half
-// enumerates the accumulator registers of the previous GEMM (position 8h + j <-> (j&3) + 8(j>>2) + 4h); four consecutive, 4-aligned k's
-// stay consecutive under that permutation, so the 8-byte stores survive it.
-__device__ __forceinline__ int m2_perm4(int k, bool perm) {
-    if (!perm) return k;
+// Both weights are staged as WeightPlanes (fp_planes.h: fetch, then park), so that the global loads of BOTH can be in flight from the start
+// of the kernel; the forward reads them as [n][k], the backward reads the forward weights transposed.  The second weight is parked with the
+// column permutation m2_perm4: inside every group of 16 k's the columns are stored in the order in which a lane-half enumerates the accumulator
+// registers of the previous GEMM (position 8h + j <-> (j&3) + 8(j>>2) + 4h); four consecutive, 4-aligned k's stay consecutive under that
+// permutation, so the 8-byte stores survive it.
+__device__ __forceinline__ int m2_perm4(int k) {
     const int a = (k & 15) >> 2;
     return (k & ~15) + 8 * (a & 1) + 4 * (a >> 1);
 }
-template <int NO, int KD, bool TRANS>
-struct M2Weight {
-    static constexpr int V4 = NO * KD / 4, PER = (V4 + M2_THREADS - 1) / M2_THREADS;                       // plain layout: float4s per thread
-    static constexpr int PATCHES = (KD / 16) * (NO / 64), PERW = (PATCHES + M2_WAVES - 1) / M2_WAVES;      // transposed layout: 16(k) x 64(n) patches per wave
-    float4 v[TRANS ? PERW * 4 : PER];
-    __device__ __forceinline__ void fetch(const float *__restrict__ w, int tid) {
-        const int lane = tid & 63, wave = tid >> 6;
-        if (!TRANS) {
-#pragma unroll
-            for (int u = 0; u < PER; ++u) {
-                const int q = tid + u * M2_THREADS;
-                v[u] = q < V4 ? *reinterpret_cast<const float4 *>(w + 4 * (size_t)q) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        } else {
-            const int n4l = (lane & 3) | ((lane >> 4) << 2), k4l = (lane >> 2) & 3;
-#pragma unroll
-            for (int u = 0; u < PERW; ++u) {
-                const int pt = wave + u * M2_WAVES;
-                const int k0 = (pt / (NO / 64)) * 16 + 4 * k4l, n0 = (pt % (NO / 64)) * 64 + 4 * n4l;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    v[4 * u + j] = pt < PATCHES ? *reinterpret_cast<const float4 *>(w + (size_t)(k0 + j) * NO + n0) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-    }
-    __device__ __forceinline__ float absmax() const {
-        float m = 0.f;
-#pragma unroll
-        for (int u = 0; u < (TRANS ? PERW * 4 : PER); ++u) m = absmax4(m, v[u]);
-        return m;
-    }
-    __device__ __forceinline__ void park(__bf16 *__restrict__ WB, int tid, bool perm, float sc = 1.0f) const {
-        constexpr int WS = KD + 8;
-        const int lane = tid & 63, wave = tid >> 6;
-        if (!TRANS) {
-#pragma unroll
-            for (int u = 0; u < PER; ++u) {
-                const int q = tid + u * M2_THREADS;
-                if (q >= V4) continue;
-                const int n = (4 * q) / KD, k = 4 * q - n * KD;
-                const float v4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                store4_planes(WB, NO, WS, n, m2_perm4(k, perm), v4, sc);
-            }
-        } else {
-            const int n4l = (lane & 3) | ((lane >> 4) << 2), k4l = (lane >> 2) & 3;
-#pragma unroll
-            for (int u = 0; u < PERW; ++u) {
-                const int pt = wave + u * M2_WAVES;
-                if (pt >= PATCHES) continue;
-                const int k0 = (pt / (NO / 64)) * 16 + 4 * k4l, n0 = (pt % (NO / 64)) * 64 + 4 * n4l;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {                     // row n0 + e of the image: k0 .. k0 + 3
-                    const float v4[4] = {e == 0 ? v[4 * u].x : e == 1 ? v[4 * u].y : e == 2 ? v[4 * u].z : v[4 * u].w,
-                                         e == 0 ? v[4 * u + 1].x : e == 1 ? v[4 * u + 1].y : e == 2 ? v[4 * u + 1].z : v[4 * u + 1].w,
-                                         e == 0 ? v[4 * u + 2].x : e == 1 ? v[4 * u + 2].y : e == 2 ? v[4 * u + 2].z : v[4 * u + 2].w,
-                                         e == 0 ? v[4 * u + 3].x : e == 1 ? v[4 * u + 3].y : e == 2 ? v[4 * u + 3].z : v[4 * u + 3].w};
-                    store4_planes(WB, NO, WS, n0 + e, m2_perm4(k0, perm), v4, sc);
-                }
-            }
-        }
-    }
-};
+template <int NO, int KD, bool TRANS> using M2Planes = WeightPlanes<NO, KD, M2_THREADS, TRANS>;
 
 // One wavefront's 32-row tile through both GEMMs and their element-wise steps, against the staged planes WB / WB2 (inverse scales unA / unB) and the
 // biases BL [NA + NB]: everything of k_mlp2 behind the staging barrier.  xa / xb: the tile's input rows (MODE 3: already times ssp'), av: the saved
@@ -119,33 +55,15 @@ __device__ __forceinline__ void m2_rows(const float4 (&xa)[KA / 16], const float
     for (int nb = 0; nb < MBA; ++nb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc1[nb][r] = 0.f;
-    float un1 = 1.0f;                                          // inverse of (row scale of x) x (scale of the first weight)
-    {
-    float am = 0.f;
-#pragma unroll
-    for (int s = 0; s < SA; ++s) { am = absmax4(am, xa[s]); am = absmax4(am, xb[s]); }
-    am = fmaxf(am, __shfl_xor(am, 32));                    // the other half of the row sits on lane ^ 32
     float xsc, xu;
-    pow2_scale(am, xsc, xu);
-    un1 = xu * unA;
-    const _Float16 *WH = reinterpret_cast<const _Float16 *>(WB);
+    pow2_scale(row_absmax<SA>(xa, xb), xsc, xu);
+    const float un1 = xu * unA;                                // inverse of (row scale of x) x (scale of the first weight)
 #pragma unroll
     for (int s = 0; s < SA; ++s) {
-        const float xv[8] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w, xb[s].x, xb[s].y, xb[s].z, xb[s].w};
         f16x8 q1, q2;
-        split2h(xv, xsc, q1, q2);
-        const int colp = 16 * s + 8 * h;
-#pragma unroll
-        for (int nb = 0; nb < MBA; ++nb) {
-            const int row = 32 * nb + l31;
-            const f16x8 p1 = *reinterpret_cast<const f16x8 *>(&WH[(0 * NA + row) * WSA + colp]);
-            const f16x8 p2 = *reinterpret_cast<const f16x8 *>(&WH[(1 * NA + row) * WSA + colp]);
-            acc1[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p2, q1, acc1[nb], 0, 0, 0);
-            acc1[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q2, acc1[nb], 0, 0, 0);
-            acc1[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q1, acc1[nb], 0, 0, 0);
-        }
+        row_split(xa[s], xb[s], xsc, q1, q2);
+        planes_kstep<NA, WSA>(WB, 16 * s + 8 * h, l31, q1, q2, acc1);
         __builtin_amdgcn_sched_barrier(0);
-    }
     }
 #pragma unroll
     for (int nb = 0; nb < MBA; ++nb)
@@ -190,9 +108,7 @@ __device__ __forceinline__ void m2_rows(const float4 (&xa)[KA / 16], const float
     for (int nb = 0; nb < MBB; ++nb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc2[nb][r] = 0.f;
-    float un2 = 1.0f;
-    {
-    float am = 0.f;                                        // the row of `mid`: 64 channels here, 64 on lane ^ 32
+    float am = 0.f;                                            // the row of `mid`: 64 channels here, 64 on lane ^ 32
 #pragma unroll
     for (int nb = 0; nb < MBA; ++nb)
 #pragma unroll
@@ -200,8 +116,7 @@ __device__ __forceinline__ void m2_rows(const float4 (&xa)[KA / 16], const float
     am = fmaxf(am, __shfl_xor(am, 32));
     float msc, mu;
     pow2_scale(am, msc, mu);
-    un2 = mu * unB;
-    const _Float16 *WH = reinterpret_cast<const _Float16 *>(WB2);
+    const float un2 = mu * unB;
 #pragma unroll
     for (int ms = 0; ms < SB; ++ms) {
         const int mb = ms >> 1, sgrp = ms & 1;
@@ -210,18 +125,8 @@ __device__ __forceinline__ void m2_rows(const float4 (&xa)[KA / 16], const float
         for (int j = 0; j < 8; ++j) hv[j] = acc1[mb][8 * sgrp + j];
         f16x8 q1, q2;
         split2h(hv, msc, q1, q2);
-        const int colp = 32 * mb + 16 * sgrp + 8 * h;
-#pragma unroll
-        for (int nb = 0; nb < MBB; ++nb) {
-            const int row = 32 * nb + l31;
-            const f16x8 p1 = *reinterpret_cast<const f16x8 *>(&WH[(0 * NB + row) * WSB + colp]);
-            const f16x8 p2 = *reinterpret_cast<const f16x8 *>(&WH[(1 * NB + row) * WSB + colp]);
-            acc2[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p2, q1, acc2[nb], 0, 0, 0);
-            acc2[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q2, acc2[nb], 0, 0, 0);
-            acc2[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, q1, acc2[nb], 0, 0, 0);
-        }
+        planes_kstep<NB, WSB>(WB2, 32 * mb + 16 * sgrp + 8 * h, l31, q1, q2, acc2);
         __builtin_amdgcn_sched_barrier(0);
-    }
     }
     if (!valid) return;                                        // (no barrier behind this point)
 #pragma unroll
@@ -239,16 +144,6 @@ __device__ __forceinline__ void m2_rows(const float4 (&xa)[KA / 16], const float
         }
 }
 
-// The two halves of a lane's part of row mr of a [.,KA] matrix: 8 of every 16 consecutive channels, the other 8 sit on lane ^ 32.
-template <int KA>
-__device__ __forceinline__ void m2_load_row(const float *__restrict__ src, int mr, int h, float4 (&a)[KA / 16], float4 (&b)[KA / 16]) {
-    const float *r = src + (size_t)mr * KA + 8 * h;
-#pragma unroll
-    for (int s = 0; s < KA / 16; ++s) {
-        a[s] = *reinterpret_cast<const float4 *>(r + 16 * s);
-        b[s] = *reinterpret_cast<const float4 *>(r + 16 * s + 4);
-    }
-}
 // MODE 3: g = dy * ssp'(pre) from the saved output (ya / yb), in place and out for the weight gradient
 template <int KA>
 __device__ __forceinline__ void m2_ssp_bwd_row(float4 (&xa)[KA / 16], float4 (&xb)[KA / 16], const float4 (&ya)[KA / 16], const float4 (&yb)[KA / 16],
@@ -294,7 +189,7 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2(const float *__restrict__ x
 
     // the wave's x rows and (backward) the saved activations are requested before any weight is staged
     float4 xa[SA], xb[SA];
-    m2_load_row<KA>(x, mr, h, xa, xb);
+    row_load<SA>(x, mr, KA, h, xa, xb);
     float4 av[MODE == 1 ? MBA : 1][4];
     if (MODE == 1) {
         const float *ar = aux + (size_t)mr * NA + 4 * h;
@@ -304,11 +199,11 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2(const float *__restrict__ x
             for (int q = 0; q < 4; ++q) av[nb][q] = *reinterpret_cast<const float4 *>(ar + 32 * nb + 8 * q);
     }
     float4 ya[SA], yb[SA];
-    if (MODE == 3) m2_load_row<KA>(aux, mr, h, ya, yb);
-    M2Weight<NA, KA, BWD> stA;
-    M2Weight<NB, NA, BWD> stB;
-    stA.fetch(wA, tid);
-    stB.fetch(wB, tid);                                        // in flight during the first GEMM
+    if (MODE == 3) row_load<SA>(aux, mr, KA, h, ya, yb);
+    M2Planes<NA, KA, BWD> stA;
+    M2Planes<NB, NA, BWD> stB;
+    stA.fetch(wA);
+    stB.fetch(wB);                                             // in flight during the first GEMM
     const float ma = wave_max(stA.absmax()), mb = wave_max(stB.absmax());
     if (lane == 0) { wred[wave] = ma; wred[M2_WAVES + wave] = mb; }
     __syncthreads();
@@ -318,8 +213,8 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2(const float *__restrict__ x
     float scA, scB;
     pow2_scale(a, scA, unA);
     pow2_scale(b, scB, unB);
-    stA.park(WB, tid, false, scA);
-    stB.park(WB2, tid, true, scB);
+    stA.park(WB, scA);
+    stB.park(WB2, scB, [](int k) { return m2_perm4(k); });
     for (int t = tid; t < NA + NB; t += M2_THREADS) BL[t] = BWD ? 0.f : (t < NA ? bA[t] : bB[t - NA]);
     if (MODE == 3) m2_ssp_bwd_row<KA>(xa, xb, ya, yb, in_out, m, h, valid);
     __syncthreads();
@@ -360,15 +255,15 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2_dual(const M2Head ha, const
     float4 xa[NX][SA], xb[NX][SA], ya[NX][SA], yb[NX][SA];
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-        m2_load_row<KA>(hd[i].x, mr, h, xa[i], xb[i]);
-        if (BWD) m2_load_row<KA>(hd[i].aux, mr, h, ya[i], yb[i]);
+        row_load<SA>(hd[i].x, mr, KA, h, xa[i], xb[i]);
+        if (BWD) row_load<SA>(hd[i].aux, mr, KA, h, ya[i], yb[i]);
     }
-    M2Weight<NA, KA, BWD> stA[NH];
-    M2Weight<NB, NA, BWD> stB[NH];
+    M2Planes<NA, KA, BWD> stA[NH];
+    M2Planes<NB, NA, BWD> stB[NH];
 #pragma unroll
     for (int i = 0; i < NH; ++i) {
-        stA[i].fetch(hd[i].wA, tid);
-        stB[i].fetch(hd[i].wB, tid);
+        stA[i].fetch(hd[i].wA);
+        stB[i].fetch(hd[i].wB);
     }
 #pragma unroll
     for (int i = 0; i < NH; ++i) {
@@ -385,8 +280,8 @@ __global__ void __launch_bounds__(M2_THREADS) k_mlp2_dual(const M2Head ha, const
         float scA, scB;
         pow2_scale(a, scA, unA[i]);
         pow2_scale(b, scB, unB[i]);
-        stA[i].park(reinterpret_cast<__bf16 *>(lds + i * WORDS), tid, false, scA);
-        stB[i].park(reinterpret_cast<__bf16 *>(lds + i * WORDS + WORDS_A), tid, true, scB);
+        stA[i].park(lds + i * WORDS, scA);
+        stB[i].park(lds + i * WORDS + WORDS_A, scB, [](int k) { return m2_perm4(k); });
         float *BL = lds + NH * WORDS + i * (NA + NB);
         for (int t = tid; t < NA + NB; t += M2_THREADS) BL[t] = BWD ? 0.f : (t < NA ? hd[i].bA[t] : hd[i].bB[t - NA]);
         if (BWD) m2_ssp_bwd_row<KA>(xa[i], xb[i], ya[i], yb[i], hd[i].in_out, m, h, valid);

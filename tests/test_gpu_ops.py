@@ -778,6 +778,26 @@ def test_linear_wide_layers_are_tiled_into_strided_chunks(M, K, N, act, w_kn):
     assert torch.isnan(y[M:]).all()                                 # rows beyond the device-side count are not touched
 
 
+def test_linear_weight_image_is_the_same_from_both_layouts():
+    """The register-streamed Linear stages W as the same [n][k] plane image whether it is handed over as [N][K] (w_kn = 0) or transposed as
+    [K][N] (w_kn = 1: what the input-gradient GEMMs read): the block maximum does not depend on the order of its operands and everything behind
+    the staging barrier is shared, so y is the same BIT FOR BIT.  One tile, a ragged second tile and more than one workgroup slot, weight
+    maxima far below, below and above the [256, 512) target of the plane scale, and one contraction of two 128-chunks (k_linear_sum16)."""
+    from conan_fgw_amd._lib import call, ptr, stream_ptr
+    gen = torch.Generator().manual_seed(11)
+    cases = [(K, N, M, wmag) for K, N in [(128, 128), (64, 128), (128, 64), (64, 64)] for M in (1, 33, 2049) for wmag in (1e-4, 0.2, 300.0)]
+    for K, N, M, wmag in cases + [(256, 128, 2049, 0.2)]:
+        x = torch.randn(M, K, generator=gen).to(dev)
+        w = (torch.randn(N, K, generator=gen) * wmag).to(dev)
+        b = torch.randn(N, generator=gen).to(dev)
+        ys = []
+        for w_kn, wl in ((0, w), (1, w.t().contiguous())):
+            y = torch.full((M, N), float("nan"), device=dev)
+            call("conan_linear_fwd", ptr(x), ptr(wl), ptr(b), None, M, K, N, w_kn, 0, None, ptr(y), stream_ptr())
+            ys.append(y)
+        assert torch.isfinite(ys[0]).all() and torch.equal(ys[0], ys[1]), (K, N, M, wmag)
+
+
 @pytest.mark.parametrize("M,nsrc,w_kn,mags", [(1, 2, 1, (1.0, 1.0)), (33, 3, 1, (1.0, 1.0, 1.0)), (5000, 3, 1, (1.0e-6, 3.0, 1.0e-3)), (2049, 2, 0, (1.0e4, 1.0e-4)),
                                               (70000, 3, 1, (1.0, 0.0, 1.0e-9)), (300, 3, 0, (0.0, 0.0, 0.0))])
 def test_sum_of_contractions_in_one_launch_matches_fp64_chunk_by_chunk(M, nsrc, w_kn, mags):
