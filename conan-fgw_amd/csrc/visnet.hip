@@ -36,36 +36,22 @@ __global__ void k_expnormal(const float *__restrict__ dist, const int *__restric
 
 // The three element-wise edge kernels below walk runs of V_RUN consecutive edges per wavefront (round 3; were one thread per element with a
 // 64-bit division, the index loads and — in k_ne_scale — a full-precision cosine per ELEMENT): per-edge quantities are formed once, one edge
-// per lane, and handed out; lane <-> CPL channels; V_EB edges in flight.
+// per lane, and handed out; lane <-> CPL channels; V_EB edges in flight (walk_runs, visnet_common.h).
 // W[e,:] *= C(r_e) * [src != tgt]      (NeighborEmbedding, :408-415: loops removed, cosine cutoff)
 template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_ne_scale(const float *Win, float *W, const float *__restrict__ dist, const int *__restrict__ col,
                                                   const int *__restrict__ tgt, const int *__restrict__ ne_dev, int max_edges, int H, float cutoff) {
-    const int E = min(*ne_dev, max_edges);
-    const int lane = threadIdx.x & 63;
-    const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
-    constexpr int ES = HALF ? 2 : 1;
-    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int base = wave * V_RUN; base < E; base += nw * V_RUN) {
-        const int cnt = min(V_RUN, E - base);
-        const float my_s = (lane < cnt && col[base + lane] != tgt[base + lane]) ? cos_cutoff(dist[base + lane], cutoff) : 0.0f;
-        for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
-            const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
-            for (int tq = 0; tq < cnt; tq += ES * V_EB) {
-                float w[V_EB][CPL];
+    const EdgeLanes<CPL, HALF> L;
+    struct S { float sc; };
+    struct R { float w[CPL]; };
+    walk_runs(L, min(*ne_dev, max_edges), H,
+        [&](int e) { return S{col[e] != tgt[e] ? cos_cutoff(dist[e], cutoff) : 0.0f}; },
+        [&](Chan c, size_t e, S) { R r; vld<CPL>(Win + e * H + c.cl, r.w); return r; },
+        [&](Chan c, size_t e, S s, R &r) {
 #pragma unroll
-                for (int b = 0; b < V_EB; ++b) vld<CPL>(Win + (size_t)(base + min(tq + ES * b + hf, cnt - 1)) * H + cl, w[b]);
-#pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    const float sc = __shfl(my_s, min(tq + ES * b + hf, cnt - 1), 64);      // before the halves diverge
-                    if (tq + ES * b + hf >= cnt) continue;
-#pragma unroll
-                    for (int u = 0; u < CPL; ++u) w[b][u] *= sc;
-                    if (on) vst<CPL>(W + (size_t)(base + tq + ES * b + hf) * H + c0, w[b]);
-                }
-            }
-        }
-    }
+            for (int u = 0; u < CPL; ++u) r.w[u] *= s.sc;
+            if (c.on) vst<CPL>(W + e * H + c.c0, r.w);
+        });
 }
 
 __global__ void k_concat2(const float *__restrict__ a, int Ha, const float *__restrict__ b, int Hb, long long rows, float *__restrict__ out) {
@@ -164,61 +150,45 @@ __global__ void k_vecdot(const float *__restrict__ vp, int n, int H, float *__re
 // One wavefront per target; lane l owns CPL consecutive channels; a head spans LPH lanes (xor-shuffle reduction).
 // Round 3: a row's col[] / dist[] entries are fetched once, one edge per lane, and handed out with cross-lane reads (a wave-uniform
 // index becomes a scalar register: row base in SGPRs, lane offset in a VGPR), and the rows of EB edges are requested before the first
-// of them is used — the loop was a chain of two dependent round trips per edge (index, then the k_j / v_j rows) and ran at 2.3 TB/s.
-// The sums run in edge order as before (bitwise-equal results).
+// of them is used (walk_row) — the loop was a chain of two dependent round trips per edge (index, then the k_j / v_j rows) and ran at 2.3 TB/s.
 template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_attn_msg(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
                                                   const float *__restrict__ dk, const float *__restrict__ dv, const int *__restrict__ rowptr,
                                                   const int *__restrict__ col, const float *__restrict__ dist, float cutoff, int n, int H,
                                                   int lph, int pre, float *__restrict__ vmsg, float *__restrict__ xagg) {
-    const int lane = threadIdx.x & 63;
-    const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
-    constexpr int ES = HALF ? 2 : 1;
-    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    const int c0 = (int)blockIdx.y * (HALF ? 32 : 64) * CPL + ll * CPL;      // blockIdx.y: block of 64 CPL (HALF: 32 CPL) channels — whole heads (H > 128)
-    const bool on = c0 < H;
-    const int cl = on ? c0 : 0;                                       // idle lanes (H < 64 CPL) read column 0 and store nothing
-    for (int i = wave; i < n; i += nw) {
+    const EdgeLanes<CPL, HALF> L;
+    const Chan c = chan_pass(L, (int)blockIdx.y * L.SPAN, H);      // blockIdx.y: block of 64 CPL (HALF: 32 CPL) channels — whole heads (H > 128)
+    struct S { int j; float cut; };
+    struct R { float kj[CPL], vj[CPL], dke[CPL], dve[CPL]; };
+    for (int i = L.wave; i < n; i += L.nw) {
         float qi[CPL], acc[CPL];
 #pragma unroll
-        for (int u = 0; u < CPL; ++u) { qi[u] = q[(size_t)i * H + cl + u]; acc[u] = 0.f; }
-        const int e0 = rowptr[i], e1 = rowptr[i + 1];
-        for (int base = e0; base < e1; base += 64) {
-            const int cnt = min(64, e1 - base);
-            const int my_j = lane < cnt ? col[base + lane] : 0;
-            const float my_c = lane < cnt ? cos_cutoff(dist[base + lane], cutoff) : 0.f;
-            for (int t = 0; t < cnt; t += ES * V_EB) {
-                float kj[V_EB][CPL], vj[V_EB][CPL], dke[V_EB][CPL], dve[V_EB][CPL];
+        for (int u = 0; u < CPL; ++u) { qi[u] = q[(size_t)i * H + c.cl + u]; acc[u] = 0.f; }
+        walk_row(L, rowptr, i,
+            [&](int e) { return S{col[e], cos_cutoff(dist[e], cutoff)}; },
+            [&](size_t e, S s) {
+                R r;
+                vld<CPL>(k + (size_t)s.j * H + c.cl, r.kj); vld<CPL>(v + (size_t)s.j * H + c.cl, r.vj);
+                vld<CPL>(dk + e * H + c.cl, r.dke); vld<CPL>(dv + e * H + c.cl, r.dve);
+                return r;
+            },
+            [&](size_t e, S s, R &r) {
+                float part = 0.f;
 #pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    const int tt = min(t + ES * b + hf, cnt - 1);                  // slots past the row repeat its last edge (not used)
-                    const int j = __shfl(my_j, tt, 64);
-                    const size_t e = (size_t)(base + tt);
-                    vld<CPL>(k + (size_t)j * H + cl, kj[b]); vld<CPL>(v + (size_t)j * H + cl, vj[b]);
-                    vld<CPL>(dk + e * H + cl, dke[b]); vld<CPL>(dv + e * H + cl, dve[b]);
+                for (int u = 0; u < CPL; ++u) {
+                    if (pre) { r.dke[u] = silu_f(r.dke[u]); r.dve[u] = silu_f(r.dve[u]); }      // dk / dv arrive as the projections' pre-activations
+                    part += qi[u] * r.kj[u] * r.dke[u];
                 }
+                if (!c.on) part = 0.f;
+                for (int o = 1; o < lph; o <<= 1) part += __shfl_xor(part, o, 64);
+                const float attn = silu_f(part) * s.cut;
+                float m[CPL];
 #pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    const float cutb = __shfl(my_c, min(t + ES * b + hf, cnt - 1), 64);      // before the halves diverge
-                    if (t + ES * b + hf >= cnt) continue;
-                    float part = 0.f;
-#pragma unroll
-                    for (int u = 0; u < CPL; ++u) {
-                        if (pre) { dke[b][u] = silu_f(dke[b][u]); dve[b][u] = silu_f(dve[b][u]); }      // dk / dv arrive as the projections' pre-activations
-                        part += qi[u] * kj[b][u] * dke[b][u];
-                    }
-                    if (!on) part = 0.f;
-                    for (int o = 1; o < lph; o <<= 1) part += __shfl_xor(part, o, 64);
-                    const float attn = silu_f(part) * cutb;
-                    float m[CPL];
-#pragma unroll
-                    for (int u = 0; u < CPL; ++u) { m[u] = vj[b][u] * dve[b][u] * attn; acc[u] += m[u]; }
-                    if (on) vst<CPL>(vmsg + (size_t)(base + t + ES * b + hf) * H + c0, m);
-                }
-            }
-        }
+                for (int u = 0; u < CPL; ++u) { m[u] = r.vj[u] * r.dve[u] * attn; acc[u] += m[u]; }
+                if (c.on) vst<CPL>(vmsg + e * H + c.c0, m);
+            });
         vfold<CPL, HALF>(acc);
-        if (on && hf == 0) vst<CPL>(xagg + (size_t)i * H + c0, acc);
+        if (c.on && L.hf == 0) vst<CPL>(xagg + (size_t)i * H + c.c0, acc);
     }
 }
 
@@ -319,7 +289,7 @@ __global__ void k_node_update(const float *__restrict__ x, const float *__restri
 // wt = w_trg_proj(vec), ws = w_src_proj(vec) are node-level [n,3,H]; t = SiLU(f_proj(f_ij)) [E,H]
 // One wavefront per run of V_RUN consecutive edges (round 3; was one thread per element: a 64-bit division, two index loads and six gathered
 // rows per ELEMENT, each waiting for its index): sources, targets and unit vectors of the run are fetched once, one edge per lane, and
-// handed out; lane <-> CPL channels; V_EB edges in flight (consecutive edges share their target: its rows are L1 hits).
+// handed out (walk_runs); lane <-> CPL channels; V_EB edges in flight (consecutive edges share their target: its rows are L1 hits).
 template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_edge_update(const float *__restrict__ wt, const float *__restrict__ ws, const float *__restrict__ t,
                                                      const float *__restrict__ dvec, const int *__restrict__ col, const int *__restrict__ tgt,
@@ -419,9 +389,9 @@ int conan_visnet_neighbor_scale_to(const float *W, const float *dist, const int 
                                    float cutoff, float *out, void *stream) {
     V_CHECK(W && out && dist && col && tgt && num_edges_dev && H > 0);
     if (max_edges <= 0) return CONAN_OK;
-    if (H == 128 && V_HALF) k_ne_scale<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
-    else if (H % 128 == 0) k_ne_scale<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
-    else k_ne_scale<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
+    with_width(H, [&](auto cpl, auto half) {
+        k_ne_scale<cpl(), half()><<<edge_grid(max_edges), 256, 0, as_stream(stream)>>>(W, out, dist, col, tgt, num_edges_dev, max_edges, H, cutoff);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_neighbor_scale(float *W, const float *dist, const int *col, const int *tgt, const int *num_edges_dev, int max_edges, int H,
@@ -436,9 +406,9 @@ int conan_concat2(const float *a, int Ha, const float *b, int Hb, long long rows
 int conan_visnet_edge_embed(const float *x, const float *p, const int *col, const int *tgt, const int *num_edges_dev, int max_edges, int H,
                             float *f, void *stream) {
     V_CHECK(x && p && col && tgt && num_edges_dev && f && H > 0);
-    if (H == 128 && V_HALF) k_edge_embed<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
-    else if (H % 128 == 0) k_edge_embed<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
-    else k_edge_embed<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
+    with_width(H, [&](auto cpl, auto half) {
+        k_edge_embed<cpl(), half()><<<edge_grid(max_edges), 256, 0, as_stream(stream)>>>(x, p, col, tgt, num_edges_dev, max_edges, H, f);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_layernorm_fwd(const float *x, const float *gamma, const float *beta, int rows, int H, float eps, float *out, void *stream) {
@@ -473,29 +443,23 @@ int conan_visnet_attn_message(const float *q, const float *k, const float *v, co
                               const int *col, const float *dist, float cutoff, int n, int H, int num_heads, int pre_act, float *vmsg,
                               float *xagg, void *stream) {
     V_CHECK(q && k && v && dk && dv && rowptr && col && dist && vmsg && xagg && n >= 0 && H > 0 && num_heads > 0 && H % num_heads == 0);
-    const int hd = H / num_heads;
-    // H a multiple of 128 (the classification backbone's 512, common.py:444-446): blocks of 128 channels on blockIdx.y, each a half-wavefront
-    // per edge — heads must not straddle a block (hd divides 128) and span a power-of-two number of 4-channel lanes
-    const bool blocks128 = H % 128 == 0 && V_HALF && hd % 4 == 0 && (((hd / 4) & (hd / 4 - 1)) == 0) && 128 % hd == 0;
-    const int cpl = H > 64 ? (H + 63) / 64 : 1;
-    if (!blocks128 && (H > 128 || (H > 64 && H != 128) || hd % cpl != 0)) return CONAN_E_UNSUPPORTED;
-    const int lph = blocks128 ? hd / 4 : hd / cpl;
-    if (lph & (lph - 1)) return CONAN_E_UNSUPPORTED;
+    const AttnShape a = attn_shape(H, num_heads);
+    if (a.rc != CONAN_OK) return a.rc;
     if (n == 0) return CONAN_OK;
-    if (blocks128)
-        k_attn_msg<4, true><<<dim3(nblk((long long)n * 64), H / 128), 256, 0, as_stream(stream)>>>(q, k, v, dk, dv, rowptr, col, dist, cutoff, n, H, hd / 4, pre_act, vmsg, xagg);
-    else if (cpl == 2) k_attn_msg<2><<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(q, k, v, dk, dv, rowptr, col, dist, cutoff, n, H, lph, pre_act, vmsg, xagg);
-    else k_attn_msg<1><<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(q, k, v, dk, dv, rowptr, col, dist, cutoff, n, H, lph, pre_act, vmsg, xagg);
+    with_attn_width(a, n, H, [&](auto cpl, auto half, dim3 grid) {
+        k_attn_msg<cpl(), half()><<<grid, 256, 0, as_stream(stream)>>>(q, k, v, dk, dv, rowptr, col, dist, cutoff, n, H, a.lph, pre_act, vmsg, xagg);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_vec_aggregate(const float *vec, const float *s, const float *dvec, const int *rowptr, const int *col, int n, int H,
                                int pre_act, float *vagg, void *stream) {
     V_CHECK(vec && s && dvec && rowptr && col && vagg && n >= 0 && H > 0);
     if (n == 0) return CONAN_OK;
-    if (H == 128 && V_HALF) k_vec_aggregate<4, true><<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
-    else if (H == 128) k_vec_aggregate<2><<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
-    else if (H == 64) k_vec_aggregate<1><<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
-    else k_vec_aggregate_any<<<nblk((long long)n * 64), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
+    if (H == 128 || H == 64)      // a whole row per pass: <4,true> (<2> without V_HALF) at 128, <1> at 64
+        with_width(H, [&](auto cpl, auto half) {
+            k_vec_aggregate<cpl(), half()><<<node_grid(n), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
+        });
+    else k_vec_aggregate_any<<<node_grid(n), 256, 0, as_stream(stream)>>>(vec, s, dvec, rowptr, col, n, H, pre_act, vagg);
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_node_update(const float *x, const float *vec, const float *vdot, const float *o, const float *vp, const float *vagg, int n,
@@ -507,9 +471,9 @@ int conan_visnet_node_update(const float *x, const float *vec, const float *vdot
 int conan_visnet_edge_update(const float *wt, const float *ws, const float *t, const float *dvec, const int *col, const int *tgt,
                              const int *num_edges_dev, int max_edges, int H, int pre_act, const float *f, float *f_out, void *stream) {
     V_CHECK(wt && ws && t && dvec && col && tgt && num_edges_dev && f && f_out && H > 0);
-    if (H == 128 && V_HALF) k_edge_update<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
-    else if (H % 128 == 0) k_edge_update<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
-    else k_edge_update<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
+    with_width(H, [&](auto cpl, auto half) {
+        k_edge_update<cpl(), half()><<<edge_grid(max_edges), 256, 0, as_stream(stream)>>>(wt, ws, t, dvec, col, tgt, num_edges_dev, max_edges, H, pre_act, f, f_out);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_spatial_norm(const float *v, int n, int H, float *out, void *stream) {

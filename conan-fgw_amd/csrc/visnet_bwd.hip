@@ -77,49 +77,24 @@ template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_edge_embed_bwd_x(const float *__restrict__ p, const float *__restrict__ df, const int *__restrict__ rowptr,
                                                           const int *__restrict__ t_rowptr, const int *__restrict__ t_eid, int n, int H,
                                                           float *__restrict__ dx) {
-    const int lane = threadIdx.x & 63;
-    const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
-    constexpr int ES = HALF ? 2 : 1;
-    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int i = wave; i < n; i += nw)
-        for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
-            const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
+    const EdgeLanes<CPL, HALF> L;
+    struct R { float g[CPL], q[CPL]; };
+    for (int i = L.wave; i < n; i += L.nw)
+        for (int cp = 0; cp < H; cp += L.SPAN) {
+            const Chan c = chan_pass(L, cp, H);
             float a[CPL];
 #pragma unroll
             for (int u = 0; u < CPL; ++u) a[u] = 0.f;
-            const int e0 = rowptr[i], e1 = rowptr[i + 1];
-            for (int e = e0; e < e1; e += ES * V_EB) {                             // the row itself: consecutive edges, no indices
-                float g[V_EB][CPL], q[V_EB][CPL];
+            const auto stage = [](int) { return NoStage{}; };
+            const auto load = [&](size_t e, NoStage) { R r; vld<CPL>(df + e * H + c.cl, r.g); vld<CPL>(p + e * H + c.cl, r.q); return r; };
+            const auto use = [&](size_t, NoStage, R &r) {
 #pragma unroll
-                for (int b = 0; b < V_EB; ++b) { const size_t ee = (size_t)min(e + ES * b + hf, e1 - 1); vld<CPL>(df + ee * H + cl, g[b]); vld<CPL>(p + ee * H + cl, q[b]); }
-#pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    if (e + ES * b + hf >= e1) continue;
-#pragma unroll
-                    for (int u = 0; u < CPL; ++u) a[u] += g[b][u] * q[b][u];
-                }
-            }
-            const int s0 = t_rowptr[i], s1 = t_rowptr[i + 1];
-            for (int base = s0; base < s1; base += 64) {                            // the by-source list: edge ids handed out per lane
-                const int cnt = min(64, s1 - base);
-                const int my_e = lane < cnt ? t_eid[base + lane] : 0;
-                for (int tq = 0; tq < cnt; tq += ES * V_EB) {
-                    float g[V_EB][CPL], q[V_EB][CPL];
-#pragma unroll
-                    for (int b = 0; b < V_EB; ++b) {
-                        const size_t ee = (size_t)__shfl(my_e, min(tq + ES * b + hf, cnt - 1), 64);
-                        vld<CPL>(df + ee * H + cl, g[b]); vld<CPL>(p + ee * H + cl, q[b]);
-                    }
-#pragma unroll
-                    for (int b = 0; b < V_EB; ++b) {
-                        if (tq + ES * b + hf >= cnt) continue;
-#pragma unroll
-                        for (int u = 0; u < CPL; ++u) a[u] += g[b][u] * q[b][u];
-                    }
-                }
-            }
+                for (int u = 0; u < CPL; ++u) a[u] += r.g[u] * r.q[u];
+            };
+            walk_row(L, rowptr, i, stage, load, use);                    // the row itself, then the by-source list: one sum
+            walk_sources(L, t_rowptr, t_eid, i, stage, load, use);
             vfold<CPL, HALF>(a);
-            if (on && hf == 0) vst<CPL>(dx + (size_t)i * H + c0, a);
+            if (c.on && L.hf == 0) vst<CPL>(dx + (size_t)i * H + c.c0, a);
         }
 }
 
@@ -210,9 +185,8 @@ __device__ __forceinline__ void attn_edge(const float *qi, const float *kj, cons
     da = t1 * cut * (sg * (1.0f + part * (1.0f - sg)));        // d attn * C * SiLU'(a)
 }
 
-// Round 3 (all row-walking kernels below): a row's indices (and what hangs off them per edge: target, cutoff, unit vector) are fetched once,
-// one edge per lane, and handed out with cross-lane reads; the rows of V_EB edges are requested before the first is used.  The loops were
-// chains of two or three dependent round trips per edge (2.3-3 TB/s); the sums still run in list order (bitwise-equal results).
+// Round 3 (all row-walking kernels below): walk_row / walk_sources of visnet_common.h, or the kernel's own copy of that skeleton (listed there).
+// The loops were chains of two or three dependent round trips per edge (2.3-3 TB/s).
 
 // target side: dq[i] (sum over row i), and the edge gradients d dk[e], d dv[e]
 template <int CPL, bool HALF = false>
@@ -283,51 +257,36 @@ __global__ void __launch_bounds__(256) k_attn_bwd_source(const float *__restrict
                                                          const float *__restrict__ dxagg, const int *__restrict__ t_rowptr, const int *__restrict__ t_eid,
                                                          const int *__restrict__ tgt, const float *__restrict__ dist, float cutoff, int n, int H, int lph,
                                                          int pre, float *__restrict__ dkn, float *__restrict__ dvn) {
-    const int lane = threadIdx.x & 63;
-    const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
-    constexpr int ES = HALF ? 2 : 1;
-    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    const int c0 = (int)blockIdx.y * (HALF ? 32 : 64) * CPL + ll * CPL;
-    const bool on = c0 < H;
-    const int cl = on ? c0 : 0;
-    for (int j = wave; j < n; j += nw) {
+    const EdgeLanes<CPL, HALF> L;
+    const Chan c = chan_pass(L, (int)blockIdx.y * L.SPAN, H);
+    struct S { int i; float cut; };
+    struct R { float qi[CPL], dke[CPL], dve[CPL], dm[CPL], gx[CPL]; };
+    for (int j = L.wave; j < n; j += L.nw) {
         float kj[CPL], vj[CPL], ak[CPL], av[CPL];
 #pragma unroll
-        for (int u = 0; u < CPL; ++u) { kj[u] = on ? k[(size_t)j * H + cl + u] : 0.f; vj[u] = on ? v[(size_t)j * H + cl + u] : 0.f; ak[u] = 0.f; av[u] = 0.f; }
-        const int s0 = t_rowptr[j], s1 = t_rowptr[j + 1];
-        for (int base = s0; base < s1; base += 64) {
-            const int cnt = min(64, s1 - base);
-            const int my_e = lane < cnt ? t_eid[base + lane] : 0;
-            const int my_i = lane < cnt ? tgt[my_e] : 0;
-            const float my_c = lane < cnt ? cos_cutoff(dist[my_e], cutoff) : 0.f;
-            for (int t = 0; t < cnt; t += ES * V_EB) {
-                float qi[V_EB][CPL], dke[V_EB][CPL], dve[V_EB][CPL], dm[V_EB][CPL], gx[V_EB][CPL];
+        for (int u = 0; u < CPL; ++u) { kj[u] = c.on ? k[(size_t)j * H + c.cl + u] : 0.f; vj[u] = c.on ? v[(size_t)j * H + c.cl + u] : 0.f; ak[u] = 0.f; av[u] = 0.f; }
+        walk_sources(L, t_rowptr, t_eid, j,
+            [&](int e) { return S{tgt[e], cos_cutoff(dist[e], cutoff)}; },
+            [&](size_t e, S s) {
+                R r;
+                vld<CPL>(q + (size_t)s.i * H + c.cl, r.qi); vld<CPL>(dxagg + (size_t)s.i * H + c.cl, r.gx);
+                vld<CPL>(dk + e * H + c.cl, r.dke); vld<CPL>(dv + e * H + c.cl, r.dve); vld<CPL>(dvmsg + e * H + c.cl, r.dm);
+                return r;
+            },
+            [&](size_t, S s, R &r) {
 #pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    const int tt = min(t + ES * b + hf, cnt - 1);
-                    const size_t e = (size_t)__shfl(my_e, tt, 64), i = (size_t)__shfl(my_i, tt, 64);
-                    vld<CPL>(q + i * H + cl, qi[b]); vld<CPL>(dxagg + i * H + cl, gx[b]);
-                    vld<CPL>(dk + e * H + cl, dke[b]); vld<CPL>(dv + e * H + cl, dve[b]); vld<CPL>(dvmsg + e * H + cl, dm[b]);
+                for (int u = 0; u < CPL; ++u) {
+                    if (pre) { r.dke[u] = silu_f(r.dke[u]); r.dve[u] = silu_f(r.dve[u]); }
+                    r.dm[u] = c.on ? r.dm[u] + r.gx[u] : 0.f;
+                    if (!c.on) { r.qi[u] = 0.f; r.dke[u] = 0.f; r.dve[u] = 0.f; }
                 }
+                float attn, da;
+                attn_edge<CPL>(r.qi, kj, vj, r.dke, r.dve, r.dm, s.cut, lph, attn, da);
 #pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    const float cutb = __shfl(my_c, min(t + ES * b + hf, cnt - 1), 64);      // before the halves diverge
-                    if (t + ES * b + hf >= cnt) continue;
-#pragma unroll
-                    for (int u = 0; u < CPL; ++u) {
-                        if (pre) { dke[b][u] = silu_f(dke[b][u]); dve[b][u] = silu_f(dve[b][u]); }
-                        dm[b][u] = on ? dm[b][u] + gx[b][u] : 0.f;
-                        if (!on) { qi[b][u] = 0.f; dke[b][u] = 0.f; dve[b][u] = 0.f; }
-                    }
-                    float attn, da;
-                    attn_edge<CPL>(qi[b], kj, vj, dke[b], dve[b], dm[b], cutb, lph, attn, da);
-#pragma unroll
-                    for (int u = 0; u < CPL; ++u) { ak[u] += da * qi[b][u] * dke[b][u]; av[u] += dm[b][u] * dve[b][u] * attn; }
-                }
-            }
-        }
+                for (int u = 0; u < CPL; ++u) { ak[u] += da * r.qi[u] * r.dke[u]; av[u] += r.dm[u] * r.dve[u] * attn; }
+            });
         vfold<CPL, HALF>(ak); vfold<CPL, HALF>(av);
-        if (on && hf == 0) { vst<CPL>(dkn + (size_t)j * H + c0, ak); vst<CPL>(dvn + (size_t)j * H + c0, av); }
+        if (c.on && L.hf == 0) { vst<CPL>(dkn + (size_t)j * H + c.c0, ak); vst<CPL>(dvn + (size_t)j * H + c.c0, av); }
     }
 }
 
@@ -337,52 +296,35 @@ template <int CPL, bool HALF = false>
 __global__ void __launch_bounds__(256) k_vec_aggregate_bwd_s(const float *__restrict__ vec, const float *__restrict__ dvagg, const float *__restrict__ dvec3,
                                                              const int *__restrict__ col, const int *__restrict__ tgt, const int *__restrict__ ne_dev,
                                                              int max_edges, int H, const float *__restrict__ s_pre, float *__restrict__ ds) {
-    // one wavefront per run of V_RUN consecutive edges, indices and unit vectors handed out per lane, V_EB edges in flight (see k_edge_update)
-    const int E = min(*ne_dev, max_edges);
-    const int lane = threadIdx.x & 63;
-    const int hf = HALF ? lane >> 5 : 0, ll = HALF ? (lane & 31) : lane;      // HALF: a half-wavefront per edge (H = 32 CPL), two edges per step
-    constexpr int ES = HALF ? 2 : 1;
-    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)), nw = (gridDim.x * blockDim.x) >> 6;
-    for (int base = wave * V_RUN; base < E; base += nw * V_RUN) {
-        const int cnt = min(V_RUN, E - base);
-        const int my_j = lane < cnt ? col[base + lane] : 0, my_i = lane < cnt ? tgt[base + lane] : 0;
-        float my_d[3];
+    // one wavefront per run of V_RUN consecutive edges (see k_edge_update)
+    const EdgeLanes<CPL, HALF> L;
+    struct S { int j, i; Vec3 d; };
+    struct R { float g[3][CPL], vj[3][CPL], p1[CPL], p2[CPL]; };
+    walk_runs(L, min(*ne_dev, max_edges), H,
+        [&](int e) { return S{col[e], tgt[e], ld_vec3(dvec3, e)}; },
+        [&](Chan c, size_t e, S s) {
+            R r;
 #pragma unroll
-        for (int sp = 0; sp < 3; ++sp) my_d[sp] = lane < cnt ? dvec3[(size_t)(base + lane) * 3 + sp] : 0.f;
-        for (int cp = 0; cp < H; cp += (HALF ? 32 : 64) * CPL) {
-            const int c0 = cp + ll * CPL; const bool on = c0 < H; const int cl = on ? c0 : 0;
-            for (int tq = 0; tq < cnt; tq += ES * V_EB) {
-                float g[V_EB][3][CPL], vj[V_EB][3][CPL], p1[V_EB][CPL], p2[V_EB][CPL];
+            for (int sp = 0; sp < 3; ++sp) { vld<CPL>(dvagg + ((size_t)s.i * 3 + sp) * H + c.cl, r.g[sp]); vld<CPL>(vec + ((size_t)s.j * 3 + sp) * H + c.cl, r.vj[sp]); }
+            if (s_pre) { vld<CPL>(s_pre + e * 2 * H + c.cl, r.p1); vld<CPL>(s_pre + e * 2 * H + H + c.cl, r.p2); }
+            else {
 #pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    const int tt = min(tq + ES * b + hf, cnt - 1);
-                    const size_t j = (size_t)__shfl(my_j, tt, 64), i = (size_t)__shfl(my_i, tt, 64), e = (size_t)(base + tt);
-#pragma unroll
-                    for (int sp = 0; sp < 3; ++sp) { vld<CPL>(dvagg + (i * 3 + sp) * H + cl, g[b][sp]); vld<CPL>(vec + (j * 3 + sp) * H + cl, vj[b][sp]); }
-                    if (s_pre) { vld<CPL>(s_pre + e * 2 * H + cl, p1[b]); vld<CPL>(s_pre + e * 2 * H + H + cl, p2[b]); }
-                    else {
-#pragma unroll
-                        for (int u = 0; u < CPL; ++u) { p1[b][u] = 0.f; p2[b][u] = 0.f; }
-                    }
-                }
-#pragma unroll
-                for (int b = 0; b < V_EB; ++b) {
-                    const float d0 = __shfl(my_d[0], min(tq + ES * b + hf, cnt - 1), 64), d1 = __shfl(my_d[1], min(tq + ES * b + hf, cnt - 1), 64), d2 = __shfl(my_d[2], min(tq + ES * b + hf, cnt - 1), 64);      // before the halves diverge
-                    if (tq + ES * b + hf >= cnt) continue;
-                    const size_t e = (size_t)(base + tq + ES * b + hf);
-                    float r1[CPL], r2[CPL];
-#pragma unroll
-                    for (int u = 0; u < CPL; ++u) {
-                        const float g0 = g[b][0][u], g1 = g[b][1][u], g2 = g[b][2][u];
-                        r1[u] = g0 * vj[b][0][u] + g1 * vj[b][1][u] + g2 * vj[b][2][u];
-                        r2[u] = g0 * d0 + g1 * d1 + g2 * d2;
-                        if (s_pre) { r1[u] *= dsilu_f(p1[b][u]); r2[u] *= dsilu_f(p2[b][u]); }   // gradient w.r.t. the pre-activation
-                    }
-                    if (on) { vst<CPL>(ds + e * 2 * H + c0, r1); vst<CPL>(ds + e * 2 * H + H + c0, r2); }
-                }
+                for (int u = 0; u < CPL; ++u) { r.p1[u] = 0.f; r.p2[u] = 0.f; }
             }
-        }
-    }
+            return r;
+        },
+        [&](Chan c, size_t e, S s, R &r) {
+            const float d0 = s.d.x, d1 = s.d.y, d2 = s.d.z;
+            float r1[CPL], r2[CPL];
+#pragma unroll
+            for (int u = 0; u < CPL; ++u) {
+                const float g0 = r.g[0][u], g1 = r.g[1][u], g2 = r.g[2][u];
+                r1[u] = g0 * r.vj[0][u] + g1 * r.vj[1][u] + g2 * r.vj[2][u];
+                r2[u] = g0 * d0 + g1 * d1 + g2 * d2;
+                if (s_pre) { r1[u] *= dsilu_f(r.p1[u]); r2[u] *= dsilu_f(r.p2[u]); }   // gradient w.r.t. the pre-activation
+            }
+            if (c.on) { vst<CPL>(ds + e * 2 * H + c.c0, r1); vst<CPL>(ds + e * 2 * H + H + c.c0, r2); }
+        });
 }
 // dvec[j,sp] = sum_{e in srclist(j)} dvagg[tgt_e,sp] * s1_e
 template <int CPL, bool HALF = false>
@@ -648,15 +590,10 @@ int conan_visnet_edge_embed_bwd(const float *x, const float *p, const float *df,
                                 float *dx, void *stream) {
     V_CHECK(x && p && df && rowptr && col && tgt && t_rowptr && t_eid && num_edges_dev && dp && dx && H > 0);
     hipStream_t s = as_stream(stream);
-    if (H % 128 == 0) {
-        if (H == 128 && V_HALF) k_edge_embed_bwd_p<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
-        else k_edge_embed_bwd_p<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
-        if (H == 128 && V_HALF) k_edge_embed_bwd_x<4, true><<<nblk((long long)n * 64), 256, 0, s>>>(p, df, rowptr, t_rowptr, t_eid, n, H, dx);
-        else k_edge_embed_bwd_x<2><<<nblk((long long)n * 64), 256, 0, s>>>(p, df, rowptr, t_rowptr, t_eid, n, H, dx);
-    } else {
-        k_edge_embed_bwd_p<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
-        k_edge_embed_bwd_x<1><<<nblk((long long)n * 64), 256, 0, s>>>(p, df, rowptr, t_rowptr, t_eid, n, H, dx);
-    }
+    with_width(H, [&](auto cpl, auto half) {
+        k_edge_embed_bwd_p<cpl(), half()><<<edge_grid(max_edges), 256, 0, s>>>(x, df, col, tgt, num_edges_dev, max_edges, H, dp);
+        k_edge_embed_bwd_x<cpl(), half()><<<node_grid(n), 256, 0, s>>>(p, df, rowptr, t_rowptr, t_eid, n, H, dx);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 long long conan_layernorm_bwd_ws(int rows, int H) { return 2LL * rows + 2LL * ((rows + LN_CHUNK - 1) / LN_CHUNK) * H; }
@@ -695,25 +632,14 @@ int conan_visnet_attn_message_bwd(const float *q, const float *k, const float *v
                                   float *dkn, float *dvn, float *ddk, float *ddv, void *stream) {
     V_CHECK(q && k && v && dk && dv && dvmsg && dxagg && rowptr && col && tgt && t_rowptr && t_eid && dist && dq && dkn && dvn && ddk && ddv);
     V_CHECK(n >= 0 && H > 0 && num_heads > 0 && H % num_heads == 0);
-    const int hd = H / num_heads, cpl = H > 64 ? (H + 63) / 64 : 1;
-    const bool blocks128 = H % 128 == 0 && V_HALF && hd % 4 == 0 && (((hd / 4) & (hd / 4 - 1)) == 0) && 128 % hd == 0;      // as conan_visnet_attn_message
-    if (!blocks128 && (H > 128 || (H > 64 && H != 128) || hd % cpl != 0)) return CONAN_E_UNSUPPORTED;
-    const int lph = blocks128 ? hd / 4 : hd / cpl;
-    if (lph & (lph - 1)) return CONAN_E_UNSUPPORTED;
+    const AttnShape a = attn_shape(H, num_heads);
+    if (a.rc != CONAN_OK) return a.rc;
     if (n == 0) return CONAN_OK;
     hipStream_t s = as_stream(stream);
-    const int g = nblk((long long)n * 64);
-    if (blocks128) {
-        const dim3 gb(g, H / 128);
-        k_attn_bwd_target<4, true><<<gb, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, rowptr, col, dist, cutoff, n, H, hd / 4, pre_act, dq, ddk, ddv);
-        k_attn_bwd_source<4, true><<<gb, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, t_rowptr, t_eid, tgt, dist, cutoff, n, H, hd / 4, pre_act, dkn, dvn);
-    } else if (cpl == 2) {
-        k_attn_bwd_target<2><<<g, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, rowptr, col, dist, cutoff, n, H, lph, pre_act, dq, ddk, ddv);
-        k_attn_bwd_source<2><<<g, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, t_rowptr, t_eid, tgt, dist, cutoff, n, H, lph, pre_act, dkn, dvn);
-    } else {
-        k_attn_bwd_target<1><<<g, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, rowptr, col, dist, cutoff, n, H, lph, pre_act, dq, ddk, ddv);
-        k_attn_bwd_source<1><<<g, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, t_rowptr, t_eid, tgt, dist, cutoff, n, H, lph, pre_act, dkn, dvn);
-    }
+    with_attn_width(a, n, H, [&](auto cpl, auto half, dim3 grid) {
+        k_attn_bwd_target<cpl(), half()><<<grid, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, rowptr, col, dist, cutoff, n, H, a.lph, pre_act, dq, ddk, ddv);
+        k_attn_bwd_source<cpl(), half()><<<grid, 256, 0, s>>>(q, k, v, dk, dv, dvmsg, dxagg, t_rowptr, t_eid, tgt, dist, cutoff, n, H, a.lph, pre_act, dkn, dvn);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_vec_aggregate_bwd(const float *vec, const float *s, const float *dvec3, const float *dvagg, const int *col, const int *tgt,
@@ -721,14 +647,10 @@ int conan_visnet_vec_aggregate_bwd(const float *vec, const float *s, const float
                                    float *ds, float *dvec, void *stream) {
     V_CHECK(vec && s && dvec3 && dvagg && col && tgt && t_rowptr && t_eid && num_edges_dev && ds && dvec && H > 0);
     hipStream_t st = as_stream(stream);
-    if (H == 128 && V_HALF) k_vec_aggregate_bwd_s<4, true><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
-    else if (H % 128 == 0) k_vec_aggregate_bwd_s<2><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
-    else k_vec_aggregate_bwd_s<1><<<nblk((long long)max_edges * (64 / V_RUN)), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
-    if (n > 0) {
-        if (H == 128 && V_HALF) k_vec_aggregate_bwd_v<4, true><<<nblk((long long)n * 64), 256, 0, st>>>(s, dvagg, t_rowptr, t_eid, tgt, n, H, pre_act, dvec);
-        else if (H % 128 == 0) k_vec_aggregate_bwd_v<2><<<nblk((long long)n * 64), 256, 0, st>>>(s, dvagg, t_rowptr, t_eid, tgt, n, H, pre_act, dvec);
-        else k_vec_aggregate_bwd_v<1><<<nblk((long long)n * 64), 256, 0, st>>>(s, dvagg, t_rowptr, t_eid, tgt, n, H, pre_act, dvec);
-    }
+    with_width(H, [&](auto cpl, auto half) {
+        k_vec_aggregate_bwd_s<cpl(), half()><<<edge_grid(max_edges), 256, 0, st>>>(vec, dvagg, dvec3, col, tgt, num_edges_dev, max_edges, H, pre_act ? s : nullptr, ds);
+        if (n > 0) k_vec_aggregate_bwd_v<cpl(), half()><<<node_grid(n), 256, 0, st>>>(s, dvagg, t_rowptr, t_eid, tgt, n, H, pre_act, dvec);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_node_update_bwd(const float *dxo, const float *dveco, const float *vdot, const float *o, const float *vp, int n, int H,
@@ -743,15 +665,10 @@ int conan_visnet_edge_update_bwd(const float *wt, const float *ws, const float *
     V_CHECK(wt && ws && t && dvec3 && dfo && rowptr && col && tgt && t_rowptr && t_eid && dwt && dws && dt && n >= 0 && H > 0);
     if (n == 0) return CONAN_OK;
     hipStream_t s = as_stream(stream);
-    if (H % 128 == 0) {
-        if (H == 128 && V_HALF) k_edge_update_bwd_t<4, true><<<nblk((long long)n * 64), 256, 0, s>>>(wt, ws, t, dvec3, dfo, rowptr, col, n, H, pre_act, dwt, dt);
-        else k_edge_update_bwd_t<2><<<nblk((long long)n * 64), 256, 0, s>>>(wt, ws, t, dvec3, dfo, rowptr, col, n, H, pre_act, dwt, dt);
-        if (H == 128 && V_HALF) k_edge_update_bwd_s<4, true><<<nblk((long long)n * 64), 256, 0, s>>>(wt, t, dvec3, dfo, t_rowptr, t_eid, tgt, n, H, pre_act, dws);
-        else k_edge_update_bwd_s<2><<<nblk((long long)n * 64), 256, 0, s>>>(wt, t, dvec3, dfo, t_rowptr, t_eid, tgt, n, H, pre_act, dws);
-    } else {
-        k_edge_update_bwd_t<1><<<nblk((long long)n * 64), 256, 0, s>>>(wt, ws, t, dvec3, dfo, rowptr, col, n, H, pre_act, dwt, dt);
-        k_edge_update_bwd_s<1><<<nblk((long long)n * 64), 256, 0, s>>>(wt, t, dvec3, dfo, t_rowptr, t_eid, tgt, n, H, pre_act, dws);
-    }
+    with_width(H, [&](auto cpl, auto half) {
+        k_edge_update_bwd_t<cpl(), half()><<<node_grid(n), 256, 0, s>>>(wt, ws, t, dvec3, dfo, rowptr, col, n, H, pre_act, dwt, dt);
+        k_edge_update_bwd_s<cpl(), half()><<<node_grid(n), 256, 0, s>>>(wt, t, dvec3, dfo, t_rowptr, t_eid, tgt, n, H, pre_act, dws);
+    });
     CONAN_LAUNCH_CHECK(); return CONAN_OK;
 }
 int conan_visnet_spatial_norm_bwd(const float *v, const float *dout, int n, int H, float *dv, void *stream) {

@@ -145,6 +145,9 @@ def test_graph_cases_are_what_their_names_say():
         if name == "capped":
             assert int((deg == R.CAP).sum()) == 40 and G.n * R.CAP > G.E + 300
             assert int(((G.src == G.tgt).sum())) < G.n           # the cap cuts some self loops off (candidates are taken in ascending source index)
+        if name == "long_lists":                                 # the walkers' 64-edge chunk loop is entered a second time, and not a third
+            out = torch.bincount(G.src, minlength=G.n)
+            assert int(out.max()) > 64 and int(out.max()) <= 128 and int((out > 64).sum()) == 32 and int((deg == R.CAP).sum()) == 80
     sizes = R.wide_sizes(822)
     n, E = sum(sizes), sum(m * m for m in sizes)
     assert n > R.NODE_PASS and E > R.EDGE_PASS and max(sizes) <= R.CAP      # the full `wide` graph (built in the GPU test only): both grid-stride loops are entered

@@ -153,10 +153,10 @@ def graph_on_cpu(pos, batch):
     return Graph(p.shape[0], src, tgt, torch.sqrt((d * d).sum(dim=1)), edge_unit(p, src, tgt), p, b)
 
 
-def _cluster(rng, m):
-    """m atoms on a jittered 4x4x4 lattice of spacing 0.7: every pair is 0.4 .. 4.1 apart, i.e. inside the cutoff and not degenerate."""
-    idx = rng.choice(64, size=m, replace=False)
-    p = np.stack([idx // 16, (idx // 4) % 4, idx % 4], axis=1) * 0.7 + rng.uniform(-0.12, 0.12, size=(m, 3))
+def _cluster(rng, m, side=4, spacing=0.7, jitter=0.12):
+    """m atoms on a jittered lattice, by default 4x4x4 of spacing 0.7: every pair is 0.4 .. 4.1 apart, i.e. inside the cutoff and not degenerate."""
+    idx = rng.choice(side ** 3, size=m, replace=False)
+    p = np.stack([idx // side ** 2, (idx // side) % side, idx % side], axis=1) * spacing + rng.uniform(-jitter, jitter, size=(m, 3))
     return p.astype(np.float32)
 
 
@@ -184,6 +184,10 @@ def graph_case(name):
         return pos, batch, 36 + 1 + 16
     if name == "capped":                     # 40 atoms inside the cutoff: every row truncated to 32; max_edges = 53 * 32 = 1696
         return _molecules(rng, [40, 5, 3, 2, 2, 1]) + (40 * 32 + 25 + 9 + 4 + 4 + 1,)
+    if name == "long_lists":                 # 80 atoms inside the cutoff (5x5x5 lattice of spacing 0.5: pairs 0.38 .. 3.7 apart): a row keeps its 32 lowest
+        big = _cluster(rng, 80, side=5, spacing=0.5, jitter=0.06)      # sources, so atoms 0 .. 31 are sources of all 80 rows: by-source lists of 80 > one 64-edge chunk
+        pos, batch = _molecules(rng, [5])
+        return np.concatenate([big, pos]), np.concatenate([np.zeros(80, np.int64), batch + 1]), 80 * 32 + 25
     if name == "ragged":                     # as tests/test_gpu_edge_cases.py
         pos, batch, g = [], [], 0
         for m in [4, 30, 2, 17]:
@@ -196,7 +200,7 @@ def graph_case(name):
     raise KeyError(name)
 
 
-GRAPHS = ["tiny", "partial_run1", "partial_run13", "isolated", "capped", "ragged"]
+GRAPHS = ["tiny", "partial_run1", "partial_run13", "isolated", "capped", "ragged", "long_lists"]
 
 
 # ================================================================================================ ops: inputs + reference
