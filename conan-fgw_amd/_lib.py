@@ -164,6 +164,11 @@ SIGNATURES = {
     "conan_fgw_pair_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(FgwParams), c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "conan_fgw_pair_dist": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P]),
     "conan_fgw_pair_dist_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P]),
+    "conan_fgw_acc_lds_resident": (c_int, [c_int]),
+    "conan_fgw_acc_pair_workspace_bytes": (c_ll, [c_int, c_int]),
+    "conan_fgw_acc_pair_fwd": (c_int, [_P] * 6 + [c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double] + [_P] * 5),
+    "conan_fgw_mixup_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "conan_fgw_mixup_barycenter_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, ctypes.POINTER(FgwParams), ctypes.c_double, c_int, ctypes.c_double] + [_P] * 8),
     "conan_sinkhorn_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
     "conan_sinkhorn_lds_resident": (c_int, [c_int, c_int]),
     "conan_sinkhorn_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_ll, c_float, c_int, c_int, c_float] + [_P] * 8),

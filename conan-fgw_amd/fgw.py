@@ -1,7 +1,8 @@
 """Functional boundary of the FGW solver, mirroring the reference's signature
 (conan_fgw/src/model/fgw/barycenter.py:7-31 `fgw_barycenters`, :393-399 `normalize_tensor`; bregman.py:8-279 `fgw`, `fgw_projected`,
 `fgw_bregman` — the coupling solve between two attributed graphs on its own, with `fgw_distance`, its differentiable distance, and
-`fgw_pairwise_distances` over an ensemble on top).
+`fgw_pairwise_distances` over an ensemble on top; barycenter.py:228-390 `fused_ACC_torch`, `fgw_barycenters_BAPG` — FGWMixup's accelerated
+mirror descent and the barycenter around it, forward only: see their docstrings for the deviations).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
 barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
@@ -26,6 +27,46 @@ import torch
 from torch import Tensor
 
 from . import ops
+
+
+def _embed_graphs(N, Ys_l, Cs_l, ps, p, sizes, d, dev):
+    """The massless embedding of fgw_barycenters and fgw_barycenters_BAPG (see the comment in fgw_barycenters) -> (embedded, Np, Ys_l, Cs_l, ps,
+    p_embedded): with input graphs of other sizes everything is padded to Np = max(N, max n_s) nodes and the weights, given or uniform, carry
+    zeros for the extra nodes; otherwise the arguments come back as they are (p_embedded None)."""
+    Np = max([N] + sizes)
+    embedded = Np != N or any(n != N for n in sizes)
+    if not embedded:
+        return False, Np, Ys_l, Cs_l, ps, None
+
+    def pad(t, *shape):
+        out = torch.zeros(*shape, dtype=torch.float32, device=dev)
+        out[tuple(slice(0, k) for k in t.shape)] = t
+        return out
+    ps_l = [torch.ones(n, device=dev) / n for n in sizes] if ps is None else [q.to(torch.float32).to(dev) for q in (ps.unbind(0) if torch.is_tensor(ps) else ps)]
+    p_full = (torch.ones(N, device=dev) / N) if p is None else p.to(torch.float32).to(dev)
+    return True, Np, [pad(y, Np, d) for y in Ys_l], [pad(c, Np, Np) for c in Cs_l], [pad(q, Np) for q in ps_l], pad(p_full, Np)
+
+
+def _seeded_init_C(N, seed, device):
+    """barycenter.py:61-65 / :303-306: torch.manual_seed(seed); xalea = torch.randn(N, 2); C = dist(xalea, xalea) — a host-side random
+    squared-distance matrix (utils.py:154-171 with X is Y: clamped at 0, zero diagonal).  Reproduced draw for draw, including the
+    reference's re-seeding of the global generator; N x 2 numbers of initialisation, not the solver."""
+    torch.manual_seed(seed)
+    xalea = torch.randn(N, 2)
+    a2 = torch.einsum("ij,ij->i", xalea, xalea)
+    c0 = -2 * (xalea @ xalea.T)
+    c0 += a2[:, None]
+    c0 += a2[None, :]
+    return (torch.clamp(c0, min=0) * (1 - torch.eye(N))).to(device)
+
+
+def _embed_init(init_C, init_Y, N, Np, d, dev):
+    """init_C [N,N] / init_Y [N,d] (or None) inside the embedded problem's Np nodes: the extra rows and columns are zero."""
+    ic = torch.zeros(Np, Np, dtype=torch.float32, device=dev); ic[:N, :N] = init_C.to(torch.float32)
+    if init_Y is not None:
+        iy = torch.zeros(Np, d, dtype=torch.float32, device=dev); iy[:N] = init_Y.to(torch.float32)
+        init_Y = iy
+    return ic, init_Y
 
 
 def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=None, lambdas=None, loss_fun="square_loss",
@@ -68,39 +109,14 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
     # every coupling is exactly zero in the Sinkhorn scaling (u_i = p_i / (K v)_i), it adds nothing to any product, and the barycenter update
     # keeps its row of Y and its row / column of C at zero (fgw_small.hip: the divisions by p are guarded) — the leading N x N / N x n_s blocks
     # are the reference's rectangular problem, term for term.
-    Np = max([N] + sizes)
-    embedded = Np != N or any(n != N for n in sizes)
     dev = Ys_l[0].device
-    if embedded:
-        def pad(t, *shape):
-            out = torch.zeros(*shape, dtype=torch.float32, device=dev)
-            out[tuple(slice(0, k) for k in t.shape)] = t
-            return out
-        ps_l = [torch.ones(n, device=dev) / n for n in sizes] if ps is None else [q.to(torch.float32).to(dev) for q in (ps.unbind(0) if torch.is_tensor(ps) else ps)]
-        p_full = (torch.ones(N, device=dev) / N) if p is None else p.to(torch.float32).to(dev)
-        Ys_l = [pad(y, Np, d) for y in Ys_l]
-        Cs_l = [pad(c, Np, Np) for c in Cs_l]
-        ps = [pad(q, Np) for q in ps_l]
-        p_embedded = pad(p_full, Np)
+    embedded, Np, Ys_l, Cs_l, ps, p_embedded = _embed_graphs(N, Ys_l, Cs_l, ps, p, sizes, d, dev)
     Ys_t, Cs_t = torch.stack(Ys_l), torch.stack(Cs_l)
     if init_C is None:
-        # barycenter.py:61-65: torch.manual_seed(seed); xalea = torch.randn(N, 2); C = dist(xalea, xalea) — a host-side random
-        # squared-distance matrix (utils.py:154-171 with X is Y: clamped at 0, zero diagonal).  Reproduced draw for draw,
-        # including the reference's re-seeding of the global generator; N x 2 numbers of initialisation, not the solver.
-        torch.manual_seed(seed)
-        xalea = torch.randn(N, 2)
-        a2 = torch.einsum("ij,ij->i", xalea, xalea)
-        c0 = -2 * (xalea @ xalea.T)
-        c0 += a2[:, None]
-        c0 += a2[None, :]
-        init_C = (torch.clamp(c0, min=0) * (1 - torch.eye(N))).to(Ys_t.device)
+        init_C = _seeded_init_C(N, seed, Ys_t.device)
     N_user = N
     if embedded:
-        ic = torch.zeros(Np, Np, dtype=torch.float32, device=dev); ic[:N, :N] = init_C.to(torch.float32)
-        init_C = ic
-        if init_Y is not None:
-            iy = torch.zeros(Np, d, dtype=torch.float32, device=dev); iy[:N] = init_Y.to(torch.float32)
-            init_Y = iy
+        init_C, init_Y = _embed_init(init_C, init_Y, N, Np, d, dev)
         N = Np
     ps_t = None
     if ps is not None:
@@ -144,6 +160,81 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
             "Ms": Ms,
             "n_outer": outer, "n_pgd": int(info[0, 1].item()), "n_sinkhorn": int(info[0, 2].item())}
     return Y[0], C[0], log_
+
+
+def fused_ACC_torch(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-5, rho=1e-1):
+    """FGWMixup's coupling solve between two attributed graphs, the reference's fused_ACC_torch (barycenter.py:228-256): accelerated mirror
+    descent on X from a b^T (or the given X), at most `epoch` epochs, stopped when the objective's relative change between two checks (every
+    10th epoch) falls below eps -> (X, obj_list).  M [n1,n2], A [n1,n1], B [n2,n2] (any sizes: n1 != n2 is embedded with massless nodes).
+    Deviations from the reference: a / b given as None mean uniform weights (the reference forms a dot product there); no gradient is carried;
+    the run is an fp64 iteration on the fp32 inputs, so counts and values follow the reference's fp64 run; a weight that is exactly ZERO marks
+    an absent node whose entries stay zero (the reference lifts them by 1e-10 every epoch).  A NaN result (exp under- / overflow at small rho)
+    is the reference's NaN.  Runs on the GPU only."""
+    for name, t in (("M", M), ("A", A), ("B", B), ("a", a), ("b", b), ("X", X)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"fused_ACC_torch runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    one = lambda t: None if t is None else t.unsqueeze(0)
+    Xo, objs, info = ops.fgw_acc_pair_batched(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps)
+    stored = int(info[0, 1].item())
+    return Xo[0], [objs[0, k] for k in range(stored)]
+
+
+def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=None, lambdas=None, loss_fun="square_loss", alpha=0.5,
+                         max_iter=100, tol=1e-9, rho=1.0, verbose=False, log=False, init_C=None, init_Y=None, fixed_structure=False,
+                         fixed_features=False, seed=0, **kwargs):
+    """The FGWMixup barycenter, the reference's fgw_barycenters_BAPG (barycenter.py:259-390): the outer loop of fgw_barycenters around
+    fused_ACC_torch (100 epochs at most, eps = 1e-5, the caller's rho, always from p ps[s]^T).  This is not fgw_barycenters(solver="BAPG"),
+    which runs the Bregman projections of fgw_bregman.  Same argument names, defaults, ValueErrors, return values and log keys as the
+    reference (the log also carries n_outer and n_inner, the outer iterations and the epochs summed over all coupling solves).  Cs may be
+    directed.  Input graphs of other sizes are embedded with massless nodes, as in fgw_barycenters.
+    Deviations: ps=None means uniform weights (the reference raises a TypeError); no gradient is carried (the reference differentiates through
+    the unrolled couplings); the run is an fp64 iteration on the fp32 inputs, so iteration counts follow the reference's fp64 run; a weight
+    that is exactly ZERO marks an absent node (the reference lifts its entries by 1e-10 every epoch).  Runs on the GPU only."""
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    if fixed_structure and init_C is None:
+        raise ValueError("If C is fixed it must be initialized")
+    if fixed_features and init_Y is None:
+        raise ValueError("If Y is fixed it must be initialized")
+    N = int(N)
+    Ys_in = Ys.unbind(0) if torch.is_tensor(Ys) else Ys
+    if not all(torch.is_tensor(y) and y.is_cuda for y in Ys_in):
+        raise NotImplementedError("fgw_barycenters_BAPG runs on the GPU only: pass CUDA (ROCm) tensors")
+    Ys_l = [y.detach().to(torch.float32) for y in Ys_in]
+    Cs_l = [c.detach().to(torch.float32) for c in (Cs.unbind(0) if torch.is_tensor(Cs) else Cs)]
+    K, d = len(Ys_l), Ys_l[0].shape[1]
+    sizes = [int(y.shape[0]) for y in Ys_l]
+    if len(Cs_l) != K or any(tuple(c.shape) != (n, n) for c, n in zip(Cs_l, sizes)):
+        raise ValueError("Cs[s] must be a square matrix over the nodes of Ys[s]")
+    dev = Ys_l[0].device
+    embedded, Np, Ys_l, Cs_l, ps_e, p_embedded = _embed_graphs(N, Ys_l, Cs_l, ps, p, sizes, d, dev)
+    if init_C is None:
+        init_C = _seeded_init_C(N, seed, dev)
+    N_user = N
+    if embedded:
+        init_C, init_Y = _embed_init(init_C, init_Y, N, Np, d, dev)
+        N = Np
+    ps_t = None if ps_e is None else (torch.stack(list(ps_e)) if not torch.is_tensor(ps_e) else ps_e).to(torch.float32).to(dev).view(1, K, N)
+    p_t = p_embedded.view(1, N) if embedded else (None if p is None else p.to(torch.float32).to(dev).view(1, N))
+    lam = None if lambdas is None else torch.as_tensor([float(l) for l in lambdas], dtype=torch.float32, device=dev)
+    res = ops.fgw_mixup_barycenter_batched(
+        torch.stack(Ys_l).view(1, K, N, d), torch.stack(Cs_l).view(1, K, N, N), ps=ps_t, p=p_t, lambdas=lam,
+        init_C=init_C.to(torch.float32).to(dev).view(1, N, N), init_Y=None if init_Y is None else init_Y.to(torch.float32).to(dev).view(1, N, d),
+        alpha=alpha, rho=rho, max_iter=max_iter, tol=tol, epoch=100, eps=1e-5, fixed_structure=fixed_structure, fixed_features=fixed_features,
+        loss_fun=loss_fun, keep_iterates=bool(log))
+    Y, C, T, info, errs = res[:5]
+    Y, C = Y[0, :N_user], C[0, :N_user, :N_user]
+    if not log:
+        return Y, C
+    outer = int(info[0, 0].item())
+    T_iter = res[5]
+    Ms = [feature_cost(Y, Ys_l[s][:sizes[s]]) for s in range(K)]          # log["Ms"] (barycenter.py:355,386): dist(Y, Ys[s]) of the returned barycenter
+    log_ = {"err_feature": [errs[0, 0, i] for i in range(outer)], "err_structure": [errs[0, 1, i] for i in range(outer)],
+            "Ts_iter": [[T_iter[i, 0, s, :N_user, :sizes[s]] for s in range(K)] for i in range(outer)],
+            "T": [T[0, s, :N_user, :sizes[s]] for s in range(K)],
+            "p": p if p is not None else torch.ones(N_user, device=dev) / N_user,
+            "Ms": Ms, "n_outer": outer, "n_inner": int(info[0, 1].item())}
+    return Y, C, log_
 
 
 _FAILED = "Solver failed to produce a transport plan. You might want to increase the regularization parameter `epsilon`."

@@ -6,6 +6,7 @@ libconan_fgw_hip.so.  All ops require CUDA(ROCm) tensors and raise otherwise.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -1046,6 +1047,105 @@ def fgw_pair_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
     M, C1, C2, p, q, G0, sizes = _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s)
     T, dist, info, errs = fgw_pair_batched(M, C1, C2, p, q, G0, **params)
     return [T[b, :n1, :n2] for b, (n1, n2) in enumerate(sizes)], dist, info, errs
+
+
+def _mixup_tensor(t, name, *shape):
+    if not t.is_cuda:
+        raise NotImplementedError(f"the FGWMixup solve runs on the GPU only: {name} is a CPU tensor")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have shape {list(shape)}, not {list(t.shape)}")
+    return _c(t.detach().to(f32))
+
+
+def _mixup_step(rho, epoch, eps):
+    rho, epoch, eps = float(rho), int(epoch), float(eps)
+    if not (rho > 0 and math.isfinite(rho)):
+        raise ValueError(f"rho must be positive and finite, not {rho}")
+    if epoch <= 0:
+        raise ValueError(f"epoch must be positive, not {epoch}")
+    return rho, epoch, eps
+
+
+def fgw_acc_pair_batched(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, X0: Optional[Tensor] = None, *,
+                         alpha: float, rho: float, epoch: int = 200, eps: float = 1e-5, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None):
+    """B independent FGWMixup coupling solves, the reference's fused_ACC_torch(M, A, B, a, b, X, alpha, epoch, eps, rho) (barycenter.py:228-256:
+    accelerated mirror descent, not the Bregman solve of fgw_pair_batched(solver="BAPG")), in one launch, one workgroup per pair.
+    M [B,N1,N2], A [B,N1,N1], Bm [B,N2,N2] (untransposed in the gradient, as the reference has it), a [B,N1] / b [B,N2] or None (uniform), X0
+    [B,N1,N2] the start or None (a b^T) -> X [B,N1,N2], objs [B, ceil(epoch / 10)] (the objective of every check that ran, the stopping one
+    included; NaN elsewhere), info [B,4] int32 = {epochs run, checks stored = the reference's len(obj_list), flags, 0}; flags bit 2: a row or
+    column with mass had a zero or non-finite sum (the reference's NaN, computed here too).
+    n1 [B] / n2 [B] int (optional): the pairs' own sizes inside the [N1,N2] container (uniform weights are then uniform over the own nodes).
+    N1 != N2 and own sizes are solved embedded in a square problem of max(N1, N2) nodes whose extra nodes carry no mass: their entries stay
+    exactly zero (no 1e-10 is added there), so the leading block is the reference's rectangular solve.  One consequence: a weight the caller
+    sets to ZERO means "absent", where the reference lifts such entries by 1e-10 per epoch.  fp32 in and out, fp64 inside.  No gradient."""
+    rho, epoch, eps = _mixup_step(rho, epoch, eps)
+    if M.dim() != 3:
+        raise ValueError(f"M must be [B,N1,N2], not {list(M.shape)}")
+    B, N1, N2 = M.shape
+    M, A, Bm = _mixup_tensor(M, "M", B, N1, N2), _mixup_tensor(A, "A", B, N1, N1), _mixup_tensor(Bm, "Bm", B, N2, N2)
+    a = None if a is None else _mixup_tensor(a, "a", B, N1)
+    b = None if b is None else _mixup_tensor(b, "b", B, N2)
+    X0 = None if X0 is None else _mixup_tensor(X0, "X0", B, N1, N2)
+    dev, N = M.device, max(N1, N2)
+    if N1 != N2 or n1 is not None or n2 is not None:
+        def own(n, Nc):
+            n = torch.full((B,), Nc, device=dev) if n is None else torch.as_tensor(n, device=dev).reshape(B)
+            return (torch.arange(N, device=dev)[None, :] < n[:, None]).to(f32), n.to(f32)
+
+        def pad(t, *shape):
+            out = torch.zeros(B, *shape, dtype=f32, device=dev)
+            out[(slice(None),) + tuple(slice(0, k) for k in t.shape[1:])] = t
+            return out
+        (m1, c1), (m2, c2) = own(n1, N1), own(n2, N2)
+        a = m1 / c1[:, None] if a is None else pad(a, N) * m1
+        b = m2 / c2[:, None] if b is None else pad(b, N) * m2
+        M, A, Bm = pad(M, N, N), pad(A, N, N), pad(Bm, N, N)
+        X0 = None if X0 is None else pad(X0, N, N)
+    X = torch.empty(B, N, N, dtype=f32, device=dev)
+    objs = torch.empty(B, (epoch + 9) // 10, dtype=f32, device=dev)
+    info = torch.empty(B, 4, dtype=i32, device=dev)
+    ws = torch.empty(int(lib().conan_fgw_acc_pair_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
+    call("conan_fgw_acc_pair_fwd", ptr(M, f32), ptr(A, f32), ptr(Bm, f32), ptr(a), ptr(b), ptr(X0), B, N, float(alpha), rho, epoch, eps,
+         ptr(X), ptr(objs), ptr(info), ptr(ws), stream_ptr())
+    return (X if N1 == N2 else X[:, :N1, :N2]), objs, info
+
+
+def fgw_mixup_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, p: Optional[Tensor] = None, lambdas: Optional[Tensor] = None,
+                                 init_C: Optional[Tensor] = None, init_Y: Optional[Tensor] = None, *, alpha: float = 0.5, rho: float = 1.0,
+                                 max_iter: int = 100, tol: float = 1e-9, epoch: int = 100, eps: float = 1e-5, fixed_structure: bool = False,
+                                 fixed_features: bool = False, loss_fun: str = "square_loss", keep_iterates: bool = False):
+    """B independent FGWMixup barycenters, the reference's fgw_barycenters_BAPG (barycenter.py:259-390): the outer loop of fgw_barycenter_batched
+    (same updates, error norms and stop rule) around the coupling solve of fgw_acc_pair_batched, run for every input graph in every outer
+    iteration from p ps[s]^T with `epoch` epochs at most and `eps` (the reference: 100 and 1e-5) and the caller's rho.
+    Ys [B,K,N,d], Cs [B,K,N,N] (may be directed), ps [B,K,N] / p [B,N] or None (uniform), lambdas [K] or None, init_C [B,N,N] or None
+    (Cs[:,0]), init_Y [B,N,d] or None (zeros) -> Y [B,N,d], C [B,N,N], T [B,K,N,N], info [B,4] int32 = {outer iterations, epochs summed over
+    couplings and iterations, 0, flags}, errs [B,2,max_iter] (+ T_iter [max_iter,B,K,N,N] with keep_iterates=True).  Flags bit 2: a row or
+    column with mass had a zero or non-finite sum (the molecule's outputs are then NaN, as the reference's).  Zero entries of p / ps are
+    nodes without mass (the embedding of other sizes); see fgw_acc_pair_batched.  The outputs carry no gradient."""
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    rho, epoch, eps = _mixup_step(rho, epoch, eps)
+    if Ys.dim() != 4:
+        raise ValueError(f"Ys must be [B,K,N,d], not {list(Ys.shape)}")
+    B, K, N, d = Ys.shape
+    Ys, Cs = _mixup_tensor(Ys, "Ys", B, K, N, d), _mixup_tensor(Cs, "Cs", B, K, N, N)
+    opt = lambda t, name, *shape: None if t is None else _mixup_tensor(t, name, *shape)
+    ps, p, lambdas = opt(ps, "ps", B, K, N), opt(p, "p", B, N), opt(lambdas, "lambdas", K)
+    init_C, init_Y = opt(init_C, "init_C", B, N, N), opt(init_Y, "init_Y", B, N, d)
+    if fixed_features and init_Y is None:
+        raise ValueError("If Y is fixed it must be initialized")
+    dev = Ys.device
+    prm = _fgw_params(alpha, 0.0, max_iter, tol, 0.0, 1, 0.0, fixed_structure, fixed_features, False, loss_fun)
+    Y = torch.empty(B, N, d, dtype=f32, device=dev)
+    C = torch.empty(B, N, N, dtype=f32, device=dev)
+    T = torch.empty(B, K, N, N, dtype=f32, device=dev)
+    T_iter = torch.empty(prm.max_iter, B, K, N, N, dtype=f32, device=dev) if keep_iterates else None
+    info = torch.empty(B, 4, dtype=i32, device=dev)
+    errs = torch.empty(B, 2, prm.max_iter, dtype=f32, device=dev)
+    ws = torch.empty(int(lib().conan_fgw_mixup_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
+    call("conan_fgw_mixup_barycenter_fwd", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d,
+         ctypes.byref(prm), rho, epoch, eps, ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+    return (Y, C, T, info, errs) if T_iter is None else (Y, C, T, info, errs, T_iter)
 
 
 class _FgwPairDistFn(torch.autograd.Function):

@@ -677,6 +677,39 @@ int conan_fgw_pair_dist_bwd(const float *C1, const float *C2, const float *p, co
                             int B, int N, float alpha, int loss_fun,
                             float *dM, float *dC1, float *dC2, float *dp, float *dq, void *stream);
 
+/* FGWMixup's coupling solve, the reference's fused_ACC_torch(M, A, B, a, b, X, alpha, epoch, eps, rho) (barycenter.py:228-256), B pairs at once,
+ * one workgroup per pair.  Not solver 2 of conan_fgw_pair_fwd: an accelerated mirror descent whose epoch ii = 0 .. epoch - 1 is
+ *   X += 1e-10;  X *= exp((4 alpha (A X) Bm - (1 - alpha) M) / rho), rows scaled to a;  the same, columns scaled to b;
+ *   ii > 0 and ii % 10 == 0: obj = sum(((1 - alpha) M - 2 alpha (A X) Bm) o X), stop when |obj - last| / |last| < eps, else store obj
+ * (Bm enters untransposed; the first check only stores, so the earliest stop is after 21 epochs; a NaN objective never stops the loop).
+ * M[B,N,N], A[B,N,N], Bm[B,N,N]; a[B,N] / b[B,N] or NULL (uniform); X0[B,N,N] the start or NULL (a b^T); all fp32, fp64 inside, every sum in a
+ * fixed order, no atomics.  Entries of a / b may be ZERO (a node without mass): its row / column of X stays exactly zero (no 1e-10 there), so a
+ * rectangular pair embedded in N = max(n1, n2) with zero rows / columns and zero weights comes out as the reference's rectangular solve.
+ * Outputs: X[B,N,N]; objs[B, ceil(epoch / 10)] fp32: the objective of every check that ran, the stopping one included (NaN elsewhere);
+ * info[B,4] int32 = {epochs run, checks stored (the reference's len(obj_list)), flags, 0}, flags bit 2: a row or column WITH mass had a zero
+ * or non-finite sum (exp under- / overflow: the reference's NaN, computed here too).
+ * The matrices (24 bytes per entry) are LDS-resident when conan_fgw_acc_lds_resident(N) (host only: N <= 79), else streamed from the workspace,
+ * conan_fgw_acc_pair_workspace_bytes(B, N) bytes (0 for a non-positive B or N).  CONAN_E_BADARG, before any launch, for a null M / A / Bm / X /
+ * objs / info / workspace, B <= 0, N <= 0, epoch <= 0, rho <= 0 or not finite, or a NaN alpha / eps. */
+int conan_fgw_acc_lds_resident(int N);
+long long conan_fgw_acc_pair_workspace_bytes(int B, int N);
+int conan_fgw_acc_pair_fwd(const float *M, const float *A, const float *Bm, const float *a, const float *b, const float *X0, int B, int N,
+                           double alpha, double rho, int epoch, double eps, float *X, float *objs, int *info, void *workspace, void *stream);
+/* The FGWMixup barycenter, the reference's fgw_barycenters_BAPG (barycenter.py:259-390): the outer loop of conan_fgw_barycenter_fwd (same
+ * feature / structure updates, error norms and stop rule, no host synchronisation) around the solve above — for every input graph and outer
+ * iteration with A = the current C, Bm = Cs[b,s], a = p, b = ps[b,s], always from p ps^T (no warm start), `epoch` epochs at most (the
+ * reference: 100), `eps` (1e-5) and the caller's rho.  Arguments and outputs as conan_fgw_barycenter_fwd, dense Cs only; of params it reads
+ * alpha, max_iter, tol, fixed_structure, fixed_features and loss_fun (which only selects the structure update).  init_C NULL = Cs[b,0].
+ * info[B,4] = {outer iterations, epochs summed over couplings and iterations, 0, flags (bit 2 as above)}; errs, T_iter as there.
+ * Workspace: conan_fgw_mixup_workspace_bytes(B, K, N, d) (0 for a non-positive dimension).  CONAN_E_BADARG, before any launch, for a null
+ * required pointer, a non-positive dimension, max_iter or epoch, rho <= 0 or not finite, a NaN eps, fixed_features without init_Y or an
+ * unknown loss_fun. */
+long long conan_fgw_mixup_workspace_bytes(int B, int K, int N, int d);
+int conan_fgw_mixup_barycenter_fwd(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas,
+                                   const float *init_C, const float *init_Y, int B, int K, int N, int d,
+                                   const conan_fgw_params *params /* (host) */, double rho, int epoch, double eps, float *Y, float *C, float *T,
+                                   float *T_iter, int *info, float *errs, void *workspace, void *stream);
+
 /* Entropic optimal transport on its own, B problems at once: the reference's sinkhorn_log (sinkhorn.py:318-450, method 0) and sinkhorn_knopp
  * (:207-315, method 1), one workgroup per problem (sinkhorn.hip).
  * M[B,N1,N2] the costs, problem b at M + b * m_batch_stride floats (0: one M shared by the whole batch); a[B,N1] / b[B,N2] the marginals or NULL
