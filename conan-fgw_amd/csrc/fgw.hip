@@ -581,7 +581,7 @@ __global__ void __launch_bounds__(256) k_densify(const float *__restrict__ feat,
             int a = 0, b = m;                                            // rp[a] <= e < rp[b]
             while (b - a > 1) { const int c = (a + b) >> 1; if (rp[c] <= e) a = c; else b = c; }
             const int i = i0 + a, j = col[e] - lo;
-            if (j >= 0 && j < N) atomicAdd(&Cg[j * N + i], 1.0f);
+            if (j >= 0 && j < n) atomicAdd(&Cg[j * N + i], 1.0f);        // a source outside this graph is dropped (j < N alone would keep a neighbour graph's atom in the padding rows)
         }
     }
     (void)e0; (void)e1;
@@ -663,6 +663,21 @@ __global__ void __launch_bounds__(64) k_readout_bwd(const float *__restrict__ Y,
                                                     float *__restrict__ dY) {
     const int b = blockIdx.x;
     const float *Yb = Y + (size_t)b * N * d;
+    // mode 1: the forward replaced a molecule that holds a NaN by zeros (a constant), so no gradient reaches its Y — without this guard the
+    // column of the NaN came out NaN and every other column carried the gradient of a normalisation the forward never performed
+    __shared__ int has_nan;
+    if (threadIdx.x == 0) has_nan = 0;
+    __syncthreads();
+    if (mode == 1) {
+        int bad = 0;
+        for (int t = threadIdx.x; t < N * d; t += 64) bad |= isnan(Yb[t]) ? 1 : 0;
+        if (bad) has_nan = 1;
+        __syncthreads();
+        if (has_nan) {
+            for (int t = threadIdx.x; t < N * d; t += 64) dY[(size_t)b * N * d + t] = 0.f;
+            return;
+        }
+    }
     for (int c = threadIdx.x; c < d; c += 64) {
         float g = 0.f;
         for (int k = 0; k < K; ++k) g += dout[((size_t)b * K + k) * d + c];

@@ -101,14 +101,16 @@ template <int OP>      // 0 = relu, 1 = sigmoid
 __global__ void k_unary_fwd(const float *__restrict__ x, long long n, float *__restrict__ y) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float v = x[i];
-        y[i] = OP == 0 ? fmaxf(v, 0.f) : OP == 1 ? 1.0f / (1.0f + expf(-v)) : ssp_f(v);
+        // relu: a NaN stays visible, as in torch.relu (fmaxf alone would turn it into 0)
+        y[i] = OP == 0 ? (v != v ? v : fmaxf(v, 0.f)) : OP == 1 ? 1.0f / (1.0f + expf(-v)) : ssp_f(v);
     }
 }
 template <int OP>
 __global__ void k_unary_bwd(const float *__restrict__ y, const float *__restrict__ dy, long long n, float *__restrict__ dx) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float o = y[i];
-        dx[i] = OP == 0 ? (o > 0.f ? dy[i] : 0.f) : OP == 1 ? dy[i] * o * (1.0f - o) : dy[i] * (1.0f - 0.5f * __expf(-o));
+        // relu: torch's threshold_backward (y <= 0 ? 0 : dy), so a NaN output lets the gradient through
+        dx[i] = OP == 0 ? (o <= 0.f ? 0.f : dy[i]) : OP == 1 ? dy[i] * o * (1.0f - o) : dy[i] * (1.0f - 0.5f * __expf(-o));
     }
 }
 

@@ -702,9 +702,13 @@ class _CFConvFn(torch.autograd.Function):
             t_rowptr, t_eid = g.transpose()
             dx = torch.empty_like(x)
             dW = torch.empty_like(W)
+            # The forward launch cleared this word ONCE: a second backward through the same forward (retain_graph) must not raise a maximum on top
+            # of the first pass's — a much smaller second gradient would be put on the fp16 planes with the first one's power of two.  The word is
+            # consumed here; a re-entry takes the pair of kernels below, whose dx kernel clears a slot of its own (same bits, one launch more).
+            gmax, ctx.gmax = ctx.gmax, None
             call("conan_cfconv_bwd_xw_pairs", ptr(W), ptr(x), ptr(dout), ptr(t_rowptr), ptr(t_eid), ptr(g.tgt), ptr(g.pid), ptr(g.pair_e0), ptr(g.pair_e1),
-                 ptr(g.pair_dist), float(g.cutoff), g.num_atoms, F, ptr(dx), ptr(dW), ptr(ctx.gmax), stream_ptr())
-            _tag_gmax(dW, ctx.gmax)
+                 ptr(g.pair_dist), float(g.cutoff), g.num_atoms, F, ptr(dx), ptr(dW), ptr(gmax), stream_ptr())
+            _tag_gmax(dW, gmax)
             return dx, dW, None, None, None
         # max |dW| of the pair gradient (F = 128): one device float per CFConv backward, raised by conan_cfconv_bwd_w_pairs with atomicMax.  It is
         # cleared by the dx kernel that runs right before it on this stream (zero_slot) — fresh on every backward pass, no fill launch, and

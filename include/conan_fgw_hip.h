@@ -766,7 +766,8 @@ int conan_fgw_readout_bwd(const float *Y, const float *dout, int B, int K, int N
 /* Elementwise activations: op 0 = ReLU, 1 = sigmoid (classification head: build_mlp_class + torch.sigmoid,
  * schnet_based_models.py:31-45,367), 2 = shifted softplus (PyG ShiftedSoftplus as a stand-alone module, `SchNetNoSum.act`,
  * schnet_no_sum.py:178,227,231 — on the model path it is fused into conan_linear_fwd).  The backward takes the forward
- * OUTPUT y (relu' = [y > 0], sigmoid' = y (1 - y), ssp' = 1 - 0.5 exp(-y)). */
+ * OUTPUT y (relu' = [y > 0], sigmoid' = y (1 - y), ssp' = 1 - 0.5 exp(-y)).  A NaN stays visible, as in torch: relu(NaN) = NaN, and a NaN
+ * output lets the gradient through (threshold_backward: y <= 0 ? 0 : dy). */
 int conan_unary_fwd(const float *x, long long count, int op, float *y, void *stream);
 int conan_unary_bwd(const float *y, const float *dy, long long count, int op, float *dx, void *stream);
 

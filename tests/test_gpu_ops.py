@@ -318,6 +318,63 @@ def test_cfconv_backward_in_one_launch_equals_the_two_kernels(shape, B, K):
     assert float(a[1][3]) < 0.01 * float(a[0][3])                                # the second pass's (1000x smaller) maximum is not the first's
 
 
+@pytest.mark.parametrize("order", ["large_then_small", "small_then_large"])
+def test_second_backward_through_one_cfconv_forward_equals_a_fresh_one(order):
+    """out.backward(g1, retain_graph=True), then out.backward(g2) through the SAME forward: the maximum |dW| that scales the pair gradient onto
+    the fp16 planes of the filter backward is cleared by the forward launch only, so the second pass must not raise it on top of the first's
+    (a 1e-6 times smaller second gradient went onto the planes with the first one's power of two: the filter-network gradients lost their
+    low bits).  Every gradient of the second pass has the bits of a fresh forward + backward(g2) and stays within the tolerance of
+    test_filter_network_backward_in_one_pass against fp64; the first pass has the bits of a fresh one too."""
+    b = make_batch("esol", 3, 2)
+    g = _edges(b)
+    n, F_, Gs = g.num_atoms, 128, 50
+    torch.manual_seed(11)
+    gs = ps.GaussianSmearing(0.0, 10.0, Gs)
+    mlp = torch.nn.Sequential(torch.nn.Linear(Gs, F_), ps.ShiftedSoftplus(), torch.nn.Linear(F_, F_))
+    gen = torch.Generator().manual_seed(12)
+    x0, big, small = torch.randn(n, F_, generator=gen), torch.randn(n, F_, generator=gen), 1e-6 * torch.randn(n, F_, generator=gen)
+    g1, g2 = (big, small) if order == "large_then_small" else (small, big)
+    off = gs.offset.to(dev)
+
+    def forward():
+        leaves = [x0.to(dev).requires_grad_(True)] + [p.detach().to(dev).requires_grad_(True) for p in (mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias)]
+        W = ops.filter_generate(g, off, gs.coeff, *leaves[1:], use_pairs=True)
+        return leaves, ops.cfconv(leaves[0], W, g, pre_cutoff_grad=True, use_pairs=True)
+
+    def take(leaves):
+        torch.cuda.synchronize()
+        out = [t.grad.clone() for t in leaves]
+        for t in leaves:
+            t.grad = None
+        return out
+
+    leaves, out = forward()
+    out.backward(g1.to(dev), retain_graph=True)
+    first = take(leaves)
+    out.backward(g2.to(dev))
+    second = take(leaves)
+    fresh = {}
+    for tag, gy in (("g1", g1), ("g2", g2)):
+        leaves, out = forward()
+        out.backward(gy.to(dev))
+        fresh[tag] = take(leaves)
+    names = ("x", "w1", "b1", "w2", "b2")
+    for k, a, c in zip(names, first, fresh["g1"]):
+        assert torch.equal(a, c), ("first pass", k)
+    for k, a, c in zip(names, second, fresh["g2"]):
+        assert torch.equal(a, c), ("second pass", k, rel(a.cpu(), c.cpu()))
+    # fp64
+    ei = g.edge_index().cpu()
+    d = g.edge_weight().cpu().double()
+    m64 = mlp.double()
+    x64 = x0.double().requires_grad_(True)
+    Wd = m64(gs(d)) * (0.5 * (torch.cos(d * math.pi / 10.0) + 1.0))[:, None]
+    ref = torch.zeros(n, F_, dtype=torch.float64).index_add_(0, ei[1], x64[ei[0]] * Wd)
+    want = torch.autograd.grad(ref, [x64, m64[0].weight, m64[0].bias, m64[2].weight, m64[2].bias], g2.double())
+    for k, a, w in zip(names, second, want):
+        assert rel(a.cpu(), w) < 1e-5, (k, rel(a.cpu(), w))
+
+
 def test_filter_gradient_maximum_travels_with_the_tensor_and_is_dropped_when_the_gradient_was_touched():
     """The fp16-plane filter backward scales g from max|g|, which the pair-gradient kernel tracks (ops._tag_gmax / _take_gmax).  (i) One
     consumer per filter (every model): the tag survives the hop through the autograd engine, the fast kernels run.  (ii) ONE filter feeding
