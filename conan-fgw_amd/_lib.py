@@ -172,6 +172,11 @@ SIGNATURES = {
     "conan_sinkhorn_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
     "conan_sinkhorn_lds_resident": (c_int, [c_int, c_int]),
     "conan_sinkhorn_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_ll, c_float, c_int, c_int, c_float] + [_P] * 8),
+    "conan_sinkhorn_ext_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
+    "conan_sinkhorn_ext_lds_resident": (c_int, [c_int, c_int]),
+    "conan_sinkhorn_ext_nerr": (c_int, [c_int, c_int, c_int]),
+    "conan_sinkhorn_ext_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_ll, ctypes.c_double, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int,
+                                       ctypes.c_double, c_int] + [_P] * 11),
     "conan_fgw_barycenter_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "conan_fgw_barycenter_bwd_full_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "conan_fgw_barycenter_bwd_full": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1373,6 +1373,109 @@ def sinkhorn_loss(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = N
     return out if return_plan else out[0]
 
 
+# ------------------------------------------------------------------------- the reference's other three Sinkhorn solvers (sinkhorn_ext.hip)
+SINKHORN_EXT_METHODS = {"greenkhorn": 2, "sinkhorn_stabilized": 3, "sinkhorn_epsilon_scaling": 4}
+_SINKHORN_EXT_ITERS = {"greenkhorn": 10000, "sinkhorn_stabilized": 1000, "sinkhorn_epsilon_scaling": 100}      # the reference's numItermax defaults
+
+
+def _sinkhorn_ext_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=False):
+    if method not in SINKHORN_EXT_METHODS:
+        raise ValueError("Unknown method '%s'." % method)
+    M, a, b, _wu, _wv, n1, n2, (B, N1, N2, _) = _sinkhorn_prepare(M, a, b, None, n1, n2, "sinkhorn", keep_graph=keep_graph)
+    f64 = torch.float64                                                   # the potentials travel as fp64 (see conan_sinkhorn_ext_fwd)
+    vec = lambda t, name, n: _sinkhorn_tensor(t, name, [(B, n)] + ([(n,)] if B == 1 else []), f64)
+    wu, wv = (None, None) if warmstart is None else (vec(warmstart[0], "warmstart[0]", N1), vec(warmstart[1], "warmstart[1]", N2))
+    return M, a, b, wu, wv, n1, n2, (B, N1, N2, SINKHORN_EXT_METHODS[method])
+
+
+def _sinkhorn_ext_fwd(M, a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr, tau, print_period, epsilon0, num_inner_iter_max):
+    """conan_sinkhorn_ext_fwd on prepared operands.  No host synchronisation."""
+    dev = M.device
+    nerr = int(lib().conan_sinkhorn_ext_nerr(code, int(num_iter_max), int(print_period)))
+    if nerr < 0:
+        raise ValueError("num_iter_max and print_period must be positive")
+    T = torch.empty(B, N1, N2, dtype=f32, device=dev)
+    loss = torch.empty(B, dtype=f32, device=dev)
+    log_u, log_v = torch.empty(B, N1, dtype=f32, device=dev), torch.empty(B, N2, dtype=f32, device=dev)
+    alpha, beta = torch.empty(B, N1, dtype=torch.float64, device=dev), torch.empty(B, N2, dtype=torch.float64, device=dev)
+    info, extra = torch.empty(B, 4, dtype=i32, device=dev), torch.empty(B, 4, dtype=i32, device=dev)
+    errs = torch.empty(B, nerr, dtype=f32, device=dev)
+    ws = torch.empty(max(int(lib().conan_sinkhorn_ext_workspace_bytes(B, N1, N2)), 1), dtype=torch.uint8, device=dev)
+    call("conan_sinkhorn_ext_fwd", ptr(M, f32), ptr(a), ptr(b), ptr(wu), ptr(wv), ptr(n1), ptr(n2), B, N1, N2, N1 * N2 if M.dim() == 3 else 0,
+         float(reg), code, int(num_iter_max), float(stop_thr), float(tau), int(print_period), float(epsilon0), int(num_inner_iter_max),
+         ptr(T), ptr(loss), ptr(log_u), ptr(log_v), ptr(alpha), ptr(beta), ptr(info), ptr(errs) if nerr else None, ptr(extra), ptr(ws), stream_ptr())
+    return T, loss, log_u, log_v, alpha, beta, info, errs, extra
+
+
+def _sinkhorn_ext_params(method, num_iter_max, print_period):
+    if method not in SINKHORN_EXT_METHODS:
+        raise ValueError("Unknown method '%s'." % method)
+    it = _SINKHORN_EXT_ITERS[method] if num_iter_max is None else num_iter_max
+    pp = (10 if method == "sinkhorn_epsilon_scaling" else 20) if print_period is None else print_period
+    return it, pp
+
+
+def sinkhorn_ext_batched(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, *, reg: float, method: str,
+                         num_iter_max: Optional[int] = None, stop_thr: float = 1e-9, tau: float = 1e3, print_period: Optional[int] = None,
+                         epsilon0: float = 1e4, num_inner_iter_max: int = 100, warmstart=None, n1: Optional[Tensor] = None,
+                         n2: Optional[Tensor] = None):
+    """B independent entropic OT problems in one launch by the reference's "greenkhorn" (sinkhorn.py:453-532), "sinkhorn_stabilized" (:535-685)
+    or "sinkhorn_epsilon_scaling" (:688-786), with its defaults (num_iter_max 10000 / 1000 / 100, print_period 20 / 10).  M, a, b, n1, n2 as
+    sinkhorn_batched; warmstart: (log u, log v) for greenkhorn, (alpha, beta) in cost units for the other two.
+    -> T [B,N1,N2], loss [B] = sum(M * T), log_u [B,N1], log_v [B,N2] (greenkhorn: log u, log v; else the reference's logu, logv),
+    alpha [B,N1], beta [B,N2] (fp64: the reference's log["alpha"], log["beta"]; zeros for greenkhorn; a warm start is read as fp64 too, since the
+    potentials of epsilon scaling carry an offset of ~epsilon0 log n that fp32 resolves to 2e-3 only), info [B,4] int32 = {the reference's iteration
+    index at exit, flags (bit 0: stopped on the threshold, bit 1: the NaN exit), checks executed, absorptions (epsilon scaling: inner solves that
+    ran to their cap)}, errs [B,nerr] (the error list, NaN where not executed; greenkhorn: nerr = 0), extra [B,4] int32 = {sweeps / steps
+    executed (epsilon scaling: over all inner solves), absorptions, inner NaN exits, inner iteration of the last one}.
+    The control flow follows the reference's fp64 run.  No gradient and no host synchronisation."""
+    it, pp = _sinkhorn_ext_params(method, num_iter_max, print_period)
+    M, a, b, wu, wv, n1, n2, (B, N1, N2, code) = _sinkhorn_ext_prepare(M, a, b, warmstart, n1, n2, method)
+    return _sinkhorn_ext_fwd(M, a, b, wu, wv, n1, n2, B, N1, N2, code, reg, it, stop_thr, tau, pp, epsilon0, num_inner_iter_max)
+
+
+def sinkhorn_ext_list(Ms, as_=None, bs=None, *, warmstarts=None, container=None, **params):
+    """sinkhorn_ext_batched for problems of different sizes in ONE launch (as sinkhorn_list; warm starts are stacked as fp32 here)
+    -> ([T_k], loss [B], [log_u_k], [log_v_k], [alpha_k], [beta_k], info [B,4], errs, extra [B,4])."""
+    M, a, b, warm, n1, n2, sizes = _sinkhorn_list_stack(Ms, as_, bs, warmstarts, container)
+    T, loss, lu, lv, al, be, info, errs, extra = sinkhorn_ext_batched(M, a, b, warmstart=warm, n1=n1, n2=n2, **params)
+    rows = lambda t: [t[k, :s[0]] for k, s in enumerate(sizes)]
+    cols = lambda t: [t[k, :s[1]] for k, s in enumerate(sizes)]
+    return [T[k, :s[0], :s[1]] for k, s in enumerate(sizes)], loss, rows(lu), cols(lv), rows(al), cols(be), info, errs, extra
+
+
+class _SinkhornExtLossFn(torch.autograd.Function):
+    """_SinkhornLossFn for the nine outputs of the ext solve: dM = gout * T at the returned plan, held constant."""
+    @staticmethod
+    def forward(ctx, M, run):
+        T, loss, *rest = run()
+        ctx.save_for_backward(T)
+        ctx.shared = M.dim() == 2
+        ctx.mark_non_differentiable(T, *rest)
+        return (loss, T, *rest)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        (T,) = ctx.saved_tensors
+        dM = g.to(f32)[:, None, None] * T
+        return (dM.sum(0) if ctx.shared else dM), None
+
+
+def sinkhorn_ext_loss(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, *, reg: float, method: str,
+                      num_iter_max: Optional[int] = None, stop_thr: float = 1e-9, tau: float = 1e3, print_period: Optional[int] = None,
+                      epsilon0: float = 1e4, num_inner_iter_max: int = 100, warmstart=None, n1: Optional[Tensor] = None,
+                      n2: Optional[Tensor] = None, return_plan: bool = False):
+    """The costs sum(M * T) of sinkhorn_ext_batched's solve (same arguments, same launch, same bits) as a loss [B] with the project's fixed-plan
+    gradient dM = gout * T; a, b and the warm start get none; no double backward; no host synchronisation.  return_plan: (loss, T, log_u,
+    log_v, alpha, beta, info, errs, extra), all but the first without gradient."""
+    it, pp = _sinkhorn_ext_params(method, num_iter_max, print_period)
+    Mp, a, b, wu, wv, n1, n2, (B, N1, N2, code) = _sinkhorn_ext_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=True)
+    out = _SinkhornExtLossFn.apply(Mp, lambda: _sinkhorn_ext_fwd(Mp.detach(), a, b, wu, wv, n1, n2, B, N1, N2, code, reg, it, stop_thr, tau, pp,
+                                                                 epsilon0, num_inner_iter_max))
+    return out if return_plan else out[0]
+
+
 class _MseLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target):

@@ -1,15 +1,21 @@
-"""Entropic optimal transport, mirroring the reference's conan_fgw/src/model/fgw/sinkhorn.py: `sinkhorn`, `sinkhorn_log`, `sinkhorn_knopp` and
-`sinkhorn2` with its signatures and defaults, on the batched HIP kernel of csrc/sinkhorn.hip (one workgroup per problem, rectangular problems
-solved as they are), plus `wasserstein_pairwise_distances`, the alpha = 0 sibling of `fgw.fgw_pairwise_distances`.
+"""Entropic optimal transport, mirroring the reference's conan_fgw/src/model/fgw/sinkhorn.py: `sinkhorn` with all five of its methods, `sinkhorn_log`,
+`sinkhorn_knopp`, `greenkhorn`, `sinkhorn_stabilized`, `sinkhorn_epsilon_scaling` and `sinkhorn2`, with its signatures and defaults, on the batched
+HIP kernels of csrc/sinkhorn.hip and csrc/sinkhorn_ext.hip (one workgroup per problem, rectangular problems solved as they are), plus
+`wasserstein_pairwise_distances`, the alpha = 0 sibling of `fgw.fgw_pairwise_distances`.
 
-Same return values (`log=True`: the reference's dict), the same two warnings with the reference's texts, the same `ValueError` for an unknown
-method.  Deviations, each a `NotImplementedError`: the methods "greenkhorn", "sinkhorn_stabilized" and "sinkhorn_epsilon_scaling" are not built; a
-2-D `b` (several histograms at once) is not built (the reference's Knopp form stops all histograms jointly, which one workgroup per problem
-does not reproduce: loop over the columns, or stack them through ops.sinkhorn_batched with a shared M); CPU tensors (the solve runs on the GPU
-only).  `verbose` is ignored.  Outputs are fp32; the iteration runs in fp64, so iteration counts, the error list and the Knopp numerical-errors
-exit follow the reference's fp64 run, not its fp32 run (fp32 exp underflows earlier, and an fp32 run cannot reach stopThr = 1e-9).  The plan
-carries no gradient; `sinkhorn2`'s value carries the gradient to M at the returned plan, held constant (the project's fixed-plan convention,
-fgw.fgw_distance's), not the reference's gradient through the unrolled iterations; a, b and the warm start get none.
+Same return values (`log=True`: the reference's dict with the reference's keys), the same warnings with the reference's texts, the same
+`ValueError` for an unknown method, the same warm starts: (log u, log v) for "sinkhorn_log", "sinkhorn" and "greenkhorn", (alpha, beta) in cost
+units for "sinkhorn_stabilized" and "sinkhorn_epsilon_scaling".  Deviations, each a `NotImplementedError`: a 2-D `b` (several histograms at once)
+is not implemented (the reference's Knopp form stops all histograms jointly, which one workgroup per problem does not reproduce, and its
+stabilized form cannot run there at all: loop over the columns, or stack them through ops.sinkhorn_batched / ops.sinkhorn_ext_batched with a
+shared M); CPU tensors (the solve runs on the GPU only).  `verbose` is ignored.  Epsilon scaling warns ONCE when any of its inner solves ran to
+`numInnerItermax` (the reference warns once per such solve, always from the same line, which Python's default filter shows once as well), and
+once, with the last one's iteration, when inner solves left on numerical errors.  Outputs are fp32 (`alpha`, `beta` of the last two methods:
+fp64, since epsilon scaling's potentials carry an offset of ~epsilon0 log n that fp32 resolves to 2e-3 only); the iteration runs in fp64, so iteration
+counts, error lists, absorptions and the numerical-errors exits follow the reference's fp64 run, not its fp32 run (fp32 exp underflows earlier,
+and an fp32 run cannot reach stopThr = 1e-9).  The plan carries no gradient; `sinkhorn2`'s value carries the gradient to M at the returned plan,
+held constant (the project's fixed-plan convention, fgw.fgw_distance's), not the reference's gradient through the unrolled iterations; a, b and
+the warm start get none.
 """
 from __future__ import annotations
 
@@ -22,7 +28,6 @@ from torch import Tensor
 from . import ops
 from .fgw import feature_cost
 
-_UNBUILT = ("greenkhorn", "sinkhorn_stabilized", "sinkhorn_epsilon_scaling")
 _NOT_CONVERGED = ("Sinkhorn did not converge. You might want to increase the number of iterations `numItermax` or the regularization "
                   "parameter `reg`.")
 
@@ -72,12 +77,84 @@ def sinkhorn_log(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log
     return _solve(a, b, M, reg, "sinkhorn_log", numItermax, stopThr, log, warn, warmstart)
 
 
+def _solve_ext(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost=False, **params):
+    """One problem through ops.sinkhorn_ext_* (B = 1) with the reference's return value, log dict and warnings (one host synchronisation)."""
+    if b is not None and torch.is_tensor(b) and b.dim() > 1:
+        raise NotImplementedError("several histograms at once (a 2-D b) are not implemented: solve them one by one, or as a batch with a shared M "
+                                  "through ops.sinkhorn_ext_batched")
+    tensors = [("M", M), ("a", a), ("b", b)] + ([] if warmstart is None else [("warmstart[0]", warmstart[0]), ("warmstart[1]", warmstart[1])])
+    for name, t in tensors:
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"method='{method}' is not implemented for CPU tensors: {method} runs on the GPU only ({name} is not a CUDA "
+                                      "(ROCm) tensor)")
+    a = None if a is None or len(a) == 0 else a.unsqueeze(0)
+    b = None if b is None or len(b) == 0 else b.unsqueeze(0)
+    warm = None if warmstart is None else (warmstart[0].unsqueeze(0), warmstart[1].unsqueeze(0))
+    kw = dict(reg=reg, method=method, num_iter_max=numItermax, stop_thr=stopThr, warmstart=warm, **params)
+    if cost:
+        loss, T, log_u, log_v, alpha, beta, info, errs, extra = ops.sinkhorn_ext_loss(M.unsqueeze(0), a, b, return_plan=True, **kw)
+    else:
+        T, loss, log_u, log_v, alpha, beta, info, errs, extra = ops.sinkhorn_ext_batched(M.unsqueeze(0), a, b, **kw)
+    res = loss[0] if cost else T[0]
+    niter, flags, nchk, last = info[0].tolist()
+    if method == "sinkhorn_epsilon_scaling":
+        _sweeps, _nabs, nan_exits, nan_iter = extra[0].tolist()
+        if nan_exits:
+            warnings.warn("Numerical errors at iteration %d" % nan_iter)
+        if last:                                                           # inner solves that ran to numInnerItermax (the reference calls them with warn=True)
+            warnings.warn(_NOT_CONVERGED)
+        if not flags & 1 and warn:
+            warnings.warn(_NOT_CONVERGED)
+    elif flags & 2:
+        warnings.warn("Numerical errors at iteration %d" % niter)
+    elif not flags & 1 and warn:
+        warnings.warn(_NOT_CONVERGED)
+    if not log:
+        return res
+    if method == "greenkhorn":
+        return res, {"n_iter": niter, "u": torch.exp(log_u[0]), "v": torch.exp(log_v[0])}
+    al, be = alpha[0], beta[0]
+    log_ = {"err": [errs[0, i] for i in range(nchk)], "alpha": al, "beta": be, "warmstart": (al, be)}
+    if method == "sinkhorn_stabilized":
+        log_.update(n_iter=niter, logu=log_u[0], logv=log_v[0])
+    else:
+        log_["niter"] = niter
+    return res, log_
+
+
+def greenkhorn(a, b, M, reg, numItermax=10000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None):
+    """The reference's greenkhorn (sinkhorn.py:453-532; Altschuler et al. 2017): T [n1,n2]; log=True: (T, {"n_iter", "u", "v"}).
+    warmstart = (log u, log v)."""
+    return _solve_ext(a, b, M, reg, "greenkhorn", numItermax, stopThr, log, warn, warmstart)
+
+
+def sinkhorn_stabilized(a, b, M, reg, numItermax=1000, tau=1e3, stopThr=1e-9, warmstart=None, verbose=False, print_period=20, log=False, warn=True,
+                        **kwargs):
+    """The reference's sinkhorn_stabilized (sinkhorn.py:535-685; Schmitzer 2016) for a 1-D b: T [n1,n2]; log=True: (T, {"err", "n_iter", "logu",
+    "logv", "alpha", "beta", "warmstart"}).  warmstart = (alpha, beta) in cost units.  The NaN exit (previous u, v returned, "Numerical errors at
+    iteration %d") is decided on fp64 values."""
+    return _solve_ext(a, b, M, reg, "sinkhorn_stabilized", numItermax, stopThr, log, warn, warmstart, tau=tau, print_period=print_period)
+
+
+def sinkhorn_epsilon_scaling(a, b, M, reg, numItermax=100, epsilon0=1e4, numInnerItermax=100, tau=1e3, stopThr=1e-9, warmstart=None, verbose=False,
+                             print_period=10, log=False, warn=True, **kwargs):
+    """The reference's sinkhorn_epsilon_scaling (sinkhorn.py:688-786): T [n1,n2]; log=True: (T, {"err", "alpha", "beta", "warmstart", "niter"}).
+    The whole outer loop runs inside one launch.  warmstart = (alpha, beta) in cost units; numItermax is raised to 35 as in the reference."""
+    return _solve_ext(a, b, M, reg, "sinkhorn_epsilon_scaling", numItermax, stopThr, log, warn, warmstart, tau=tau, print_period=print_period,
+                      epsilon0=epsilon0, num_inner_iter_max=numInnerItermax)
+
+
 def sinkhorn(a, b, M, reg, method="sinkhorn_log", numItermax=100, stopThr=1e-5, verbose=False, log=False, warn=True, warmstart=None, **kwargs):
     """The reference's sinkhorn (sinkhorn.py:6-91): the entropic OT plan between the histograms a [n1] and b [n2] (empty: uniform) for the cost
-    M [n1,n2], by method "sinkhorn_log" or "sinkhorn" (Knopp).  warmstart = (log_u, log_v) for both.  See the module docstring for the deviations."""
+    M [n1,n2], by method "sinkhorn_log", "sinkhorn" (Knopp), "greenkhorn", "sinkhorn_stabilized" or "sinkhorn_epsilon_scaling" (the last two take
+    tau, print_period, and epsilon0, numInnerItermax, through **kwargs).  warmstart: see the module docstring, also for the deviations."""
     m = str(method).lower()
-    if m in _UNBUILT:
-        raise NotImplementedError(f"method='{method}' is not implemented on this backend: use 'sinkhorn_log' or 'sinkhorn'")
+    if m == "greenkhorn":                                                  # (the reference hands greenkhorn no **kwargs)
+        return greenkhorn(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, log=log, warn=warn, warmstart=warmstart)
+    if m == "sinkhorn_stabilized":
+        return sinkhorn_stabilized(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, warmstart=warmstart, log=log, warn=warn, **kwargs)
+    if m == "sinkhorn_epsilon_scaling":
+        return sinkhorn_epsilon_scaling(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, warmstart=warmstart, log=log, warn=warn, **kwargs)
     if m not in ops.SINKHORN_METHODS:
         raise ValueError("Unknown method '%s'." % method)
     return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart)
@@ -88,7 +165,8 @@ def sinkhorn2(a, b, M, reg, method="sinkhorn", numItermax=1000, stopThr=1e-9, ve
     solver's log).  It carries the gradient dM = T at the returned plan, held constant; a and b get none."""
     m = str(method).lower()
     if m == "sinkhorn_stabilized":
-        raise NotImplementedError(f"method='{method}' is not implemented on this backend: use 'sinkhorn_log' or 'sinkhorn'")
+        return _solve_ext(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True, tau=kwargs.get("tau", 1e3),
+                          print_period=kwargs.get("print_period", 20))
     if m not in ops.SINKHORN_METHODS:                                      # (the reference's sinkhorn2 knows neither greenkhorn nor epsilon scaling)
         raise ValueError("Unknown method '%s'." % method)
     return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True)

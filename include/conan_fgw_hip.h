@@ -736,6 +736,33 @@ int conan_sinkhorn_fwd(const float *M, const float *a, const float *b, const flo
                        int B, int N1, int N2, long long m_batch_stride, float reg, int method, int num_iter_max, float stop_thr, float *T,
                        float *loss, float *log_u, float *log_v, int *info, float *errs, void *workspace, void *stream);
 
+/* The other three solvers of the reference's sinkhorn dispatcher, same conventions (sinkhorn_ext.hip): method 2 greenkhorn (sinkhorn.py:453-532,
+ * one wavefront per problem), 3 sinkhorn_stabilized (:535-685, 1-D b), 4 sinkhorn_epsilon_scaling (:688-786, the outer loop inside the launch).
+ * M, a, b, n1, n2, m_batch_stride, T, loss as conan_sinkhorn_fwd; the scalars are doubles.  warm_u[B,N1] / warm_v[B,N2] (fp64): the reference's
+ * warm start, (log u, log v) for method 2 and (alpha, beta) in cost units for methods 3 and 4, or NULL.  The potentials are fp64 both ways: those
+ * of epsilon scaling carry an offset of ~epsilon0 log n (4e4 at the defaults), which fp32 would resolve to 2e-3, 2 % of reg = 0.1.  tau: the absorption threshold; print_period: the check
+ * period (method 3: of the sweeps, method 4: of the outer iterations; its inner solves check every 20 sweeps); epsilon0 and
+ * num_inner_iter_max: method 4 only; num_iter_max is raised to 35 for method 4 as the reference does.  The control flow is the reference's on
+ * fp64 values: err <= stop_thr stops (not <), the stabilized NaN exit restores the previous u, v.
+ * Outputs (all but T may be NULL): log_u[B,N1], log_v[B,N2] = log u, log v (method 2), alpha / reg + log u, beta / reg + log v (3; 4: of the
+ * last inner solve at its reg_i); alpha[B,N1], beta[B,N2] (fp64) = the reference's log["alpha"], log["beta"] (zeros for method 2);
+ * info[B,4] = {the reference's iteration index at exit, flags (bit 0: stopped on the threshold, bit 1: the NaN exit; method 4: of any inner
+ * solve), checks executed, absorptions (method 4: inner solves that ran to num_inner_iter_max)};
+ * errs[B, conan_sinkhorn_ext_nerr(method, num_iter_max, print_period)] the error list, NaN where not executed (method 2 has none: nerr = 0);
+ * extra[B,4] = {sweeps or steps executed (method 4: summed over the inner solves), absorptions (method 4: of all inner solves), inner solves
+ * that took the NaN exit, the inner iteration index of the last of them}.
+ * The matrix is LDS-resident when (16 + 4 N1 + 4 N2 + N1 (N2 | 1)) * 8 bytes <= 160 KiB (conan_sinkhorn_ext_lds_resident), else streamed from
+ * the workspace (conan_sinkhorn_ext_workspace_bytes; 0 for refused sizes).  CONAN_E_BADARG before any launch for what conan_sinkhorn_fwd
+ * refuses, a method outside 2..4, a NaN stop_thr, and for methods 3, 4 tau <= 0 or NaN, print_period <= 0, for method 4 num_inner_iter_max <= 0
+ * or an epsilon0 that is not finite. */
+long long conan_sinkhorn_ext_workspace_bytes(int B, int N1, int N2);
+int conan_sinkhorn_ext_lds_resident(int n1, int n2);
+int conan_sinkhorn_ext_nerr(int method, int num_iter_max, int print_period);
+int conan_sinkhorn_ext_fwd(const float *M, const float *a, const float *b, const double *warm_u, const double *warm_v, const int *n1, const int *n2,
+                           int B, int N1, int N2, long long m_batch_stride, double reg, int method, int num_iter_max, double stop_thr, double tau,
+                           int print_period, double epsilon0, int num_inner_iter_max, float *T, float *loss, float *log_u, float *log_v,
+                           double *alpha, double *beta, int *info, float *errs, int *extra, void *workspace, void *stream);
+
 /* dYs[b,s,j,:] = lambdas[s] * sum_i T[b,s,i,j] * (1/p[b,i]) * dY[b,i,:]  — the whole backward of the block given the
  * saved couplings (the reference solves them under torch.no_grad(), barycenter.py:120). */
 int conan_fgw_barycenter_bwd(const float *T, const float *dY, const float *p, const float *lambdas, int B, int K,
