@@ -172,6 +172,9 @@ SIGNATURES = {
     "conan_sinkhorn_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
     "conan_sinkhorn_lds_resident": (c_int, [c_int, c_int]),
     "conan_sinkhorn_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_ll, c_float, c_int, c_int, c_float] + [_P] * 8),
+    "conan_sinkhorn_bwd_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "conan_sinkhorn_bwd_lds_resident": (c_int, [c_int, c_int]),
+    "conan_sinkhorn_bwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_ll, c_float, c_int, c_int] + [_P] * 9),
     "conan_sinkhorn_ext_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
     "conan_sinkhorn_ext_lds_resident": (c_int, [c_int, c_int]),
     "conan_sinkhorn_ext_nerr": (c_int, [c_int, c_int, c_int]),

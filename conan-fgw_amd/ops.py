@@ -1240,9 +1240,10 @@ def _sinkhorn_tensor(t, name, shapes, dtype=f32, keep_graph=False):
     return _c((t if keep_graph else t.detach()).to(dtype))
 
 
-def _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=False):
+def _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=False, keep_vec_graph=False):
     """The checked, contiguous operands of conan_sinkhorn_fwd -> (M, a, b, wu, wv, n1, n2, (B, N1, N2, method code)).  M [B,N1,N2], or [N1,N2]
-    shared by the B problems of a / b / n1 / n2 (m_batch_stride = 0)."""
+    shared by the B problems of a / b / n1 / n2 (m_batch_stride = 0).  keep_graph: M stays attached to autograd; keep_vec_graph: a, b and
+    warmstart[0] too (the unrolled gradient)."""
     if method not in SINKHORN_METHODS:
         raise ValueError("Unknown method '%s'." % method)
     if not torch.is_tensor(M) or not M.is_cuda:
@@ -1255,9 +1256,9 @@ def _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=False):
     else:
         B = next((int(t.shape[0]) for t in (b, a, n1, n2) if t is not None and t.dim() == (1 if t is n1 or t is n2 else 2)), 1)
     M = _sinkhorn_tensor(M, "M", [(B, N1, N2), (N1, N2)], keep_graph=keep_graph)
-    vec = lambda t, name, n: None if t is None else _sinkhorn_tensor(t, name, [(B, n)] + ([(n,)] if B == 1 else []))
-    a, b = vec(a, "a", N1), vec(b, "b", N2)
-    wu, wv = (None, None) if warmstart is None else (vec(warmstart[0], "warmstart[0]", N1), vec(warmstart[1], "warmstart[1]", N2))
+    vec = lambda t, name, n, keep=False: None if t is None else _sinkhorn_tensor(t, name, [(B, n)] + ([(n,)] if B == 1 else []), keep_graph=keep)
+    a, b = vec(a, "a", N1, keep_vec_graph), vec(b, "b", N2, keep_vec_graph)
+    wu, wv = (None, None) if warmstart is None else (vec(warmstart[0], "warmstart[0]", N1, keep_vec_graph), vec(warmstart[1], "warmstart[1]", N2))
     n1 = None if n1 is None else _sinkhorn_tensor(n1, "n1", [(B,)], i32)
     n2 = None if n2 is None else _sinkhorn_tensor(n2, "n2", [(B,)], i32)
     return M, a, b, wu, wv, n1, n2, (B, N1, N2, SINKHORN_METHODS[method])
@@ -1293,8 +1294,9 @@ def sinkhorn_batched(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] 
     return _sinkhorn_fwd(M, a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr)
 
 
-def _sinkhorn_list_stack(Ms, as_, bs, warmstarts, container, keep_graph=False):
-    """Ragged problems in one container [B,N1,N2] (default: the largest n1 and n2) with their sizes on the device."""
+def _sinkhorn_list_stack(Ms, as_, bs, warmstarts, container, keep_graph=False, keep_vec_graph=False):
+    """Ragged problems in one container [B,N1,N2] (default: the largest n1 and n2) with their sizes on the device.  keep_graph / keep_vec_graph
+    as _sinkhorn_prepare."""
     B = len(Ms)
     if B == 0:
         raise ValueError("Ms must be a non-empty list")
@@ -1324,10 +1326,10 @@ def _sinkhorn_list_stack(Ms, as_, bs, warmstarts, container, keep_graph=False):
     if warmstarts is not None and any(w is not None for w in warmstarts):
         if any(w is None for w in warmstarts):
             raise ValueError("warmstarts must hold a warm start for every problem or for none")
-        warm = (stack([w[0] for w in warmstarts], (N1,), 0), stack([w[1] for w in warmstarts], (N2,), 1))
+        warm = (stack([w[0] for w in warmstarts], (N1,), 0, keep=keep_vec_graph), stack([w[1] for w in warmstarts], (N2,), 1))
     n1 = torch.tensor([s[0] for s in sizes], dtype=i32, device=dev)
     n2 = torch.tensor([s[1] for s in sizes], dtype=i32, device=dev)
-    return M, stack(as_, (N1,), 0), stack(bs, (N2,), 1), warm, n1, n2, sizes
+    return M, stack(as_, (N1,), 0, keep=keep_vec_graph), stack(bs, (N2,), 1, keep=keep_vec_graph), warm, n1, n2, sizes
 
 
 def sinkhorn_list(Ms, as_=None, bs=None, *, warmstarts=None, container=None, **params):
@@ -1363,14 +1365,83 @@ class _SinkhornLossFn(torch.autograd.Function):
 
 def sinkhorn_loss(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, *, reg: float, method: str = "sinkhorn_log",
                   num_iter_max: int = 1000, stop_thr: float = 1e-9, warmstart=None, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None,
-                  return_plan: bool = False):
-    """The entropic OT costs sum(M * T) of B problems as a loss: sinkhorn_batched's solve (same arguments, same launch, same bits) -> loss [B],
-    which carries the gradient at the RETURNED plan, held constant, to M: dM = gout * T.  This is not the reference's unrolled gradient through
-    every Sinkhorn sweep.  a, b and the warm start get none; no double backward; no host synchronisation.  return_plan: (loss, T, log_u, log_v,
-    info, errs), all but the first without gradient."""
+                  return_plan: bool = False, grad: str = "plan"):
+    """The entropic OT costs sum(M * T) of B problems as a loss: sinkhorn_batched's solve (same arguments, same launch, same bits) -> loss [B].
+    grad="plan" (default): it carries the gradient at the RETURNED plan, held constant, to M: dM = gout * T; a, b and the warm start get none.
+    grad="unrolled": the reference's gradient through every Sinkhorn sweep to M, a, b and warmstart[0] (sinkhorn_unrolled; with return_plan the
+    plan carries it too).  No double backward; no host synchronisation.  return_plan: (loss, T, log_u, log_v, info, errs)."""
+    if grad == "unrolled":
+        T, loss, log_u, log_v, info, errs = sinkhorn_unrolled(M, a, b, reg=reg, method=method, num_iter_max=num_iter_max, stop_thr=stop_thr,
+                                                              warmstart=warmstart, n1=n1, n2=n2)
+        return (loss, T, log_u, log_v, info, errs) if return_plan else loss
+    if grad != "plan":
+        raise ValueError("grad must be 'plan' or 'unrolled', not %r" % (grad,))
     Mp, a, b, wu, wv, n1, n2, (B, N1, N2, code) = _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=True)
     out = _SinkhornLossFn.apply(Mp, lambda: _sinkhorn_fwd(Mp.detach(), a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr))
     return out if return_plan else out[0]
+
+
+# --------------------------------------------------------------------------- the reference's unrolled gradient (sinkhorn_grad.hip)
+class _SinkhornUnrolledFn(torch.autograd.Function):
+    """sinkhorn_batched's launch with conan_sinkhorn_bwd as its backward: the gradient through the S executed sweeps, as the reference's autograd
+    delivers it, from the cotangents of T and loss to M, a, b and warmstart[0].  The backward is ONE launch that recomputes the sweeps from the
+    saved inputs (nothing but the inputs and info is kept from the forward).  No double backward, no host synchronisation."""
+    @staticmethod
+    def forward(ctx, M, a, b, wu, wv, n1, n2, dims, reg, num_iter_max, stop_thr):
+        B, N1, N2, code = dims
+        T, loss, log_u, log_v, info, errs = _sinkhorn_fwd(M, a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr)
+        ctx.save_for_backward(M, a, b, wu, wv, n1, n2, info)
+        ctx.dims, ctx.reg, ctx.num_iter_max = dims, float(reg), int(num_iter_max)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(log_u, log_v, info, errs)
+        return T, loss, log_u, log_v, info, errs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gT, gloss, *_):
+        M, a, b, wu, wv, n1, n2, info = ctx.saved_tensors
+        B, N1, N2, code = ctx.dims
+        if gT is None and gloss is None:
+            return (None,) * 11
+        dev = M.device
+        gT = None if gT is None else _c(gT.to(f32))
+        gloss = None if gloss is None else _c(gloss.to(f32))
+        need = ctx.needs_input_grad
+        dM = torch.empty(B, N1, N2, dtype=f32, device=dev)
+        da = torch.empty(B, N1, dtype=f32, device=dev) if a is not None and need[1] else None
+        db = torch.empty(B, N2, dtype=f32, device=dev) if b is not None and need[2] else None
+        dwu = torch.empty(B, N1, dtype=f32, device=dev) if wu is not None and need[3] else None
+        nbytes = int(lib().conan_sinkhorn_bwd_workspace_bytes(B, N1, N2, ctx.num_iter_max))
+        if nbytes == 0:
+            raise NotImplementedError(f"the unrolled Sinkhorn gradient does not support the container {N1} x {N2}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("conan_sinkhorn_bwd", ptr(M, f32), ptr(a), ptr(b), ptr(wu), ptr(wv), ptr(n1), ptr(n2), B, N1, N2, N1 * N2 if M.dim() == 3 else 0,
+             ctx.reg, code, ctx.num_iter_max, ptr(info), ptr(gloss), ptr(gT), ptr(dM), ptr(da), ptr(db), ptr(dwu), ptr(ws), stream_ptr())
+        like = lambda g, t: None if g is None else g.reshape(t.shape)
+        return ((dM.sum(0) if M.dim() == 2 else dM) if need[0] else None, like(da, a), like(db, b), like(dwu, wu)) + (None,) * 7
+
+
+def sinkhorn_unrolled(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, *, reg: float, method: str = "sinkhorn_log",
+                      num_iter_max: int = 1000, stop_thr: float = 1e-9, warmstart=None, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None):
+    """sinkhorn_batched (same arguments, same ONE launch, same bits) -> (T, loss, log_u, log_v, info, errs), where T and loss carry the
+    reference's gradient through the unrolled Sinkhorn sweeps (its sinkhorn / sinkhorn2 are differentiable torch code) to M, a, b and
+    warmstart[0]: one backward launch (conan_sinkhorn_bwd) that recomputes the executed sweeps, runs them in reverse and forms dM from the
+    stored vector histories.  A 2-D shared M gets the sum over the batch; a / b given as None (uniform) get none; warmstart[1] gets none (the
+    first column pass overwrites v; the reference's .grad is None there too); log_u, log_v, info, errs are not differentiable; the stop decision
+    carries no gradient.  An entry a_i = 0 (b_j = 0) gets gradient 0 and contributes nothing (the reference: NaN at that entry for
+    sinkhorn_log, NaN everywhere for Knopp).  The backward's workspace is (2 num_iter_max + 1) (N1 + N2) * 8 bytes per problem (1 MB per
+    33 x 33 problem at num_iter_max = 1000): the caller chooses the cap.  No double backward, no host synchronisation in either direction."""
+    M, a, b, wu, wv, n1, n2, dims = _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=True, keep_vec_graph=True)
+    return _SinkhornUnrolledFn.apply(M, a, b, wu, wv, n1, n2, dims, reg, num_iter_max, stop_thr)
+
+
+def sinkhorn_unrolled_list(Ms, as_=None, bs=None, *, warmstarts=None, container=None, **params):
+    """sinkhorn_unrolled for problems of different sizes in ONE launch each way (arguments and result as sinkhorn_list): the plans and loss
+    carry the unrolled gradient to the entries of Ms, as_, bs and to warmstarts[k][0]."""
+    M, a, b, warm, n1, n2, sizes = _sinkhorn_list_stack(Ms, as_, bs, warmstarts, container, keep_graph=True, keep_vec_graph=True)
+    T, loss, lu, lv, info, errs = sinkhorn_unrolled(M, a, b, warmstart=warm, n1=n1, n2=n2, **params)
+    return ([T[k, :s[0], :s[1]] for k, s in enumerate(sizes)], loss, [lu[k, :s[0]] for k, s in enumerate(sizes)],
+            [lv[k, :s[1]] for k, s in enumerate(sizes)], info, errs)
 
 
 # ------------------------------------------------------------------------- the reference's other three Sinkhorn solvers (sinkhorn_ext.hip)

@@ -13,9 +13,17 @@ shared M); CPU tensors (the solve runs on the GPU only).  `verbose` is ignored. 
 once, with the last one's iteration, when inner solves left on numerical errors.  Outputs are fp32 (`alpha`, `beta` of the last two methods:
 fp64, since epsilon scaling's potentials carry an offset of ~epsilon0 log n that fp32 resolves to 2e-3 only); the iteration runs in fp64, so iteration
 counts, error lists, absorptions and the numerical-errors exits follow the reference's fp64 run, not its fp32 run (fp32 exp underflows earlier,
-and an fp32 run cannot reach stopThr = 1e-9).  The plan carries no gradient; `sinkhorn2`'s value carries the gradient to M at the returned plan,
-held constant (the project's fixed-plan convention, fgw.fgw_distance's), not the reference's gradient through the unrolled iterations; a, b and
-the warm start get none.
+and an fp32 run cannot reach stopThr = 1e-9).
+
+Gradients.  `sinkhorn`, `sinkhorn_log`, `sinkhorn_knopp`, `sinkhorn2` and `wasserstein_pairwise_distances` take grad="plan" (default) or
+grad="unrolled".  "plan": the plan carries no gradient; `sinkhorn2`'s value carries the gradient to M at the returned plan, held constant (the
+project's fixed-plan convention, fgw.fgw_distance's); a, b and the warm start get none.  "unrolled": the reference's gradient, autograd through
+every executed Sinkhorn sweep, from one backward launch (csrc/sinkhorn_grad.hip): the returned plan requires grad, `sinkhorn2`'s value carries
+the full gradient, and M, a, b and warmstart[0] receive it (warmstart[1] gets none, as in the reference: the first column pass overwrites v).
+Deviation: an entry a_i = 0 (b_j = 0) gets gradient 0 and contributes nothing, where the reference's sinkhorn_log gives NaN at that entry and
+its Knopp NaN everywhere.  The backward keeps (2 numItermax + 1) (n1 + n2) fp64 values per problem (1 MB for 33 x 33 at numItermax = 1000).
+grad="unrolled" with "greenkhorn", "sinkhorn_stabilized" or "sinkhorn_epsilon_scaling" raises NotImplementedError; any other value of grad
+raises ValueError.  No double backward.
 """
 from __future__ import annotations
 
@@ -32,8 +40,17 @@ _NOT_CONVERGED = ("Sinkhorn did not converge. You might want to increase the num
                   "parameter `reg`.")
 
 
-def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost=False):
+def _check_grad(grad, ext_method=None):
+    if grad not in ("plan", "unrolled"):
+        raise ValueError("grad must be 'plan' or 'unrolled', not %r" % (grad,))
+    if grad == "unrolled" and ext_method is not None:
+        raise NotImplementedError(f"grad='unrolled' is not implemented for method='{ext_method}': only 'sinkhorn_log' and 'sinkhorn' have the "
+                                  "unrolled gradient")
+
+
+def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost=False, grad="plan"):
     """One problem through ops (B = 1) with the reference's return value and warnings (one host synchronisation, as fgw._pair_solve)."""
+    _check_grad(grad)
     if b is not None and torch.is_tensor(b) and b.dim() > 1:
         raise NotImplementedError("several histograms at once (a 2-D b) are not implemented: solve them one by one, or as a batch with a shared M "
                                   "through ops.sinkhorn_batched")
@@ -45,7 +62,9 @@ def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost
     b = None if b is None or len(b) == 0 else b.unsqueeze(0)
     warm = None if warmstart is None else (warmstart[0].unsqueeze(0), warmstart[1].unsqueeze(0))
     kw = dict(reg=reg, method=method, num_iter_max=numItermax, stop_thr=stopThr, warmstart=warm)
-    if cost:
+    if grad == "unrolled":
+        T, loss, log_u, log_v, info, errs = ops.sinkhorn_unrolled(M.unsqueeze(0), a, b, **kw)
+    elif cost:
         loss, T, log_u, log_v, info, errs = ops.sinkhorn_loss(M.unsqueeze(0), a, b, return_plan=True, **kw)
     else:
         T, loss, log_u, log_v, info, errs = ops.sinkhorn_batched(M.unsqueeze(0), a, b, **kw)
@@ -66,15 +85,15 @@ def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost
     return res, log_
 
 
-def sinkhorn_knopp(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, **kwargs):
+def sinkhorn_knopp(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, grad="plan", **kwargs):
     """The reference's sinkhorn_knopp (sinkhorn.py:207-315): T [n1,n2]; log=True: (T, {"err", "niter", "u", "v"}).  The numerical-errors exit
     (a zero K^T u, a NaN or Inf in u or v: the previous u, v are returned, with the reference's warning) is decided on fp64 values."""
-    return _solve(a, b, M, reg, "sinkhorn", numItermax, stopThr, log, warn, warmstart)
+    return _solve(a, b, M, reg, "sinkhorn", numItermax, stopThr, log, warn, warmstart, grad=grad)
 
 
-def sinkhorn_log(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, **kwargs):
+def sinkhorn_log(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, grad="plan", **kwargs):
     """The reference's sinkhorn_log (sinkhorn.py:318-450): T [n1,n2]; log=True: (T, {"err", "niter", "log_u", "log_v", "u", "v"})."""
-    return _solve(a, b, M, reg, "sinkhorn_log", numItermax, stopThr, log, warn, warmstart)
+    return _solve(a, b, M, reg, "sinkhorn_log", numItermax, stopThr, log, warn, warmstart, grad=grad)
 
 
 def _solve_ext(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost=False, **params):
@@ -133,6 +152,7 @@ def sinkhorn_stabilized(a, b, M, reg, numItermax=1000, tau=1e3, stopThr=1e-9, wa
     """The reference's sinkhorn_stabilized (sinkhorn.py:535-685; Schmitzer 2016) for a 1-D b: T [n1,n2]; log=True: (T, {"err", "n_iter", "logu",
     "logv", "alpha", "beta", "warmstart"}).  warmstart = (alpha, beta) in cost units.  The NaN exit (previous u, v returned, "Numerical errors at
     iteration %d") is decided on fp64 values."""
+    _check_grad(kwargs.get("grad", "plan"), "sinkhorn_stabilized")        # (the signature stays the reference's: grad arrives in **kwargs)
     return _solve_ext(a, b, M, reg, "sinkhorn_stabilized", numItermax, stopThr, log, warn, warmstart, tau=tau, print_period=print_period)
 
 
@@ -140,15 +160,19 @@ def sinkhorn_epsilon_scaling(a, b, M, reg, numItermax=100, epsilon0=1e4, numInne
                              print_period=10, log=False, warn=True, **kwargs):
     """The reference's sinkhorn_epsilon_scaling (sinkhorn.py:688-786): T [n1,n2]; log=True: (T, {"err", "alpha", "beta", "warmstart", "niter"}).
     The whole outer loop runs inside one launch.  warmstart = (alpha, beta) in cost units; numItermax is raised to 35 as in the reference."""
+    _check_grad(kwargs.get("grad", "plan"), "sinkhorn_epsilon_scaling")
     return _solve_ext(a, b, M, reg, "sinkhorn_epsilon_scaling", numItermax, stopThr, log, warn, warmstart, tau=tau, print_period=print_period,
                       epsilon0=epsilon0, num_inner_iter_max=numInnerItermax)
 
 
-def sinkhorn(a, b, M, reg, method="sinkhorn_log", numItermax=100, stopThr=1e-5, verbose=False, log=False, warn=True, warmstart=None, **kwargs):
+def sinkhorn(a, b, M, reg, method="sinkhorn_log", numItermax=100, stopThr=1e-5, verbose=False, log=False, warn=True, warmstart=None, grad="plan",
+             **kwargs):
     """The reference's sinkhorn (sinkhorn.py:6-91): the entropic OT plan between the histograms a [n1] and b [n2] (empty: uniform) for the cost
     M [n1,n2], by method "sinkhorn_log", "sinkhorn" (Knopp), "greenkhorn", "sinkhorn_stabilized" or "sinkhorn_epsilon_scaling" (the last two take
-    tau, print_period, and epsilon0, numInnerItermax, through **kwargs).  warmstart: see the module docstring, also for the deviations."""
+    tau, print_period, and epsilon0, numInnerItermax, through **kwargs).  warmstart and grad ("plan" / "unrolled"): see the module docstring,
+    also for the deviations."""
     m = str(method).lower()
+    _check_grad(grad, m if m in ops.SINKHORN_EXT_METHODS else None)
     if m == "greenkhorn":                                                  # (the reference hands greenkhorn no **kwargs)
         return greenkhorn(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, log=log, warn=warn, warmstart=warmstart)
     if m == "sinkhorn_stabilized":
@@ -157,27 +181,33 @@ def sinkhorn(a, b, M, reg, method="sinkhorn_log", numItermax=100, stopThr=1e-5, 
         return sinkhorn_epsilon_scaling(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, warmstart=warmstart, log=log, warn=warn, **kwargs)
     if m not in ops.SINKHORN_METHODS:
         raise ValueError("Unknown method '%s'." % method)
-    return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart)
+    return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, grad=grad)
 
 
-def sinkhorn2(a, b, M, reg, method="sinkhorn", numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=False, warmstart=None, **kwargs):
+def sinkhorn2(a, b, M, reg, method="sinkhorn", numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=False, warmstart=None, grad="plan",
+              **kwargs):
     """The reference's sinkhorn2 (sinkhorn.py:94-204): the transport cost sum(M * T) of the entropic plan as a 0-d tensor (log=True: with the
-    solver's log).  It carries the gradient dM = T at the returned plan, held constant; a and b get none."""
+    solver's log).  grad="plan": it carries the gradient dM = T at the returned plan, held constant; a and b get none.  grad="unrolled": the
+    reference's gradient through the sweeps to M, a, b and warmstart[0]."""
     m = str(method).lower()
+    _check_grad(grad, m if m == "sinkhorn_stabilized" else None)
     if m == "sinkhorn_stabilized":
         return _solve_ext(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True, tau=kwargs.get("tau", 1e3),
                           print_period=kwargs.get("print_period", 20))
     if m not in ops.SINKHORN_METHODS:                                      # (the reference's sinkhorn2 knows neither greenkhorn nor epsilon scaling)
         raise ValueError("Unknown method '%s'." % method)
-    return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True)
+    return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True, grad=grad)
 
 
-def wasserstein_pairwise_distances(Ys: Sequence[Tensor], ps=None, reg=0.1, method="sinkhorn_log", numItermax=100, stopThr=1e-5) -> Tensor:
+def wasserstein_pairwise_distances(Ys: Sequence[Tensor], ps=None, reg=0.1, method="sinkhorn_log", numItermax=100, stopThr=1e-5,
+                                   grad="plan") -> Tensor:
     """The entropic Wasserstein cost matrix of G feature clouds (the conformers of an ensemble), the structure-free (alpha = 0) sibling of
     fgw.fgw_pairwise_distances: Ys[g] [n_g,d], ps[g] weights or None (uniform) -> [G,G], symmetric with a zero diagonal.  The G (G - 1) / 2 pairs
     a < b are solved in ONE launch (per-problem sizes when the clouds differ in size) with M = fgw.feature_cost(Ys[a], Ys[b]); entry (a, b) is
     sinkhorn2(ps[a], ps[b], M, reg, method=method, numItermax=numItermax, stopThr=stopThr), bit for bit.  When any of Ys requires grad the result
-    carries gradients to them: sinkhorn2's fixed-plan gradient to every M, and torch's through feature_cost.  ps get none."""
+    carries gradients to them: sinkhorn2's fixed-plan gradient to every M, and torch's through feature_cost; ps get none.  grad="unrolled":
+    sinkhorn2's unrolled gradient instead, to every M and to ps."""
+    _check_grad(grad)
     G = len(Ys)
     if ps is not None and len(ps) != G:
         raise ValueError("Ys and ps must have one entry per cloud")
@@ -193,12 +223,13 @@ def wasserstein_pairwise_distances(Ys: Sequence[Tensor], ps=None, reg=0.1, metho
         return out
     Ms = [feature_cost(Ys[i], Ys[j]) for i, j in zip(ia, ib)]
     pick = lambda idx: None if ps is None else [ps[i] for i in idx]
-    kw = dict(reg=reg, method=m, num_iter_max=numItermax, stop_thr=stopThr)
+    kw = dict(reg=reg, method=m, num_iter_max=numItermax, stop_thr=stopThr, grad=grad)
+    unrolled = grad == "unrolled"
     if len({int(y.shape[0]) for y in Ys}) == 1:
-        st = lambda ts: None if ts is None else torch.stack([t.detach().to(torch.float32) for t in ts])
+        st = lambda ts: None if ts is None else torch.stack([(t if unrolled else t.detach()).to(torch.float32) for t in ts])
         cost = ops.sinkhorn_loss(torch.stack(Ms), st(pick(ia)), st(pick(ib)), **kw)
     else:
-        M, a, b, _w, n1, n2, _sizes = ops._sinkhorn_list_stack(Ms, pick(ia), pick(ib), None, None, keep_graph=True)
+        M, a, b, _w, n1, n2, _sizes = ops._sinkhorn_list_stack(Ms, pick(ia), pick(ib), None, None, keep_graph=True, keep_vec_graph=unrolled)
         cost = ops.sinkhorn_loss(M, a, b, n1=n1, n2=n2, **kw)
     out[ia, ib] = cost
     out[ib, ia] = cost

@@ -736,6 +736,27 @@ int conan_sinkhorn_fwd(const float *M, const float *a, const float *b, const flo
                        int B, int N1, int N2, long long m_batch_stride, float reg, int method, int num_iter_max, float stop_thr, float *T,
                        float *loss, float *log_u, float *log_v, int *info, float *errs, void *workspace, void *stream);
 
+/* The reference's gradient through the unrolled sweeps of conan_sinkhorn_fwd (sinkhorn_grad.hip): autograd's result for M, a, b and
+ * warmstart[0] of sinkhorn / sinkhorn2, one workgroup per problem, one launch.  M, a, b, warm_u, warm_v, n1, n2, B, N1, N2, m_batch_stride,
+ * reg, method, num_iter_max: exactly what the forward was called with; info[B,4]: what it returned.  The kernel recomputes the
+ * S = info[0] + 1 - ((info[1] >> 1) & 1) sweeps the forward executed (clamped to [0, num_iter_max]; on the exact log-domain path when flag bit
+ * 2 is set), runs them in reverse and forms the matrix gradient as one product over the stored vector histories.
+ * Cotangents: gloss[B] of loss = sum(M o T) and gT[B,N1,N2] of the plan, either may be NULL (zero), not both.
+ * Outputs: dM[B,N1,N2] (per problem also when M is shared: the caller sums), da[B,N1], db[B,N2], dwu[B,N1] = d warm_u (da, db, dwu may be
+ * NULL).  warm_v gets no gradient (the first column pass overwrites v).  An entry a_i = 0 (b_j = 0) contributes nothing and its own da_i
+ * (db_j) is 0 (the reference gives NaN there: sinkhorn_log at that entry, Knopp everywhere).  Everything outside a problem's block is zero.
+ * fp32 in and out, fp64 inside, every sum in a fixed order, no atomics: the same bits alone, in any batch, position and container, resident
+ * or streamed.  K is LDS-resident when (16 + 5 N1 + 5 N2 + N1 (N2 | 1)) * 8 + 16384 bytes <= 160 KiB (conan_sinkhorn_bwd_lds_resident, host
+ * only, e.g. 130 x 130), else streamed from the workspace.
+ * Workspace: conan_sinkhorn_bwd_workspace_bytes (host only; 0 for refused sizes) = B * roundup256(((2 num_iter_max + 1) (N1 + N2) +
+ * [streamed] N1 (N2 | 1)) * 8) bytes: 1.06 MB per 33 x 33 problem at num_iter_max = 1000.  The caller chooses the cap.
+ * CONAN_E_BADARG before any launch for a null M / info / dM / workspace, both cotangents null, and whatever conan_sinkhorn_fwd refuses. */
+long long conan_sinkhorn_bwd_workspace_bytes(int B, int N1, int N2, int num_iter_max);
+int conan_sinkhorn_bwd_lds_resident(int n1, int n2);
+int conan_sinkhorn_bwd(const float *M, const float *a, const float *b, const float *warm_u, const float *warm_v, const int *n1, const int *n2,
+                       int B, int N1, int N2, long long m_batch_stride, float reg, int method, int num_iter_max, const int *info,
+                       const float *gloss, const float *gT, float *dM, float *da, float *db, float *dwu, void *workspace, void *stream);
+
 /* The other three solvers of the reference's sinkhorn dispatcher, same conventions (sinkhorn_ext.hip): method 2 greenkhorn (sinkhorn.py:453-532,
  * one wavefront per problem), 3 sinkhorn_stabilized (:535-685, 1-D b), 4 sinkhorn_epsilon_scaling (:688-786, the outer loop inside the launch).
  * M, a, b, n1, n2, m_batch_stride, T, loss as conan_sinkhorn_fwd; the scalars are doubles.  warm_u[B,N1] / warm_v[B,N2] (fp64): the reference's
