@@ -2,7 +2,8 @@
 (conan_fgw/src/model/fgw/barycenter.py:7-31 `fgw_barycenters`, :393-399 `normalize_tensor`; bregman.py:8-279 `fgw`, `fgw_projected`,
 `fgw_bregman` — the coupling solve between two attributed graphs on its own, with `fgw_distance`, its differentiable distance, and
 `fgw_pairwise_distances` over an ensemble on top; barycenter.py:228-390 `fused_ACC_torch`, `fgw_barycenters_BAPG` — FGWMixup's accelerated
-mirror descent and the barycenter around it, forward only: see their docstrings for the deviations).
+mirror descent and the barycenter around it, with `fgw_mixup_distance`, the differentiable distance of that solve; the barycenter and the
+distance carry gradients at the solved couplings, held constant: see their docstrings for this and the other deviations).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
 barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
@@ -166,10 +167,11 @@ def fused_ACC_torch(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-
     """FGWMixup's coupling solve between two attributed graphs, the reference's fused_ACC_torch (barycenter.py:228-256): accelerated mirror
     descent on X from a b^T (or the given X), at most `epoch` epochs, stopped when the objective's relative change between two checks (every
     10th epoch) falls below eps -> (X, obj_list).  M [n1,n2], A [n1,n1], B [n2,n2] (any sizes: n1 != n2 is embedded with massless nodes).
-    Deviations from the reference: a / b given as None mean uniform weights (the reference forms a dot product there); no gradient is carried;
-    the run is an fp64 iteration on the fp32 inputs, so counts and values follow the reference's fp64 run; a weight that is exactly ZERO marks
-    an absent node whose entries stay zero (the reference lifts them by 1e-10 every epoch).  A NaN result (exp under- / overflow at small rho)
-    is the reference's NaN.  Runs on the GPU only."""
+    Deviations from the reference: a / b given as None mean uniform weights (the reference forms a dot product there); the plan carries no
+    gradient (the reference's would unroll every epoch; to train through the solve use fgw_mixup_distance, the gradient of the distance at the
+    returned plan); the run is an fp64 iteration on the fp32 inputs, so counts and values follow the reference's fp64 run; a weight that is exactly
+    ZERO marks an absent node whose entries stay zero (the reference lifts them by 1e-10 every epoch).  A NaN result (exp under- / overflow at
+    small rho) is the reference's NaN.  Runs on the GPU only."""
     for name, t in (("M", M), ("A", A), ("B", B), ("a", a), ("b", b), ("X", X)):
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"fused_ACC_torch runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
@@ -177,6 +179,27 @@ def fused_ACC_torch(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-
     Xo, objs, info = ops.fgw_acc_pair_batched(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps)
     stored = int(info[0, 1].item())
     return Xo[0], [objs[0, k] for k in range(stored)]
+
+
+def fgw_mixup_distance(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-5, rho=1e-1, log=False):
+    """The FGWMixup distance of two attributed graphs as a differentiable value: fused_ACC_torch's arguments, defaults and solve, and the
+    distance the reference's commented lines describe (barycenter.py:348-350) at the plan X that solve returns,
+        (1 - alpha) <M, X> + alpha (<c1, X> - 2 <A X B, X>),   c1 = (A o A) a 1^T + 1 b^T (B o B)
+    (the solve's final objective plus alpha <c1, X>), as a 0-d tensor that carries gradients to M, A, B, a and b.  The gradient is that of this
+    formula at the solve's plan X, held constant — the treatment the barycenter gives its couplings (barycenter.py:120) — and NOT what
+    back-propagating through the reference's fused_ACC_torch gives, which unrolls every epoch into the graph.  X (the start) and the plan get no
+    gradient; there is no double backward.  A finite difference of this function moves the plan, so it does not check this gradient.
+    log=True: (dist, {"T": the plan (no gradient, fused_ACC_torch's bits), "obj_list": fused_ACC_torch's list}).  Runs on the GPU only."""
+    for name, t in (("M", M), ("A", A), ("B", B), ("a", a), ("b", b), ("X", X)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"fgw_mixup_distance runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    one = lambda t: None if t is None else t.unsqueeze(0)
+    dist, Xo, objs, info = ops.fgw_acc_pair_distance(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps,
+                                                     return_plan=True)
+    if not log:
+        return dist[0]
+    stored = int(info[0, 1].item())
+    return dist[0], {"T": Xo[0], "obj_list": [objs[0, k] for k in range(stored)]}
 
 
 def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=None, lambdas=None, loss_fun="square_loss", alpha=0.5,
@@ -187,9 +210,16 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
     which runs the Bregman projections of fgw_bregman.  Same argument names, defaults, ValueErrors, return values and log keys as the
     reference (the log also carries n_outer and n_inner, the outer iterations and the epochs summed over all coupling solves).  Cs may be
     directed.  Input graphs of other sizes are embedded with massless nodes, as in fgw_barycenters.
-    Deviations: ps=None means uniform weights (the reference raises a TypeError); no gradient is carried (the reference differentiates through
-    the unrolled couplings); the run is an fp64 iteration on the fp32 inputs, so iteration counts follow the reference's fp64 run; a weight
-    that is exactly ZERO marks an absent node (the reference lifts its entries by 1e-10 every epoch).  Runs on the GPU only."""
+    Differentiable in the project's fixed-plan convention, the one fgw_barycenters uses: Y and C carry gradients to Ys, Cs, p and lambdas (to
+    init_Y / init_C instead of Ys / Cs under fixed_features / fixed_structure); ps gets none, nor do log["T"], log["Ts_iter"] and log["Ms"].  The
+    gradient is that of the last update steps (update_feature_matrix, update_square_loss / update_kl_loss) at the couplings T[s] of the last outer
+    iteration, held constant — the treatment fgw_barycenters gives its couplings (barycenter.py:120) — and NOT what the reference's
+    fgw_barycenters_BAPG gives under autograd, which back-propagates through all 100 epochs of every fused_ACC_torch call.  There is no double
+    backward.  A finite difference of this function moves the plan, so it does not check this gradient.  Gradients of embedded inputs arrive in
+    the caller's own shapes, and a node without mass receives exactly zero.  A run that ends in NaN (below) gives NaN gradients.
+    Other deviations: ps=None means uniform weights (the reference raises a TypeError); the run is an fp64 iteration on the fp32 inputs, so
+    iteration counts follow the reference's fp64 run; a weight that is exactly ZERO marks an absent node (the reference lifts its entries by
+    1e-10 every epoch); a NaN result (exp under- / overflow at small rho) is the reference's NaN.  Runs on the GPU only."""
     if loss_fun not in ("square_loss", "kl_loss"):
         raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
     if fixed_structure and init_C is None:
@@ -200,8 +230,8 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
     Ys_in = Ys.unbind(0) if torch.is_tensor(Ys) else Ys
     if not all(torch.is_tensor(y) and y.is_cuda for y in Ys_in):
         raise NotImplementedError("fgw_barycenters_BAPG runs on the GPU only: pass CUDA (ROCm) tensors")
-    Ys_l = [y.detach().to(torch.float32) for y in Ys_in]
-    Cs_l = [c.detach().to(torch.float32) for c in (Cs.unbind(0) if torch.is_tensor(Cs) else Cs)]
+    Ys_l = [y.to(torch.float32) for y in Ys_in]
+    Cs_l = [c.to(torch.float32) for c in (Cs.unbind(0) if torch.is_tensor(Cs) else Cs)]
     K, d = len(Ys_l), Ys_l[0].shape[1]
     sizes = [int(y.shape[0]) for y in Ys_l]
     if len(Cs_l) != K or any(tuple(c.shape) != (n, n) for c, n in zip(Cs_l, sizes)):
@@ -216,7 +246,15 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
         N = Np
     ps_t = None if ps_e is None else (torch.stack(list(ps_e)) if not torch.is_tensor(ps_e) else ps_e).to(torch.float32).to(dev).view(1, K, N)
     p_t = p_embedded.view(1, N) if embedded else (None if p is None else p.to(torch.float32).to(dev).view(1, N))
-    lam = None if lambdas is None else torch.as_tensor([float(l) for l in lambdas], dtype=torch.float32, device=dev)
+    lam = None
+    if lambdas is not None:
+        if torch.is_tensor(lambdas):
+            lam = lambdas.to(torch.float32).to(dev)
+        elif any(torch.is_tensor(l) for l in lambdas):
+            # a list of (0-d) tensors: stacked, so that a lambda that requires grad keeps its graph (as fgw_barycenters does)
+            lam = torch.stack([torch.as_tensor(l, dtype=torch.float32, device=dev).reshape(()) for l in lambdas])
+        else:
+            lam = torch.as_tensor([float(l) for l in lambdas], dtype=torch.float32, device=dev)
     res = ops.fgw_mixup_barycenter_batched(
         torch.stack(Ys_l).view(1, K, N, d), torch.stack(Cs_l).view(1, K, N, N), ps=ps_t, p=p_t, lambdas=lam,
         init_C=init_C.to(torch.float32).to(dev).view(1, N, N), init_Y=None if init_Y is None else init_Y.to(torch.float32).to(dev).view(1, N, d),
@@ -228,7 +266,8 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
         return Y, C
     outer = int(info[0, 0].item())
     T_iter = res[5]
-    Ms = [feature_cost(Y, Ys_l[s][:sizes[s]]) for s in range(K)]          # log["Ms"] (barycenter.py:355,386): dist(Y, Ys[s]) of the returned barycenter
+    # log["Ms"] (barycenter.py:355,386): dist(Y, Ys[s]) of the returned barycenter; a by-product for inspection, without gradient
+    Ms = [feature_cost(Y.detach(), Ys_l[s][:sizes[s]].detach()) for s in range(K)]
     log_ = {"err_feature": [errs[0, 0, i] for i in range(outer)], "err_structure": [errs[0, 1, i] for i in range(outer)],
             "Ts_iter": [[T_iter[i, 0, s, :N_user, :sizes[s]] for s in range(K)] for i in range(outer)],
             "T": [T[0, s, :N_user, :sizes[s]] for s in range(K)],

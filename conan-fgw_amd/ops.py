@@ -830,6 +830,60 @@ def _fgw_params(alpha, epsilon, max_iter, tol, inner_tol, num_iter_max, stop_thr
                      int(bool(fixed_structure)), int(bool(fixed_features)), int(bool(warmstart)), _LOSS_CODE[loss_fun], int(bool(cs_small_int)))
 
 
+def _barycenter_save(ctx, Ys, Cs, p, lambdas, Y, C, T, loss_code, fs, ff) -> bool:
+    """What a barycenter forward (inputs Ys, Cs, ps, p, lambdas, init_C, init_Y, params, in this order) keeps for _barycenter_backward, shared
+    by _FgwBarycenterFn and _FgwMixupBarycenterFn -> whether C is differentiable.
+    Gradients beyond Ys (conan_fgw_barycenter_bwd_full): the last update steps are differentiable in Cs, p, lambdas (and init_C / init_Y under
+    fixed_structure / fixed_features), as in the reference.  Every model asks for Ys only: that path saves and launches exactly what it
+    always did, and C stays non-differentiable."""
+    need = ctx.needs_input_grad
+    want = dict(Ys=need[0] and not ff, Cs=need[1] and Cs is not None and not fs, p=need[3] and p is not None,
+                lam=need[4] and lambdas is not None, init_C=need[5] and fs, init_Y=need[6] and ff)
+    ctx.full = any(want[k] for k in ("Cs", "p", "lam", "init_C", "init_Y")) or (need[0] and ff)
+    c_diff = want["init_C"] if fs else (want["Cs"] or want["p"] or want["lam"])
+    if not ctx.full:
+        ctx.save_for_backward(T, p, lambdas)
+    else:
+        kl = loss_code == 1
+        ctx.want, ctx.flags = want, (loss_code, int(fs), int(ff))
+        keep_Ys = want["lam"] and not ff
+        keep_Cs = (want["Cs"] or want["lam"]) and not fs
+        keep_Y = want["p"] and not ff
+        keep_C = not fs and (want["p"] or (kl and (want["Cs"] or want["lam"])))
+        ctx.save_for_backward(T, p, lambdas, Ys if keep_Ys else None, Cs if keep_Cs else None, Y if keep_Y else None,
+                              C if keep_C else None)
+    return c_diff
+
+
+def _barycenter_backward(ctx, dY, dC):
+    """The gradients of the last update steps at the saved couplings (ctx as _barycenter_save left it) for the eight forward inputs."""
+    if not ctx.full:
+        if dY is None:
+            return (None,) * 8
+        T, p, lambdas = ctx.saved_tensors
+        B, K, N, d = ctx.dims
+        dYs = torch.empty(B, K, N, d, dtype=f32, device=dY.device)
+        call("conan_fgw_barycenter_bwd", ptr(T), ptr(_c(dY)), ptr(p), ptr(lambdas), B, K, N, d, ptr(dYs), stream_ptr())
+        return dYs, None, None, None, None, None, None, None
+    if dY is None and dC is None:
+        return (None,) * 8
+    T, p, lambdas, Ys, Cs, Y, C = ctx.saved_tensors
+    B, K, N, d = ctx.dims
+    w = ctx.want
+    loss, fs, ff = ctx.flags
+    dev = T.device
+    new = lambda want, *shape: torch.empty(*shape, dtype=f32, device=dev) if want else None
+    dYs, dCs = new(w["Ys"], B, K, N, d), new(w["Cs"], B, K, N, N)
+    dp = torch.empty_like(p) if w["p"] else None
+    dlam = torch.empty_like(lambdas) if w["lam"] else None
+    dinit_C, dinit_Y = new(w["init_C"], B, N, N), new(w["init_Y"], B, N, d)
+    ws = torch.empty(int(lib().conan_fgw_barycenter_bwd_full_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
+    opt = lambda t: ptr(_c(t)) if t is not None else None
+    call("conan_fgw_barycenter_bwd_full", ptr(T), ptr(Ys), ptr(Cs), ptr(Y), ptr(C), opt(dY), opt(dC), ptr(p), ptr(lambdas), B, K, N, d,
+         loss, fs, ff, ptr(dYs), ptr(dCs), ptr(dp), ptr(dlam), ptr(dinit_C), ptr(dinit_Y), ptr(ws), stream_ptr())
+    return dYs, dCs, None, dp, dlam, dinit_C, dinit_Y, None
+
+
 class _FgwBarycenterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Ys, Cs, ps, p, lambdas, init_C, init_Y, params):
@@ -862,26 +916,7 @@ class _FgwBarycenterFn(torch.autograd.Function):
                  *common)
         ctx.dims = (B, K, N, d)
         ctx.set_materialize_grads(False)          # C, T, info, errs carry no gradient: without this autograd fills four zero tensors per backward
-        # Gradients beyond Ys (conan_fgw_barycenter_bwd_full): the last update steps are differentiable in Cs, p, lambdas (and init_C /
-        # init_Y under fixed_structure / fixed_features), as in the reference.  Every model asks for Ys only: that path saves and launches
-        # exactly what it always did, and C stays non-differentiable.
-        need = ctx.needs_input_grad
-        fs, ff = bool(params["fixed_structure"]), bool(params["fixed_features"])
-        want = dict(Ys=need[0] and not ff, Cs=need[1] and Cs is not None and not fs, p=need[3] and p is not None,
-                    lam=need[4] and lambdas is not None, init_C=need[5] and fs, init_Y=need[6] and ff)
-        ctx.full = any(want[k] for k in ("Cs", "p", "lam", "init_C", "init_Y")) or (need[0] and ff)
-        c_diff = want["init_C"] if fs else (want["Cs"] or want["p"] or want["lam"])
-        if not ctx.full:
-            ctx.save_for_backward(T, p, lambdas)
-        else:
-            kl = prm.loss_fun == 1
-            ctx.want, ctx.flags = want, (prm.loss_fun, int(fs), int(ff))
-            keep_Ys = want["lam"] and not ff
-            keep_Cs = (want["Cs"] or want["lam"]) and not fs
-            keep_Y = want["p"] and not ff
-            keep_C = not fs and (want["p"] or (kl and (want["Cs"] or want["lam"])))
-            ctx.save_for_backward(T, p, lambdas, Ys if keep_Ys else None, Cs if keep_Cs else None, Y if keep_Y else None,
-                                  C if keep_C else None)
+        c_diff = _barycenter_save(ctx, Ys, Cs, p, lambdas, Y, C, T, prm.loss_fun, bool(params["fixed_structure"]), bool(params["fixed_features"]))
         nd = (T, info, errs) if c_diff else (C, T, info, errs)
         if T_iter is None:
             ctx.mark_non_differentiable(*nd)
@@ -891,31 +926,7 @@ class _FgwBarycenterFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY, dC=None, *_):
-        if not ctx.full:
-            if dY is None:
-                return (None,) * 8
-            T, p, lambdas = ctx.saved_tensors
-            B, K, N, d = ctx.dims
-            dYs = torch.empty(B, K, N, d, dtype=f32, device=dY.device)
-            call("conan_fgw_barycenter_bwd", ptr(T), ptr(_c(dY)), ptr(p), ptr(lambdas), B, K, N, d, ptr(dYs), stream_ptr())
-            return dYs, None, None, None, None, None, None, None
-        if dY is None and dC is None:
-            return (None,) * 8
-        T, p, lambdas, Ys, Cs, Y, C = ctx.saved_tensors
-        B, K, N, d = ctx.dims
-        w = ctx.want
-        loss, fs, ff = ctx.flags
-        dev = T.device
-        new = lambda want, *shape: torch.empty(*shape, dtype=f32, device=dev) if want else None
-        dYs, dCs = new(w["Ys"], B, K, N, d), new(w["Cs"], B, K, N, N)
-        dp = torch.empty_like(p) if w["p"] else None
-        dlam = torch.empty_like(lambdas) if w["lam"] else None
-        dinit_C, dinit_Y = new(w["init_C"], B, N, N), new(w["init_Y"], B, N, d)
-        ws = torch.empty(int(lib().conan_fgw_barycenter_bwd_full_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
-        opt = lambda t: ptr(_c(t)) if t is not None else None
-        call("conan_fgw_barycenter_bwd_full", ptr(T), ptr(Ys), ptr(Cs), ptr(Y), ptr(C), opt(dY), opt(dC), ptr(p), ptr(lambdas), B, K, N, d,
-             loss, fs, ff, ptr(dYs), ptr(dCs), ptr(dp), ptr(dlam), ptr(dinit_C), ptr(dinit_Y), ptr(ws), stream_ptr())
-        return dYs, dCs, None, dp, dlam, dinit_C, dinit_Y, None
+        return _barycenter_backward(ctx, dY, dC)
 
 
 def fgw_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, p: Optional[Tensor] = None,
@@ -1053,12 +1064,12 @@ def fgw_pair_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
     return [T[b, :n1, :n2] for b, (n1, n2) in enumerate(sizes)], dist, info, errs
 
 
-def _mixup_tensor(t, name, *shape):
+def _mixup_tensor(t, name, *shape, keep_graph=False):
     if not t.is_cuda:
         raise NotImplementedError(f"the FGWMixup solve runs on the GPU only: {name} is a CPU tensor")
     if tuple(t.shape) != shape:
         raise ValueError(f"{name} must have shape {list(shape)}, not {list(t.shape)}")
-    return _c(t.detach().to(f32))
+    return _c((t if keep_graph else t.detach()).to(f32))
 
 
 def _mixup_step(rho, epoch, eps):
@@ -1070,25 +1081,17 @@ def _mixup_step(rho, epoch, eps):
     return rho, epoch, eps
 
 
-def fgw_acc_pair_batched(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, X0: Optional[Tensor] = None, *,
-                         alpha: float, rho: float, epoch: int = 200, eps: float = 1e-5, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None):
-    """B independent FGWMixup coupling solves, the reference's fused_ACC_torch(M, A, B, a, b, X, alpha, epoch, eps, rho) (barycenter.py:228-256:
-    accelerated mirror descent, not the Bregman solve of fgw_pair_batched(solver="BAPG")), in one launch, one workgroup per pair.
-    M [B,N1,N2], A [B,N1,N1], Bm [B,N2,N2] (untransposed in the gradient, as the reference has it), a [B,N1] / b [B,N2] or None (uniform), X0
-    [B,N1,N2] the start or None (a b^T) -> X [B,N1,N2], objs [B, ceil(epoch / 10)] (the objective of every check that ran, the stopping one
-    included; NaN elsewhere), info [B,4] int32 = {epochs run, checks stored = the reference's len(obj_list), flags, 0}; flags bit 2: a row or
-    column with mass had a zero or non-finite sum (the reference's NaN, computed here too).
-    n1 [B] / n2 [B] int (optional): the pairs' own sizes inside the [N1,N2] container (uniform weights are then uniform over the own nodes).
-    N1 != N2 and own sizes are solved embedded in a square problem of max(N1, N2) nodes whose extra nodes carry no mass: their entries stay
-    exactly zero (no 1e-10 is added there), so the leading block is the reference's rectangular solve.  One consequence: a weight the caller
-    sets to ZERO means "absent", where the reference lifts such entries by 1e-10 per epoch.  fp32 in and out, fp64 inside.  No gradient."""
-    rho, epoch, eps = _mixup_step(rho, epoch, eps)
+def _acc_prepare(M, A, Bm, a, b, X0, n1, n2, keep_graph=False):
+    """The checked, contiguous fp32 operands of conan_fgw_acc_pair_fwd, N1 != N2 and own sizes embedded in N = max(N1, N2) with massless nodes
+    -> (M, A, Bm, a, b, X0, (B, N, N1, N2)).  keep_graph: the inputs are not detached, so that torch differentiates the conversion and the
+    embedding (X0 never is)."""
     if M.dim() != 3:
         raise ValueError(f"M must be [B,N1,N2], not {list(M.shape)}")
     B, N1, N2 = M.shape
-    M, A, Bm = _mixup_tensor(M, "M", B, N1, N2), _mixup_tensor(A, "A", B, N1, N1), _mixup_tensor(Bm, "Bm", B, N2, N2)
-    a = None if a is None else _mixup_tensor(a, "a", B, N1)
-    b = None if b is None else _mixup_tensor(b, "b", B, N2)
+    kg = dict(keep_graph=keep_graph)
+    M, A, Bm = _mixup_tensor(M, "M", B, N1, N2, **kg), _mixup_tensor(A, "A", B, N1, N1, **kg), _mixup_tensor(Bm, "Bm", B, N2, N2, **kg)
+    a = None if a is None else _mixup_tensor(a, "a", B, N1, **kg)
+    b = None if b is None else _mixup_tensor(b, "b", B, N2, **kg)
     X0 = None if X0 is None else _mixup_tensor(X0, "X0", B, N1, N2)
     dev, N = M.device, max(N1, N2)
     if N1 != N2 or n1 is not None or n2 is not None:
@@ -1105,13 +1108,77 @@ def fgw_acc_pair_batched(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] =
         b = m2 / c2[:, None] if b is None else pad(b, N) * m2
         M, A, Bm = pad(M, N, N), pad(A, N, N), pad(Bm, N, N)
         X0 = None if X0 is None else pad(X0, N, N)
+    return M, A, Bm, a, b, X0, (B, N, N1, N2)
+
+
+def _acc_fwd(M, A, Bm, a, b, X0, B, N, alpha, rho, epoch, eps):
+    """conan_fgw_acc_pair_fwd on prepared operands -> X [B,N,N], objs, info."""
+    dev = M.device
     X = torch.empty(B, N, N, dtype=f32, device=dev)
     objs = torch.empty(B, (epoch + 9) // 10, dtype=f32, device=dev)
     info = torch.empty(B, 4, dtype=i32, device=dev)
     ws = torch.empty(int(lib().conan_fgw_acc_pair_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
     call("conan_fgw_acc_pair_fwd", ptr(M, f32), ptr(A, f32), ptr(Bm, f32), ptr(a), ptr(b), ptr(X0), B, N, float(alpha), rho, epoch, eps,
          ptr(X), ptr(objs), ptr(info), ptr(ws), stream_ptr())
+    return X, objs, info
+
+
+def fgw_acc_pair_batched(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, X0: Optional[Tensor] = None, *,
+                         alpha: float, rho: float, epoch: int = 200, eps: float = 1e-5, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None):
+    """B independent FGWMixup coupling solves, the reference's fused_ACC_torch(M, A, B, a, b, X, alpha, epoch, eps, rho) (barycenter.py:228-256:
+    accelerated mirror descent, not the Bregman solve of fgw_pair_batched(solver="BAPG")), in one launch, one workgroup per pair.
+    M [B,N1,N2], A [B,N1,N1], Bm [B,N2,N2] (untransposed in the gradient, as the reference has it), a [B,N1] / b [B,N2] or None (uniform), X0
+    [B,N1,N2] the start or None (a b^T) -> X [B,N1,N2], objs [B, ceil(epoch / 10)] (the objective of every check that ran, the stopping one
+    included; NaN elsewhere), info [B,4] int32 = {epochs run, checks stored = the reference's len(obj_list), flags, 0}; flags bit 2: a row or
+    column with mass had a zero or non-finite sum (the reference's NaN, computed here too).
+    n1 [B] / n2 [B] int (optional): the pairs' own sizes inside the [N1,N2] container (uniform weights are then uniform over the own nodes).
+    N1 != N2 and own sizes are solved embedded in a square problem of max(N1, N2) nodes whose extra nodes carry no mass: their entries stay
+    exactly zero (no 1e-10 is added there), so the leading block is the reference's rectangular solve.  One consequence: a weight the caller
+    sets to ZERO means "absent", where the reference lifts such entries by 1e-10 per epoch.  fp32 in and out, fp64 inside.  No gradient:
+    fgw_acc_pair_distance is the same solve with the differentiable FGWMixup distance of the returned plan."""
+    rho, epoch, eps = _mixup_step(rho, epoch, eps)
+    M, A, Bm, a, b, X0, (B, N, N1, N2) = _acc_prepare(M, A, Bm, a, b, X0, n1, n2)
+    X, objs, info = _acc_fwd(M, A, Bm, a, b, X0, B, N, alpha, rho, epoch, eps)
     return (X if N1 == N2 else X[:, :N1, :N2]), objs, info
+
+
+def _mixup_barycenter_fwd(Ys, Cs, ps, p, lambdas, init_C, init_Y, prm, rho, epoch, eps, keep_iterates):
+    """conan_fgw_mixup_barycenter_fwd on prepared operands -> Y, C, T, info, errs, T_iter (or None)."""
+    B, K, N, d = Ys.shape
+    dev = Ys.device
+    Y = torch.empty(B, N, d, dtype=f32, device=dev)
+    C = torch.empty(B, N, N, dtype=f32, device=dev)
+    T = torch.empty(B, K, N, N, dtype=f32, device=dev)
+    T_iter = torch.empty(prm.max_iter, B, K, N, N, dtype=f32, device=dev) if keep_iterates else None
+    info = torch.empty(B, 4, dtype=i32, device=dev)
+    errs = torch.empty(B, 2, prm.max_iter, dtype=f32, device=dev)
+    ws = torch.empty(int(lib().conan_fgw_mixup_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
+    call("conan_fgw_mixup_barycenter_fwd", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d,
+         ctypes.byref(prm), rho, epoch, eps, ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr())
+    return Y, C, T, info, errs, T_iter
+
+
+class _FgwMixupBarycenterFn(torch.autograd.Function):
+    """fgw_mixup_barycenter_batched with gradients: forward is conan_fgw_mixup_barycenter_fwd on the prepared fp32 operands, backward that of
+    _FgwBarycenterFn (the FGWMixup barycenter ends with the same three update steps: _barycenter_save / _barycenter_backward), at the couplings of
+    the last outer iteration, held constant.  params = (conan_fgw_params, rho, epoch, eps, keep_iterates)."""
+    @staticmethod
+    def forward(ctx, Ys, Cs, ps, p, lambdas, init_C, init_Y, params):
+        prm, rho, epoch, eps, keep_iterates = params
+        Y, C, T, info, errs, T_iter = _mixup_barycenter_fwd(Ys, Cs, ps, p, lambdas, init_C, init_Y, prm, rho, epoch, eps, keep_iterates)
+        ctx.dims = tuple(Ys.shape)
+        ctx.set_materialize_grads(False)
+        c_diff = _barycenter_save(ctx, Ys, Cs, p, lambdas, Y, C, T, prm.loss_fun, bool(prm.fixed_structure), bool(prm.fixed_features))
+        nd = (T, info, errs) if c_diff else (C, T, info, errs)
+        if T_iter is None:
+            ctx.mark_non_differentiable(*nd)
+            return Y, C, T, info, errs
+        ctx.mark_non_differentiable(*nd, T_iter)
+        return Y, C, T, info, errs, T_iter
+
+    @staticmethod
+    def backward(ctx, dY, dC=None, *_):
+        return _barycenter_backward(ctx, dY, dC)
 
 
 def fgw_mixup_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, p: Optional[Tensor] = None, lambdas: Optional[Tensor] = None,
@@ -1125,31 +1192,34 @@ def fgw_mixup_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = 
     (Cs[:,0]), init_Y [B,N,d] or None (zeros) -> Y [B,N,d], C [B,N,N], T [B,K,N,N], info [B,4] int32 = {outer iterations, epochs summed over
     couplings and iterations, 0, flags}, errs [B,2,max_iter] (+ T_iter [max_iter,B,K,N,N] with keep_iterates=True).  Flags bit 2: a row or
     column with mass had a zero or non-finite sum (the molecule's outputs are then NaN, as the reference's).  Zero entries of p / ps are
-    nodes without mass (the embedding of other sizes); see fgw_acc_pair_batched.  The outputs carry no gradient."""
+    nodes without mass (the embedding of other sizes); see fgw_acc_pair_batched.
+    Gradients flow through the last update steps with the couplings T of the last outer iteration held constant, the convention of
+    fgw_barycenter_batched (and the same backward kernels): Y to Ys, p and lambdas (to init_Y instead of Ys under fixed_features); C to Cs, p
+    and lambdas (to init_C under fixed_structure; with init_C=None there, C is Cs[:, 0] and gets none).  ps, T, info, errs and T_iter get none;
+    no double backward.  This is NOT the reference's gradient, which back-propagates through all `epoch` epochs of every coupling solve; a finite
+    difference of this function moves the plan, so it does not check this gradient.  With only Ys requiring grad C is non-differentiable and
+    the backward is conan_fgw_barycenter_bwd alone.  A molecule whose flags have bit 2 (NaN outputs) gives NaN gradients for its own inputs
+    and, through the sum over molecules, for lambdas; they are not masked.  With no input requiring grad, or under torch.no_grad(), nothing
+    is saved and the call is the forward launch alone."""
     if loss_fun not in ("square_loss", "kl_loss"):
         raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
     rho, epoch, eps = _mixup_step(rho, epoch, eps)
     if Ys.dim() != 4:
         raise ValueError(f"Ys must be [B,K,N,d], not {list(Ys.shape)}")
     B, K, N, d = Ys.shape
-    Ys, Cs = _mixup_tensor(Ys, "Ys", B, K, N, d), _mixup_tensor(Cs, "Cs", B, K, N, N)
-    opt = lambda t, name, *shape: None if t is None else _mixup_tensor(t, name, *shape)
-    ps, p, lambdas = opt(ps, "ps", B, K, N), opt(p, "p", B, N), opt(lambdas, "lambdas", K)
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (Ys, Cs, p, lambdas, init_C, init_Y))
+    opt = lambda t, name, *shape: None if t is None else _mixup_tensor(t, name, *shape, keep_graph=kg)
+    Ys, Cs = opt(Ys, "Ys", B, K, N, d), opt(Cs, "Cs", B, K, N, N)
+    ps = None if ps is None else _mixup_tensor(ps, "ps", B, K, N)
+    p, lambdas = opt(p, "p", B, N), opt(lambdas, "lambdas", K)
     init_C, init_Y = opt(init_C, "init_C", B, N, N), opt(init_Y, "init_Y", B, N, d)
     if fixed_features and init_Y is None:
         raise ValueError("If Y is fixed it must be initialized")
-    dev = Ys.device
     prm = _fgw_params(alpha, 0.0, max_iter, tol, 0.0, 1, 0.0, fixed_structure, fixed_features, False, loss_fun)
-    Y = torch.empty(B, N, d, dtype=f32, device=dev)
-    C = torch.empty(B, N, N, dtype=f32, device=dev)
-    T = torch.empty(B, K, N, N, dtype=f32, device=dev)
-    T_iter = torch.empty(prm.max_iter, B, K, N, N, dtype=f32, device=dev) if keep_iterates else None
-    info = torch.empty(B, 4, dtype=i32, device=dev)
-    errs = torch.empty(B, 2, prm.max_iter, dtype=f32, device=dev)
-    ws = torch.empty(int(lib().conan_fgw_mixup_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
-    call("conan_fgw_mixup_barycenter_fwd", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d,
-         ctypes.byref(prm), rho, epoch, eps, ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(ws), stream_ptr())
-    return (Y, C, T, info, errs) if T_iter is None else (Y, C, T, info, errs, T_iter)
+    if kg:
+        return _FgwMixupBarycenterFn.apply(Ys, Cs, ps, p, lambdas, init_C, init_Y, (prm, rho, epoch, eps, bool(keep_iterates)))
+    res = _mixup_barycenter_fwd(Ys, Cs, ps, p, lambdas, init_C, init_Y, prm, rho, epoch, eps, keep_iterates)
+    return res[:5] if res[5] is None else res
 
 
 class _FgwPairDistFn(torch.autograd.Function):
@@ -1226,6 +1296,33 @@ def fgw_pair_dist(M: Tensor, C1: Tensor, C2: Tensor, T: Tensor, p: Optional[Tens
         return out, T, None, None
 
     return _FgwPairDistFn.apply(M, C1, C2, p, q, run, alpha, _LOSS_CODE[loss_fun])[0] if kg else run()[0]
+
+
+def fgw_acc_pair_distance(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, X0: Optional[Tensor] = None, *,
+                          alpha: float, rho: float, epoch: int = 200, eps: float = 1e-5, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None,
+                          return_plan: bool = False):
+    """The FGWMixup distances of B pairs as a loss: fgw_acc_pair_batched's solve (same arguments, same launch, same bits of X) -> dist [B],
+    the distance the reference's commented lines describe (barycenter.py:348-350) at the returned plan X:
+        (1 - alpha) <M, X> + alpha (<c1, X> - 2 <A X Bm, X>),   c1 = (A o A) a 1^T + 1 b^T (Bm o Bm),
+    that is the solve's final objective plus alpha <c1, X>.  It is formed once, by conan_fgw_pair_dist on the solved plan with C2 = Bm^T (the
+    kernel's C1 X C2^T is then FGWMixup's untransposed A X Bm on directed graphs), and carries gradients to M, A, Bm, a and b — those of the
+    formula at the RETURNED plan, held constant (conan_fgw_pair_dist_bwd).  This is not what back-propagating through the reference's epochs gives;
+    X and X0 get no gradient; no double backward; a finite difference of this function moves the plan, so it does not check this gradient.
+    Rectangular and own-size pairs are embedded as in fgw_acc_pair_batched and the gradients come back in the caller's shapes.
+    return_plan: (dist, X [B,N1,N2], objs, info), the last three as fgw_acc_pair_batched returns them, without gradient."""
+    rho, epoch, eps = _mixup_step(rho, epoch, eps)
+    M, A, Bm, a, b, X0, (B, N, N1, N2) = _acc_prepare(M, A, Bm, a, b, X0, n1, n2, keep_graph=True)
+    Bt = _c(Bm.transpose(1, 2))
+
+    def run():
+        X, objs, info = _acc_fwd(M, A, Bm, a, b, X0, B, N, alpha, rho, epoch, eps)
+        dist = torch.empty(B, dtype=f32, device=M.device)
+        call("conan_fgw_pair_dist", ptr(M, f32), ptr(A, f32), ptr(Bt, f32), ptr(a), ptr(b), ptr(X, f32), B, N, float(alpha), _LOSS_CODE["square_loss"],
+             ptr(dist), stream_ptr())
+        return dist, X, info, objs
+
+    dist, X, info, objs = _FgwPairDistFn.apply(M, A, Bt, a, b, run, alpha, _LOSS_CODE["square_loss"])
+    return (dist, (X if N1 == N2 else X[:, :N1, :N2]), objs, info) if return_plan else dist
 
 
 # ------------------------------------------------------------------------------------------------ entropic OT on its own (sinkhorn.hip)

@@ -1,6 +1,7 @@
-"""What does the FGWMixup barycenter (ops.fgw_mixup_barycenter_batched) cost next to the same iteration written with batched torch ops?
+"""What does the FGWMixup barycenter (ops.fgw_mixup_barycenter_batched) cost next to the same iteration written with batched torch ops, and
+what does its backward add?
 
-    python tools/probe_fgw_mixup.py [--runs 25] [--warmup 3] [--repeats 3] [--out profiles/fgw_mixup_probe.txt]
+    python tools/probe_fgw_mixup.py [--runs 25] [--warmup 3] [--repeats 3] [--out profiles/fgw_mixup_grad_probe.txt]
 
 Two shapes with max_iter = 5, tol = 1e-9, alpha = 0.5, rho = 8, epoch = 100, eps = 1e-5: cfg2's (B = 256 molecules, K = 5 graphs, N = 33 nodes,
 d = 64) and BACE's (B = 64, K = 3, N = 90, d = 64: its matrices are streamed, N > 79).  Inputs are seeded: features uniform in [0.1, 2], random
@@ -11,6 +12,11 @@ undirected graphs of density 0.3, init_C the first graph.  Per shape, HIP events
     torch_ms    the reference's arithmetic on the same GPU: the same iteration as batched fp32 torch ops over all B * K couplings; a coupling
                 that has passed its check keeps its plan while the batch is iterated until the last one has (one host synchronisation per
                 check, as in the reference), all five outer iterations
+
+A second row per shape ("grad") times the same call followed by its backward (torch.autograd.backward with fixed output gradients for Y and C,
+no loss kernels in between), once with every differentiable input a leaf (Ys, Cs, p, lambdas: conan_fgw_barycenter_bwd_full) and once with Ys alone
+(conan_fgw_barycenter_bwd), beside a forward with the same explicit uniform p and lambdas; the backward's own cost is the difference.  The backward
+works on the couplings of the last outer iteration only, so it does not grow with max_iter or epoch.  No threshold is set: the figures are stated.
 
 Every shape runs in a process of its own under `timeout -k 10` (this script is the driver; --shape NAME is the worker), and the driver stops
 at the first shape that fails.  The epoch counts of both sides are printed beside the times, and so is each side's distance (relative Frobenius
@@ -25,6 +31,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = {"cfg2": (256, 5, 33, 64), "bace": (64, 3, 90, 64)}
 PRM = dict(alpha=0.5, rho=8.0, max_iter=5, tol=1e-9, epoch=100, eps=1e-5)
+GRAD_HEAD = "grad  shape                 fwd_ms  fwd+bwd all leaves_ms  fwd+bwd Ys only_ms  bwd all_ms  bwd Ys_ms  repeats fwd | all leaves | Ys only"
 HEAD = "shape                      kernel_ms  torch_ms  kernel epochs (sum / per coupling solve)  torch epochs  kernel rel(Y) rel(C)  torch rel(Y) rel(C)  flags  repeats kernel | torch"
 
 
@@ -105,6 +112,38 @@ def worker(name, runs, warmup, repeats):
     print(f"B={B:<4d}K={K} N={N:<3d}d={d:<4d}  {statistics.median(k_ms):9.3f}  {statistics.median(t_ms):8.3f}  "
           f"{int(info[:, 1].sum())} / {int(info[:, 1].sum()) / max(solves, 1):.1f}".ljust(90) + f"{tn:<12d}  {rel(Y, Yd):.2e} {rel(C, Cd):.2e}  {rel(Yt, Yd):.2e} {rel(Ct, Cd):.2e}  "
           f"{int((info[:, 3] != 0).sum()):<5d}  {' '.join(f'{x:.3f}' for x in k_ms)} | {' '.join(f'{x:.3f}' for x in t_ms)}")
+    # forward + backward: explicit uniform weights, so that p and lambdas can be leaves; the output gradients are fixed tensors
+    p = torch.full((B, N), 1.0 / N, device=dev)
+    lam = torch.full((K,), 1.0 / K, device=dev)
+    gen = torch.Generator().manual_seed(7)
+    gw, gc = torch.randn(B, N, d, generator=gen).to(dev), torch.randn(B, N, N, generator=gen).to(dev)
+    leaf = lambda t: t.clone().requires_grad_(True)
+    all_leaves = (leaf(Ys), leaf(Cs), leaf(p), leaf(lam))
+    ys_leaf = leaf(Ys)
+
+    def fwd():
+        ops.fgw_mixup_barycenter_batched(Ys, Cs, p=p, lambdas=lam, **PRM)
+
+    def fb_all():
+        for t in all_leaves:
+            t.grad = None
+        Yo, Co = ops.fgw_mixup_barycenter_batched(all_leaves[0], all_leaves[1], p=all_leaves[2], lambdas=all_leaves[3], **PRM)[:2]
+        torch.autograd.backward((Yo, Co), (gw, gc))
+
+    def fb_ys():
+        ys_leaf.grad = None
+        Yo = ops.fgw_mixup_barycenter_batched(ys_leaf, Cs, p=p, lambdas=lam, **PRM)[0]
+        Yo.backward(gw)
+
+    f_ms, a_ms, y_ms = [], [], []
+    for _ in range(repeats):
+        f_ms.append(timed(fwd))
+        a_ms.append(timed(fb_all))
+        y_ms.append(timed(fb_ys))
+    assert all(bool(torch.isfinite(t.grad).all()) for t in all_leaves) and bool(torch.isfinite(ys_leaf.grad).all())
+    med = statistics.median
+    print(f"grad  B={B:<4d}K={K} N={N:<3d}d={d:<4d} {med(f_ms):7.3f}  {med(a_ms):21.3f}  {med(y_ms):18.3f}  {med(a_ms) - med(f_ms):10.3f}  {med(y_ms) - med(f_ms):9.3f}  "
+          f"{' '.join(f'{x:.3f}' for x in f_ms)} | {' '.join(f'{x:.3f}' for x in a_ms)} | {' '.join(f'{x:.3f}' for x in y_ms)}")
     print(f"# device: {torch.cuda.get_device_name(0)}")
 
 
@@ -132,6 +171,7 @@ def main():
         out = r.stdout.strip().splitlines()
         lines += [l for l in out if not l.startswith("# device")]
         device = next((l for l in out if l.startswith("# device")), device)
+    lines = [l for l in lines if not l.startswith("grad")] + [GRAD_HEAD] + [l for l in lines if l.startswith("grad")]
     lines.insert(1, device)
     text = "\n".join(lines)
     print(text)
