@@ -188,6 +188,15 @@ SIGNATURES = {
     "conan_fgw_readout_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
+# Exports added after include/conan_fgw_hip.h was frozen at ABI version 6 (an added export does not change the version): declared in
+# include/conan_fgw_hip_ext.h, bound by lib() next to SIGNATURES; tests/test_fgw_acc_grad_cpu.py checks this table against that header.
+_D = ctypes.c_double
+EXT_SIGNATURES = {
+    "conan_fgw_acc_pair_bwd_lds_resident": (c_int, [c_int]),
+    "conan_fgw_acc_pair_bwd_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
+    "conan_fgw_acc_pair_bwd": (c_int, [_P] * 6 + [c_int, c_int, _D, _D, c_int] + [_P] * 12),
+}
+
 _ERR = {-1: "bad argument", -2: "HIP launch failure", -3: "unsupported configuration"}
 
 
@@ -212,9 +221,10 @@ def lib():
                 f"{_SO} is missing: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or make -C conan-fgw_amd/csrc). There is no CPU fallback for this path.")
         L = ctypes.CDLL(_SO)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
+        for table in (SIGNATURES, EXT_SIGNATURES):
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = res, args
         if L.conan_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libconan_fgw_hip.so: ABI version {L.conan_abi_version()} != {ABI_VERSION} expected by _lib.py (stale build: "
                                "make -C conan-fgw_amd/csrc)")

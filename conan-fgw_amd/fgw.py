@@ -3,7 +3,9 @@
 `fgw_bregman` — the coupling solve between two attributed graphs on its own, with `fgw_distance`, its differentiable distance, and
 `fgw_pairwise_distances` over an ensemble on top; barycenter.py:228-390 `fused_ACC_torch`, `fgw_barycenters_BAPG` — FGWMixup's accelerated
 mirror descent and the barycenter around it, with `fgw_mixup_distance`, the differentiable distance of that solve; the barycenter and the
-distance carry gradients at the solved couplings, held constant: see their docstrings for this and the other deviations).
+distance carry gradients at the solved couplings, held constant: see their docstrings for this and the other deviations;
+`fused_ACC_unrolled` and `fgw_mixup_distance_unrolled` are the pair solve and its distance with the reference's own gradient, the one torch
+autograd forms through every epoch of fused_ACC_torch).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
 barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
@@ -171,7 +173,7 @@ def fused_ACC_torch(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-
     gradient (the reference's would unroll every epoch; to train through the solve use fgw_mixup_distance, the gradient of the distance at the
     returned plan); the run is an fp64 iteration on the fp32 inputs, so counts and values follow the reference's fp64 run; a weight that is exactly
     ZERO marks an absent node whose entries stay zero (the reference lifts them by 1e-10 every epoch).  A NaN result (exp under- / overflow at
-    small rho) is the reference's NaN.  Runs on the GPU only."""
+    small rho) is the reference's NaN.  Runs on the GPU only.  fused_ACC_unrolled is this solve with the reference's differentiable plan."""
     for name, t in (("M", M), ("A", A), ("B", B), ("a", a), ("b", b), ("X", X)):
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"fused_ACC_torch runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
@@ -189,7 +191,8 @@ def fgw_mixup_distance(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=
     formula at the solve's plan X, held constant — the treatment the barycenter gives its couplings (barycenter.py:120) — and NOT what
     back-propagating through the reference's fused_ACC_torch gives, which unrolls every epoch into the graph.  X (the start) and the plan get no
     gradient; there is no double backward.  A finite difference of this function moves the plan, so it does not check this gradient.
-    log=True: (dist, {"T": the plan (no gradient, fused_ACC_torch's bits), "obj_list": fused_ACC_torch's list}).  Runs on the GPU only."""
+    log=True: (dist, {"T": the plan (no gradient, fused_ACC_torch's bits), "obj_list": fused_ACC_torch's list}).  Runs on the GPU only.
+    fgw_mixup_distance_unrolled is this distance with the gradient through the unrolled epochs."""
     for name, t in (("M", M), ("A", A), ("B", B), ("a", a), ("b", b), ("X", X)):
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"fgw_mixup_distance runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
@@ -200,6 +203,37 @@ def fgw_mixup_distance(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=
         return dist[0]
     stored = int(info[0, 1].item())
     return dist[0], {"T": Xo[0], "obj_list": [objs[0, k] for k in range(stored)]}
+
+
+def _unrolled_pair(fn, M, A, B, a, b, X, alpha, epoch, eps, rho):
+    for name, t in (("M", M), ("A", A), ("B", B), ("a", a), ("b", b), ("X", X)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"{fn} runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    one = lambda t: None if t is None else t.unsqueeze(0)
+    Xo, dist, objs, info = ops.fgw_acc_pair_unrolled(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps)
+    stored = int(info[0, 1].item())
+    return Xo[0], dist[0], [objs[0, k] for k in range(stored)]
+
+
+def fused_ACC_unrolled(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-5, rho=1e-1):
+    """fused_ACC_torch (same arguments, defaults, solve and bits) -> (X, obj_list) with a DIFFERENTIABLE plan: X carries the gradient the
+    reference's fused_ACC_torch delivers under torch autograd, back through every executed epoch, to M, A, B, a, b and to the start X when one
+    is given (ops.fgw_acc_pair_unrolled: one backward launch that replays the epochs and walks them in reverse).  Deviations from the
+    reference beyond fused_ACC_torch's: obj_list carries no gradient; a node whose weight is exactly ZERO gets gradient 0 (the reference: a
+    finite value from the entries it lifts by 1e-10); no double backward.  A NaN solve gives NaN gradients.  Runs on the GPU only."""
+    Xo, _dist, objs = _unrolled_pair("fused_ACC_unrolled", M, A, B, a, b, X, alpha, epoch, eps, rho)
+    return Xo, objs
+
+
+def fgw_mixup_distance_unrolled(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-5, rho=1e-1, log=False):
+    """fgw_mixup_distance (same arguments, defaults, solve, value and bits) with the TOTAL derivative: the 0-d distance carries the gradient of
+        (1 - alpha) <M, X> + alpha (<c1, X> - 2 <A X B, X>),   c1 = (A o A) a 1^T + 1 b^T (B o B)
+    to M, A, B, a, b and the start X with the plan X moving with them — what back-propagating this formula through the reference's
+    fused_ACC_torch gives — where fgw_mixup_distance holds the plan fixed.  A central difference of this function (at a fixed epoch count)
+    does check this gradient.  log=True: (dist, {"T": the plan, which carries the unrolled gradient too, "obj_list": fused_ACC_torch's list,
+    without gradient}).  No double backward.  Runs on the GPU only."""
+    Xo, dist, objs = _unrolled_pair("fgw_mixup_distance_unrolled", M, A, B, a, b, X, alpha, epoch, eps, rho)
+    return (dist, {"T": Xo, "obj_list": objs}) if log else dist
 
 
 def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=None, lambdas=None, loss_fun="square_loss", alpha=0.5,

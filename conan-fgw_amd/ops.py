@@ -1081,10 +1081,10 @@ def _mixup_step(rho, epoch, eps):
     return rho, epoch, eps
 
 
-def _acc_prepare(M, A, Bm, a, b, X0, n1, n2, keep_graph=False):
+def _acc_prepare(M, A, Bm, a, b, X0, n1, n2, keep_graph=False, keep_start_graph=False):
     """The checked, contiguous fp32 operands of conan_fgw_acc_pair_fwd, N1 != N2 and own sizes embedded in N = max(N1, N2) with massless nodes
     -> (M, A, Bm, a, b, X0, (B, N, N1, N2)).  keep_graph: the inputs are not detached, so that torch differentiates the conversion and the
-    embedding (X0 never is)."""
+    embedding (X0 only with keep_start_graph: the unrolled gradient reaches the start, the fixed-plan one does not)."""
     if M.dim() != 3:
         raise ValueError(f"M must be [B,N1,N2], not {list(M.shape)}")
     B, N1, N2 = M.shape
@@ -1092,7 +1092,7 @@ def _acc_prepare(M, A, Bm, a, b, X0, n1, n2, keep_graph=False):
     M, A, Bm = _mixup_tensor(M, "M", B, N1, N2, **kg), _mixup_tensor(A, "A", B, N1, N1, **kg), _mixup_tensor(Bm, "Bm", B, N2, N2, **kg)
     a = None if a is None else _mixup_tensor(a, "a", B, N1, **kg)
     b = None if b is None else _mixup_tensor(b, "b", B, N2, **kg)
-    X0 = None if X0 is None else _mixup_tensor(X0, "X0", B, N1, N2)
+    X0 = None if X0 is None else _mixup_tensor(X0, "X0", B, N1, N2, keep_graph=keep_start_graph)
     dev, N = M.device, max(N1, N2)
     if N1 != N2 or n1 is not None or n2 is not None:
         def own(n, Nc):
@@ -1135,7 +1135,8 @@ def fgw_acc_pair_batched(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] =
     N1 != N2 and own sizes are solved embedded in a square problem of max(N1, N2) nodes whose extra nodes carry no mass: their entries stay
     exactly zero (no 1e-10 is added there), so the leading block is the reference's rectangular solve.  One consequence: a weight the caller
     sets to ZERO means "absent", where the reference lifts such entries by 1e-10 per epoch.  fp32 in and out, fp64 inside.  No gradient:
-    fgw_acc_pair_distance is the same solve with the differentiable FGWMixup distance of the returned plan."""
+    fgw_acc_pair_distance is the same solve with the differentiable FGWMixup distance of the returned plan.  fgw_acc_pair_unrolled is the same
+    solve with the reference's gradient through the unrolled epochs on the plan and the distance."""
     rho, epoch, eps = _mixup_step(rho, epoch, eps)
     M, A, Bm, a, b, X0, (B, N, N1, N2) = _acc_prepare(M, A, Bm, a, b, X0, n1, n2)
     X, objs, info = _acc_fwd(M, A, Bm, a, b, X0, B, N, alpha, rho, epoch, eps)
@@ -1309,7 +1310,8 @@ def fgw_acc_pair_distance(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] 
     formula at the RETURNED plan, held constant (conan_fgw_pair_dist_bwd).  This is not what back-propagating through the reference's epochs gives;
     X and X0 get no gradient; no double backward; a finite difference of this function moves the plan, so it does not check this gradient.
     Rectangular and own-size pairs are embedded as in fgw_acc_pair_batched and the gradients come back in the caller's shapes.
-    return_plan: (dist, X [B,N1,N2], objs, info), the last three as fgw_acc_pair_batched returns them, without gradient."""
+    return_plan: (dist, X [B,N1,N2], objs, info), the last three as fgw_acc_pair_batched returns them, without gradient.
+    fgw_acc_pair_unrolled delivers the gradient through the unrolled epochs instead."""
     rho, epoch, eps = _mixup_step(rho, epoch, eps)
     M, A, Bm, a, b, X0, (B, N, N1, N2) = _acc_prepare(M, A, Bm, a, b, X0, n1, n2, keep_graph=True)
     Bt = _c(Bm.transpose(1, 2))
@@ -1323,6 +1325,81 @@ def fgw_acc_pair_distance(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] 
 
     dist, X, info, objs = _FgwPairDistFn.apply(M, A, Bt, a, b, run, alpha, _LOSS_CODE["square_loss"])
     return (dist, (X if N1 == N2 else X[:, :N1, :N2]), objs, info) if return_plan else dist
+
+
+# ------------------------------------------------------------------- the reference's gradient through the unrolled epochs (fgw_acc_grad.hip)
+def _acc_dist(M, A, Bm, a, b, X, B, N, alpha):
+    """fgw_acc_pair_distance's value at the plan X: conan_fgw_pair_dist with C2 = Bm^T -> dist [B]."""
+    dist = torch.empty(B, dtype=f32, device=M.device)
+    call("conan_fgw_pair_dist", ptr(M, f32), ptr(A, f32), ptr(_c(Bm.transpose(1, 2)), f32), ptr(a), ptr(b), ptr(X, f32), B, N, float(alpha),
+         _LOSS_CODE["square_loss"], ptr(dist), stream_ptr())
+    return dist
+
+
+class _FgwAccUnrolledFn(torch.autograd.Function):
+    """fgw_acc_pair_batched's launch and fgw_acc_pair_distance's distance with conan_fgw_acc_pair_bwd as their backward: the gradient through the
+    executed epochs, as the reference's autograd delivers it, from the cotangents of X and dist to M, A, Bm, a, b and X0.  The backward is ONE
+    launch that replays the epochs from the saved inputs (nothing but the inputs and info is kept from the forward).  No double backward, no
+    host synchronisation."""
+    @staticmethod
+    def forward(ctx, M, A, Bm, a, b, X0, dims, alpha, rho, epoch, eps):
+        B, N = dims
+        X, objs, info = _acc_fwd(M, A, Bm, a, b, X0, B, N, alpha, rho, epoch, eps)
+        dist = _acc_dist(M, A, Bm, a, b, X, B, N, alpha)
+        ctx.save_for_backward(M, A, Bm, a, b, X0, info)
+        ctx.dims, ctx.alpha, ctx.rho, ctx.epoch = dims, float(alpha), float(rho), int(epoch)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(objs, info)
+        return X, dist, objs, info
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gX, gdist, *_):
+        M, A, Bm, a, b, X0, info = ctx.saved_tensors
+        B, N = ctx.dims
+        if gX is None and gdist is None:
+            return (None,) * 11
+        dev = M.device
+        gX = None if gX is None else _c(gX.to(f32))
+        gdist = None if gdist is None else _c(gdist.to(f32))
+        need = ctx.needs_input_grad
+        dM, dA, dBm = (torch.empty(B, N, N, dtype=f32, device=dev) for _ in range(3))
+        da = torch.empty(B, N, dtype=f32, device=dev) if a is not None and need[3] else None
+        db = torch.empty(B, N, dtype=f32, device=dev) if b is not None and need[4] else None
+        dX0 = torch.empty(B, N, N, dtype=f32, device=dev) if X0 is not None and need[5] else None
+        nbytes = int(lib().conan_fgw_acc_pair_bwd_workspace_bytes(B, N, ctx.epoch))
+        if nbytes == 0:
+            raise NotImplementedError(f"the unrolled FGWMixup gradient does not support N = {N}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("conan_fgw_acc_pair_bwd", ptr(M, f32), ptr(A, f32), ptr(Bm, f32), ptr(a), ptr(b), ptr(X0), B, N, ctx.alpha, ctx.rho, ctx.epoch, ptr(info),
+             ptr(gX), ptr(gdist), ptr(dM), ptr(dA), ptr(dBm), ptr(da), ptr(db), ptr(dX0), None, ptr(ws), stream_ptr())
+        return (dM if need[0] else None, dA if need[1] else None, dBm if need[2] else None, da, db, dX0) + (None,) * 5
+
+
+def fgw_acc_pair_unrolled(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, X0: Optional[Tensor] = None, *,
+                          alpha: float, rho: float, epoch: int = 200, eps: float = 1e-5, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None):
+    """fgw_acc_pair_batched's solve and fgw_acc_pair_distance's distance (same arguments, same launches, same bits) -> (X, dist, objs, info),
+    where X and dist carry the reference's gradient through the unrolled epochs (its fused_ACC_torch is differentiable torch code,
+    barycenter.py:228-256) to M, A, Bm, a, b, and to X0 when one is given: the total derivative, not the one at a plan held constant that
+    fgw_acc_pair_distance delivers.  One backward launch per backward call (conan_fgw_acc_pair_bwd) serves both cotangents: it replays the epochs
+    the forward ran (info[:, 0], read on the device), recording the fp64 input of every half-step, and walks them in reverse.  a / b given as
+    None (uniform) get none; info and objs are not differentiable (the reference's obj_list is: a deviation), and the stop decision carries no
+    gradient.  A node without mass (a_i = 0, b_j = 0, the padding of rectangular and own-size pairs) gets exactly 0 in its rows / columns of
+    every gradient and in da_i / db_j, where the reference — which lifts such entries by 1e-10 — gives a finite da_i; a pair with info flags
+    bit 2 (a zero or non-finite line sum) gets NaN gradients, as the reference's autograd gives.  Rectangular and own-size pairs are embedded as in
+    fgw_acc_pair_batched and the gradients come back in the caller's shapes.  The backward's workspace is B * (2 epoch + 3) * N^2 * 8 bytes, N =
+    max(N1, N2): the record of the half-steps alone is B * 2 epoch * N^2 * 8 bytes (3.5 MB per 33 x 33 pair at the default epoch = 200), plus
+    five N x N fp64 matrices per pair above N = 61; the caller chooses the cap.  When no input requires grad nothing is saved and nothing
+    beyond the two forward launches runs.  No double backward, no host synchronisation in either direction."""
+    rho, epoch, eps = _mixup_step(rho, epoch, eps)
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (M, A, Bm, a, b, X0))
+    M, A, Bm, a, b, X0, (B, N, N1, N2) = _acc_prepare(M, A, Bm, a, b, X0, n1, n2, keep_graph=kg, keep_start_graph=kg)
+    if kg:
+        X, dist, objs, info = _FgwAccUnrolledFn.apply(M, A, Bm, a, b, X0, (B, N), alpha, rho, epoch, eps)
+    else:
+        X, objs, info = _acc_fwd(M, A, Bm, a, b, X0, B, N, alpha, rho, epoch, eps)
+        dist = _acc_dist(M, A, Bm, a, b, X, B, N, alpha)
+    return (X if N1 == N2 else X[:, :N1, :N2]), dist, objs, info
 
 
 # ------------------------------------------------------------------------------------------------ entropic OT on its own (sinkhorn.hip)
