@@ -197,6 +197,17 @@ EXT_SIGNATURES = {
     "conan_fgw_acc_pair_bwd": (c_int, [_P] * 6 + [c_int, c_int, _D, _D, c_int] + [_P] * 12),
 }
 
+# Further homes for exports added after the freeze, one signature table per header under include/ (its base name is the key): a new group of
+# exports adds a header and an entry here, nothing else changes.  tests/test_fgw_pair_unrolled_cpu.py checks every entry against its header and
+# the library's exports.
+EXT_TABLES = {
+    "conan_fgw_hip_pair_grad.h": {
+        "conan_fgw_pair_bwd_lds_resident": (c_int, [c_int]),
+        "conan_fgw_pair_bwd_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+        "conan_fgw_pair_bwd": (c_int, [_P] * 6 + [c_int, c_int, _D, _D, c_int, c_int, _D, c_int, c_int] + [_P] * 13),
+    },
+}
+
 _ERR = {-1: "bad argument", -2: "HIP launch failure", -3: "unsupported configuration"}
 
 
@@ -221,7 +232,7 @@ def lib():
                 f"{_SO} is missing: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or make -C conan-fgw_amd/csrc). There is no CPU fallback for this path.")
         L = ctypes.CDLL(_SO)
-        for table in (SIGNATURES, EXT_SIGNATURES):
+        for table in (SIGNATURES, EXT_SIGNATURES, *EXT_TABLES.values()):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -5,7 +5,9 @@
 mirror descent and the barycenter around it, with `fgw_mixup_distance`, the differentiable distance of that solve; the barycenter and the
 distance carry gradients at the solved couplings, held constant: see their docstrings for this and the other deviations;
 `fused_ACC_unrolled` and `fgw_mixup_distance_unrolled` are the pair solve and its distance with the reference's own gradient, the one torch
-autograd forms through every epoch of fused_ACC_torch).
+autograd forms through every epoch of fused_ACC_torch; `fgw_unrolled`, `fgw_distance_unrolled` and `fgw_pairwise_distances_unrolled` are
+`fgw`, `fgw_distance` and `fgw_pairwise_distances` with the reference's own gradient too, the one torch autograd forms through every PGD / PPA
+iteration and Sinkhorn sweep of its fgw).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
 barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
@@ -413,9 +415,96 @@ def fgw_distance(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1,
     return _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, log, num_iter_max, stop_thr, distance=True)
 
 
+def _pair_solve_unrolled(fn, M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, method, warmstart, kwargs):
+    """The refusals of the unrolled names, then one pair through ops.fgw_pair_unrolled (B = 1) -> (T, dist, log without "fgw_dist" / "T")."""
+    if solver not in ("PGD", "PPA", "BAPG"):
+        raise ValueError("Unknown solver '%s'. Pick one in ['PGD', 'PPA', 'BAPG']." % solver)
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    if solver == "BAPG":
+        raise NotImplementedError(f"{fn} covers solver 'PGD' and 'PPA': 'BAPG' is not implemented")
+    if loss_fun == "kl_loss":
+        raise NotImplementedError(f"{fn} covers loss_fun 'square_loss': 'kl_loss' is not implemented")
+    if kwargs.pop("marginal_loss", False):
+        raise NotImplementedError("marginal_loss=True is not implemented")
+    num_iter_max, stop_thr = _check_projected(loss_fun, solver, method, warmstart, kwargs)
+    for name, t in (("M", M), ("C1", C1), ("C2", C2), ("p", p), ("q", q), ("G0", G0)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"{fn} runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    one = lambda t: None if t is None else t.unsqueeze(0)
+    T, dist, info, errs = ops.fgw_pair_unrolled(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol,
+                                                num_iter_max=num_iter_max, stop_thr=stop_thr, loss_fun=loss_fun, solver=solver, symmetric=symmetric)
+    T = T[0]
+    if bool(abs(T.detach().sum() - 1) > 1e-5):                              # bregman.py:159-162, one host synchronisation as in the reference
+        warnings.warn(_FAILED)
+    n_iter, n_sk = int(info[0, 0].item()), int(info[0, 1].item())
+    return T, dist[0], {"err": [errs[0, i] for i in range((n_iter + 9) // 10)], "n_iter": n_iter, "n_sinkhorn": n_sk}
+
+
+def fgw_unrolled(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=100, tol=1e-5, solver="PGD",
+                 method="sinkhorn_log", warmstart=False, verbose=False, log=False, **kwargs):
+    """fgw (same arguments, defaults, solve, warning and bits) with DIFFERENTIABLE outputs, as the reference's call delivers them: T, and with
+    log=True log["fgw_dist"], carry the gradient torch autograd forms through the reference's fgw — back through every executed PGD / PPA
+    iteration and every Sinkhorn sweep — to M, C1, C2, p, q and to G0 when one is given (ops.fgw_pair_unrolled: one backward launch that replays
+    the iterations and walks them in reverse).  solver "PGD" or "PPA" and the square loss; "BAPG", "kl_loss", warmstart=True, another method and
+    marginal_loss raise NotImplementedError.  Deviations from the reference beyond fgw's: log["err"] carries no gradient; a node whose weight is
+    exactly ZERO gets gradient 0 (the reference: NaN from log(0)); no double backward.  A solve the reference's autograd answers with NaN (PPA
+    after entries of the plan have underflowed to zero) gives NaN gradients.  Runs on the GPU only."""
+    T, dist, log_ = _pair_solve_unrolled("fgw_unrolled", M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, method, warmstart, kwargs)
+    if not log:
+        return T
+    log_["fgw_dist"] = dist
+    return T, log_
+
+
+def fgw_distance_unrolled(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=100, tol=1e-5,
+                          solver="PGD", method="sinkhorn_log", warmstart=False, verbose=False, log=False, **kwargs):
+    """fgw_distance (same arguments, defaults, solve, value and bits) with the TOTAL derivative: the 0-d distance carries the gradient of
+    log["fgw_dist"] with the plan moving with the inputs — the reference's log["fgw_dist"].backward() — to M, C1, C2, p, q and the start G0, where
+    fgw_distance holds the plan fixed.  A central difference of this function (at fixed iteration and sweep counts) does check this gradient.
+    log=True: (dist, {"T": the plan, which carries the unrolled gradient too, "err", "fgw_dist" (detached), "n_iter", "n_sinkhorn"}).  Refusals
+    and deviations as fgw_unrolled.  Runs on the GPU only."""
+    T, dist, log_ = _pair_solve_unrolled("fgw_distance_unrolled", M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, method, warmstart,
+                                         kwargs)
+    if not log:
+        return dist
+    log_["fgw_dist"], log_["T"] = dist.detach(), T
+    return dist, log_
+
+
 def feature_cost(Y: Tensor, Z: Tensor) -> Tensor:
     """dist(Y, Z) of the reference (utils.py:154-171): the squared Euclidean distances of the feature rows, clamped at 0 -> [n1,n2]."""
     return torch.clamp((Y * Y).sum(1)[:, None] + (Z * Z).sum(1)[None, :] - 2.0 * (Y @ Z.T), min=0)
+
+
+def _pairwise(name, Ys, Cs, ps, kw, with_grad, without_grad):
+    """The all-pairs matrix of fgw_pairwise_distances: with_grad / without_grad = (batched, list) forms that return the distances [npairs]."""
+    G = len(Ys)
+    if len(Cs) != G or (ps is not None and len(ps) != G):
+        raise ValueError("Ys, Cs (and ps) must have one entry per graph")
+    if not all(torch.is_tensor(t) and t.is_cuda for t in list(Ys) + list(Cs)):
+        raise NotImplementedError(f"{name} runs on the GPU only: pass CUDA (ROCm) tensors")
+    grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in list(Ys) + list(Cs) + list(ps or []))
+    keep = (lambda t: t) if grad else (lambda t: t.detach())
+    Ys = [keep(y).to(torch.float32) for y in Ys]
+    out = torch.zeros(G, G, dtype=torch.float32, device=Ys[0].device)
+    ia, ib = torch.triu_indices(G, G, 1).tolist() if G > 1 else ([], [])
+    if not ia:
+        return out
+    Ms = [feature_cost(Ys[a], Ys[b]) for a, b in zip(ia, ib)]
+    pick = lambda ts, idx: None if ts is None else [ts[i] for i in idx]
+    batched, lst = with_grad if grad else without_grad
+    if len({int(y.shape[0]) for y in Ys}) == 1:
+        st = lambda ts: None if ts is None else torch.stack([keep(t).to(torch.float32) for t in ts])
+        dist = batched(torch.stack(Ms), st(pick(Cs, ia)), st(pick(Cs, ib)), st(pick(ps, ia)), st(pick(ps, ib)), **kw)
+    else:
+        dist = lst(Ms, pick(Cs, ia), pick(Cs, ib), pick(ps, ia), pick(ps, ib), **kw)
+    out[ia, ib] = dist
+    out[ib, ia] = dist
+    return out
+
+
+_PLAIN_PAIRS = (lambda *a, **k: ops.fgw_pair_batched(*a, **k)[1], lambda *a, **k: ops.fgw_pair_list(*a, **k)[1])
 
 
 def fgw_pairwise_distances(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, alpha=0.5, epsilon=0.1, loss_fun="square_loss", symmetric=None,
@@ -428,32 +517,22 @@ def fgw_pairwise_distances(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, 
     fgw_distance's value with its gradient at the solved plan (ops.fgw_pair_distance); feature_cost, the stacking of the pairs and the scatter into
     the matrix stay in torch and are differentiated by torch.  The values are the same bits either way; with no input requiring grad the calls issued
     are the same as before."""
-    G = len(Ys)
-    if len(Cs) != G or (ps is not None and len(ps) != G):
-        raise ValueError("Ys, Cs (and ps) must have one entry per graph")
-    if not all(torch.is_tensor(t) and t.is_cuda for t in list(Ys) + list(Cs)):
-        raise NotImplementedError("fgw_pairwise_distances runs on the GPU only: pass CUDA (ROCm) tensors")
-    grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in list(Ys) + list(Cs) + list(ps or []))
-    keep = (lambda t: t) if grad else (lambda t: t.detach())
-    Ys = [keep(y).to(torch.float32) for y in Ys]
-    out = torch.zeros(G, G, dtype=torch.float32, device=Ys[0].device)
-    ia, ib = torch.triu_indices(G, G, 1).tolist() if G > 1 else ([], [])
-    if not ia:
-        return out
     kw = dict(alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, num_iter_max=numItermax, stop_thr=stopThr, loss_fun=loss_fun, solver=solver,
               symmetric=symmetric)
-    Ms = [feature_cost(Ys[a], Ys[b]) for a, b in zip(ia, ib)]
-    pick = lambda ts, idx: None if ts is None else [ts[i] for i in idx]
-    if len({int(y.shape[0]) for y in Ys}) == 1:
-        st = lambda ts: None if ts is None else torch.stack([keep(t).to(torch.float32) for t in ts])
-        args = (torch.stack(Ms), st(pick(Cs, ia)), st(pick(Cs, ib)), st(pick(ps, ia)), st(pick(ps, ib)))
-        dist = ops.fgw_pair_distance(*args, **kw) if grad else ops.fgw_pair_batched(*args, **kw)[1]
-    else:
-        args = (Ms, pick(Cs, ia), pick(Cs, ib), pick(ps, ia), pick(ps, ib))
-        dist = ops.fgw_pair_distance_list(*args, **kw) if grad else ops.fgw_pair_list(*args, **kw)[1]
-    out[ia, ib] = dist
-    out[ib, ia] = dist
-    return out
+    return _pairwise("fgw_pairwise_distances", Ys, Cs, ps, kw, (ops.fgw_pair_distance, ops.fgw_pair_distance_list), _PLAIN_PAIRS)
+
+
+def fgw_pairwise_distances_unrolled(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, alpha=0.5, epsilon=0.1, loss_fun="square_loss", symmetric=None,
+                                    max_iter=100, tol=1e-5, solver="PGD", numItermax=100, stopThr=1e-5) -> Tensor:
+    """fgw_pairwise_distances (same arguments, defaults, calls and bits of the matrix) with the TOTAL derivative: when any of Ys, Cs, ps requires
+    grad every entry carries the gradient of fgw_distance_unrolled — through every iteration of its pair's solve (ops.fgw_pair_unrolled: one
+    forward and one backward launch for all pairs) — and reaches Ys through feature_cost, Cs and ps.  solver "PGD" or "PPA", the square loss."""
+    kw = dict(alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, num_iter_max=numItermax, stop_thr=stopThr, loss_fun=loss_fun, solver=solver,
+              symmetric=symmetric)
+    if solver == "BAPG" or (solver in ("PGD", "PPA") and loss_fun == "kl_loss"):
+        ops._pair_unrolled_params(**kw)                                     # (raises: NotImplementedError under the new names)
+    return _pairwise("fgw_pairwise_distances_unrolled", Ys, Cs, ps, kw,
+                     (lambda *a, **k: ops.fgw_pair_unrolled(*a, **k)[1], lambda *a, **k: ops.fgw_pair_unrolled_list(*a, **k)[1]), _PLAIN_PAIRS)
 
 
 def normalize_tensor(tensor: Tensor, a: float, b: float) -> Tensor:

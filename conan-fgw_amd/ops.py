@@ -971,9 +971,10 @@ def _pair_tensor(t, name, *shape, keep_graph=False):
     return _c((t if keep_graph else t.detach()).to(f32))
 
 
-def _pair_prepare(M, C1, C2, p, q, G0, keep_graph=False):
+def _pair_prepare(M, C1, C2, p, q, G0, keep_graph=False, keep_start_graph=False):
     """The checked, contiguous fp32 operands of conan_fgw_pair_fwd, n1 != n2 embedded in N = max(n1, n2) with massless nodes -> (M, C1, C2, p, q, G0,
-    (B, N, n1, n2)).  keep_graph: the inputs are not detached, so that torch differentiates the conversion and the embedding (G0 never is)."""
+    (B, N, n1, n2)).  keep_graph: the inputs are not detached, so that torch differentiates the conversion and the embedding (G0 only with
+    keep_start_graph: the unrolled gradient reaches the start)."""
     if M.dim() != 3:
         raise ValueError(f"M must be [B,n1,n2], not {list(M.shape)}")
     B, n1, n2 = M.shape
@@ -981,7 +982,7 @@ def _pair_prepare(M, C1, C2, p, q, G0, keep_graph=False):
     M, C1, C2 = _pair_tensor(M, "M", B, n1, n2, **kg), _pair_tensor(C1, "C1", B, n1, n1, **kg), _pair_tensor(C2, "C2", B, n2, n2, **kg)
     p = None if p is None else _pair_tensor(p, "p", B, n1, **kg)
     q = None if q is None else _pair_tensor(q, "q", B, n2, **kg)
-    G0 = None if G0 is None else _pair_tensor(G0, "G0", B, n1, n2)
+    G0 = None if G0 is None else _pair_tensor(G0, "G0", B, n1, n2, keep_graph=keep_start_graph)
     dev, N = M.device, max(n1, n2)
     if n1 != n2:
         def pad(t, *shape):
@@ -1027,7 +1028,7 @@ def fgw_pair_batched(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = No
     return (T if n1 == n2 else T[:, :n1, :n2]), dist, info, errs
 
 
-def _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s, keep_graph=False):
+def _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s, keep_graph=False, keep_start_graph=False):
     """The ragged pairs of fgw_pair_list embedded in the common Np = max over all n1_b, n2_b -> (M, C1, C2, p, q, G0, sizes)."""
     B = len(Ms)
     if B == 0 or len(C1s) != B or len(C2s) != B:
@@ -1050,7 +1051,7 @@ def _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s, keep_graph=False):
     if G0s is not None and any(g is not None for g in G0s):
         if any(g is None for g in G0s):
             raise ValueError("G0s must hold a start plan for every pair or for none")
-        G0 = stack(G0s, 2, keep=False)
+        G0 = stack(G0s, 2, keep=keep_start_graph)
     return (stack(Ms, 2), stack(C1s, 2), stack(C2s, 2), stack(ps, 1, lambda b: torch.full((sizes[b][0],), 1.0 / sizes[b][0], device=dev)),
             stack(qs, 1, lambda b: torch.full((sizes[b][1],), 1.0 / sizes[b][1], device=dev)), G0, sizes)
 
@@ -1400,6 +1401,98 @@ def fgw_acc_pair_unrolled(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] 
         X, objs, info = _acc_fwd(M, A, Bm, a, b, X0, B, N, alpha, rho, epoch, eps)
         dist = _acc_dist(M, A, Bm, a, b, X, B, N, alpha)
     return (X if N1 == N2 else X[:, :N1, :N2]), dist, objs, info
+
+
+# ------------------------------------------------------------------- the reference's gradient through the unrolled pair solve (fgw_pair_grad.hip)
+class _FgwPairUnrolledFn(torch.autograd.Function):
+    """fgw_pair_batched's launch with conan_fgw_pair_bwd as its backward: the gradient through the executed PGD / PPA iterations and their
+    Sinkhorn sweeps, as the reference's autograd delivers it, from the cotangents of T and fgw_dist to M, C1, C2, p, q and G0.  The backward
+    is ONE launch that replays the iterations from the saved inputs (nothing but the inputs and info is kept from the forward).  No double
+    backward, no host synchronisation."""
+    @staticmethod
+    def forward(ctx, M, C1, C2, p, q, G0, dims, prm, solver_code, sym_code, exact):
+        B, N = dims
+        T, dist, info, errs = _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, solver_code, sym_code, True)
+        ctx.save_for_backward(M, C1, C2, p, q, G0, info)
+        # exact: the caller's alpha, epsilon, stop_thr as Python floats (the forward's parameter block holds their fp32 roundings; the replay runs in
+        # fp64 on what the reference's fp64 run is given)
+        ctx.dims, ctx.cfg = dims, (*exact[:2], int(prm.max_iter), int(prm.num_iter_max), exact[2], solver_code, sym_code)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(info, errs)
+        return T, dist, info, errs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gT, gdist, *_):
+        M, C1, C2, p, q, G0, info = ctx.saved_tensors
+        B, N = ctx.dims
+        if gT is None and gdist is None:
+            return (None,) * 11
+        alpha, epsilon, max_iter, num_iter_max, stop_thr, solver_code, sym_code = ctx.cfg
+        dev = M.device
+        gT = None if gT is None else _c(gT.to(f32))
+        gdist = None if gdist is None else _c(gdist.to(f32))
+        need = ctx.needs_input_grad
+        dM, dC1, dC2 = (torch.empty(B, N, N, dtype=f32, device=dev) for _ in range(3))
+        dp = torch.empty(B, N, dtype=f32, device=dev) if p is not None and need[3] else None
+        dq = torch.empty(B, N, dtype=f32, device=dev) if q is not None and need[4] else None
+        dG0 = torch.empty(B, N, N, dtype=f32, device=dev) if G0 is not None and need[5] else None
+        nbytes = int(lib().conan_fgw_pair_bwd_workspace_bytes(B, N, max_iter, num_iter_max))
+        if nbytes == 0:
+            raise NotImplementedError(f"the unrolled pairwise FGW gradient does not support N = {N}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("conan_fgw_pair_bwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, alpha, epsilon, max_iter, num_iter_max, stop_thr,
+             solver_code, sym_code, ptr(info), ptr(gT), ptr(gdist), ptr(dM), ptr(dC1), ptr(dC2), ptr(dp), ptr(dq), ptr(dG0), None, None, ptr(ws),
+             stream_ptr())
+        return (dM if need[0] else None, dC1 if need[1] else None, dC2 if need[2] else None, dp, dq, dG0) + (None,) * 5
+
+
+def _pair_unrolled_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric):
+    prm, solver_code, sym_code = _pair_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric)
+    if solver == "BAPG":
+        raise NotImplementedError("the unrolled pairwise FGW gradient covers solver 'PGD' and 'PPA': 'BAPG' is not implemented")
+    if loss_fun != "square_loss":
+        raise NotImplementedError("the unrolled pairwise FGW gradient covers loss_fun 'square_loss': 'kl_loss' is not implemented")
+    return prm, solver_code, sym_code
+
+
+def fgw_pair_unrolled(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, G0: Optional[Tensor] = None, *,
+                      alpha: float = 0.5, epsilon: float = 0.1, max_iter: int = 100, tol: float = 1e-5, num_iter_max: int = 100,
+                      stop_thr: float = 1e-5, loss_fun: str = "square_loss", solver: str = "PGD", symmetric=None):
+    """fgw_pair_batched's solve (same arguments, same launch, same bits) -> (T, fgw_dist, info, errs), where T and fgw_dist carry the reference's
+    gradient through the unrolled solve — what torch autograd forms through its fgw (bregman.py:70-167: every executed PGD / PPA iteration and
+    every Sinkhorn sweep inside it) — to M, C1, C2, p, q, and to G0 when one is given: the total derivative, not the one at a plan held
+    constant that fgw_pair_distance delivers.  One backward launch per backward call (conan_fgw_pair_bwd) serves both cotangents: it replays in
+    fp64 the iterations the forward ran (info[:, 0], read on the device), recording every iteration's input plan and deciding its Sinkhorn sweep
+    count by the reference's rule, and walks them in reverse.  Solver "PGD" or "PPA", the square loss, symmetric True / False / None; "BAPG" and
+    "kl_loss" raise NotImplementedError.  p / q given as None (uniform) get none; info and errs are not differentiable (the reference's
+    log["err"] is: a deviation), and the stop decisions carry no gradient.  A node without mass (p_i = 0, q_j = 0, the padding of rectangular
+    and own-size pairs) gets exactly 0 in its rows / columns of every gradient and in dp_i / dq_j, where the reference's log(0) gives NaN; a
+    pair with info flags bit 2, or whose replay meets a non-finite plan or, under PPA, the logarithm of an exact zero of a plan, gets NaN
+    gradients, as the reference's autograd gives, beside healthy pairs that keep theirs.  Rectangular pairs are embedded as in fgw_pair_batched
+    and the gradients come back in the caller's shapes; a leaf shared by the batch (an expanded M) gets the sum.  The backward's workspace is
+    B * ((max_iter + 3) N^2 + (4 num_iter_max + 2) N) * 8 bytes, N = max(n1, n2) (1.0 MB per 33 x 33 pair at the defaults; 76 KB at the models'
+    max_iter = 5, num_iter_max = 5), plus five N x N fp64 matrices per pair above N = 61; the caller chooses the caps.  When no input requires grad
+    nothing is saved and nothing beyond the forward runs.  No double backward, no host synchronisation in either direction."""
+    prm, solver_code, sym_code = _pair_unrolled_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric)
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (M, C1, C2, p, q, G0))
+    M, C1, C2, p, q, G0, (B, N, n1, n2) = _pair_prepare(M, C1, C2, p, q, G0, keep_graph=kg, keep_start_graph=kg)
+    if kg:
+        T, dist, info, errs = _FgwPairUnrolledFn.apply(M, C1, C2, p, q, G0, (B, N), prm, solver_code, sym_code, (float(alpha), float(epsilon), float(stop_thr)))
+    else:
+        T, dist, info, errs = _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, solver_code, sym_code, True)
+    return (T if n1 == n2 else T[:, :n1, :n2]), dist, info, errs
+
+
+def fgw_pair_unrolled_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
+    """fgw_pair_unrolled for pairs of different sizes (the lists of fgw_pair_list, one forward and one backward launch) ->
+    ([T_b [n1_b,n2_b]], fgw_dist [B], info, errs); the gradients reach the list entries in their own shapes, and a pair's bits do not depend on
+    the batch it is part of."""
+    _pair_unrolled_params(0.5, 0.1, 1, 1e-5, 1, 1e-5, params.get("loss_fun", "square_loss"), params.get("solver", "PGD"), None)      # the refusals first
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for ts in (Ms, C1s, C2s, ps, qs, G0s) if ts is not None for t in ts)
+    M, C1, C2, p, q, G0, sizes = _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s, keep_graph=kg, keep_start_graph=kg)
+    T, dist, info, errs = fgw_pair_unrolled(M, C1, C2, p, q, G0, **params)
+    return [T[b, :n1, :n2] for b, (n1, n2) in enumerate(sizes)], dist, info, errs
 
 
 # ------------------------------------------------------------------------------------------------ entropic OT on its own (sinkhorn.hip)
