@@ -27,6 +27,7 @@
 // The epochs themselves (acc_epochs, with the sizes and the LDS carve) are in fgw_acc_body.h: the unrolled gradient (fgw_acc_grad.hip) replays
 // them from the same text.
 #include "fgw_acc_body.h"
+#include "../../include/conan_fgw_hip_mixup_grad.h"
 
 namespace {
 
@@ -214,11 +215,16 @@ int conan_fgw_acc_pair_fwd(const float *M, const float *A, const float *Bm, cons
 
 long long conan_fgw_mixup_workspace_bytes(int B, int K, int N, int d) { return (long long)acc_workspace(B, K, N, d).total; }
 
+}  // extern "C"
+
+namespace {
 // The outer loop of fgw_barycenters_BAPG: as fgw_fwd_impl queues it — init, then max_iter times coupling solve, snapshot, update — with no
-// host synchronisation; a molecule that has converged leaves its workgroups at once (fgw_active).
-int conan_fgw_mixup_barycenter_fwd(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
-                                   const float *init_Y, int B, int K, int N, int d, const conan_fgw_params *params, double rho, int epoch, double eps,
-                                   float *Y, float *C, float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream) {
+// host synchronisation; a molecule that has converged leaves its workgroups at once (fgw_active).  record (nullable): the fp64 state after
+// init and after every update, [max_iter + 1][B][N,N] then [max_iter + 1][B][N,d], copied device to device as T_iter is (the unrolled
+// gradient, fgw_mixup_grad.hip, walks it back; a molecule that has converged keeps its state, so the later entries repeat its last one).
+int acc_mixup_fwd(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
+                  const float *init_Y, int B, int K, int N, int d, const conan_fgw_params *params, double rho, int epoch, double eps,
+                  float *Y, float *C, float *T, float *T_iter, int *info, float *errs, double *record, void *workspace, void *stream) {
     if (!Ys || !Cs || !params || !Y || !C || !T || !info || !errs || !workspace || B <= 0 || K <= 0 || N <= 0 || d <= 0) return CONAN_E_BADARG;
     if (params->max_iter <= 0 || acc_bad_step(rho, epoch, eps)) return CONAN_E_BADARG;
     if (params->fixed_features && !init_Y) return CONAN_E_BADARG;      // barycenter.py:311-313
@@ -238,7 +244,15 @@ int conan_fgw_mixup_barycenter_fwd(const float *Ys, const float *Cs, const float
     const bool lds = acc_lds(N) <= ACC_LDS_LIMIT;
     const size_t bytes = lds ? acc_lds(N) : acc_vec_bytes(N);
 
+    const size_t Nd = (size_t)N * d;
+    double *Crec = record, *Yrec = record ? record + (size_t)(c.prm.max_iter + 1) * B * NN : nullptr;
+    auto snapshot = [&](int t) {
+        (void)hipMemcpyAsync(Crec + (size_t)t * B * NN, c.Cw, (size_t)B * NN * sizeof(double), hipMemcpyDeviceToDevice, c.s);
+        (void)hipMemcpyAsync(Yrec + (size_t)t * B * Nd, c.Yw, (size_t)B * Nd * sizeof(double), hipMemcpyDeviceToDevice, c.s);
+    };
+
     k_fgw_acc_init<<<B, 256, 0, c.s>>>(Cs, init_C, init_Y, c.D, c.prm.max_iter, c.Cw, c.Yw, c.active, info, errs, Y, C);
+    if (record) snapshot(0);
     for (int outer = 0; outer < c.prm.max_iter; ++outer) {
         const int y_zero = (outer == 0 && !init_Y) ? 1 : 0;
         with_flags([&](auto L, auto KL) {
@@ -248,9 +262,29 @@ int conan_fgw_mixup_barycenter_fwd(const float *Ys, const float *Cs, const float
         if (T_iter)      // log["Ts_iter"] (barycenter.py:373): a snapshot per outer iteration, only when the caller asks for the log
             (void)hipMemcpyAsync(T_iter + (size_t)outer * B * K * NN, T, (size_t)B * K * NN * sizeof(float), hipMemcpyDeviceToDevice, c.s);
         conan_fgw_small_update(c, outer, false);
+        if (record) snapshot(outer + 1);
     }
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int conan_fgw_mixup_barycenter_fwd(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
+                                   const float *init_Y, int B, int K, int N, int d, const conan_fgw_params *params, double rho, int epoch, double eps,
+                                   float *Y, float *C, float *T, float *T_iter, int *info, float *errs, void *workspace, void *stream) {
+    return acc_mixup_fwd(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, rho, epoch, eps, Y, C, T, T_iter, info, errs, nullptr, workspace, stream);
+}
+
+// (declared in include/conan_fgw_hip_mixup_grad.h)
+int conan_fgw_mixup_barycenter_fwd_record(const float *Ys, const float *Cs, const float *ps, const float *p, const float *lambdas, const float *init_C,
+                                          const float *init_Y, int B, int K, int N, int d, const conan_fgw_params *params, double rho, int epoch,
+                                          double eps, float *Y, float *C, float *T, float *T_iter, int *info, float *errs, void *record,
+                                          void *workspace, void *stream) {
+    if (!record) return CONAN_E_BADARG;
+    return acc_mixup_fwd(Ys, Cs, ps, p, lambdas, init_C, init_Y, B, K, N, d, params, rho, epoch, eps, Y, C, T, T_iter, info, errs,
+                         static_cast<double *>(record), workspace, stream);
 }
 
 }  // extern "C"

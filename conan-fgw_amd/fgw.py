@@ -7,7 +7,8 @@ distance carry gradients at the solved couplings, held constant: see their docst
 `fused_ACC_unrolled` and `fgw_mixup_distance_unrolled` are the pair solve and its distance with the reference's own gradient, the one torch
 autograd forms through every epoch of fused_ACC_torch; `fgw_unrolled`, `fgw_distance_unrolled` and `fgw_pairwise_distances_unrolled` are
 `fgw`, `fgw_distance` and `fgw_pairwise_distances` with the reference's own gradient too, the one torch autograd forms through every PGD / PPA
-iteration and Sinkhorn sweep of its fgw).
+iteration and Sinkhorn sweep of its fgw; `fgw_barycenters_BAPG_unrolled` is `fgw_barycenters_BAPG` with the gradient torch autograd forms
+through the reference's, i.e. through every epoch of every coupling solve of every outer iteration).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
 barycenter.py:33-44).  `loss_fun` = "square_loss" (every model) or "kl_loss" (utils.py:20-32,76-87).  All three coupling solvers of the
@@ -238,24 +239,10 @@ def fgw_mixup_distance_unrolled(M, A, B, a=None, b=None, X=None, alpha=0, epoch=
     return (dist, {"T": Xo, "obj_list": objs}) if log else dist
 
 
-def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=None, lambdas=None, loss_fun="square_loss", alpha=0.5,
-                         max_iter=100, tol=1e-9, rho=1.0, verbose=False, log=False, init_C=None, init_Y=None, fixed_structure=False,
-                         fixed_features=False, seed=0, **kwargs):
-    """The FGWMixup barycenter, the reference's fgw_barycenters_BAPG (barycenter.py:259-390): the outer loop of fgw_barycenters around
-    fused_ACC_torch (100 epochs at most, eps = 1e-5, the caller's rho, always from p ps[s]^T).  This is not fgw_barycenters(solver="BAPG"),
-    which runs the Bregman projections of fgw_bregman.  Same argument names, defaults, ValueErrors, return values and log keys as the
-    reference (the log also carries n_outer and n_inner, the outer iterations and the epochs summed over all coupling solves).  Cs may be
-    directed.  Input graphs of other sizes are embedded with massless nodes, as in fgw_barycenters.
-    Differentiable in the project's fixed-plan convention, the one fgw_barycenters uses: Y and C carry gradients to Ys, Cs, p and lambdas (to
-    init_Y / init_C instead of Ys / Cs under fixed_features / fixed_structure); ps gets none, nor do log["T"], log["Ts_iter"] and log["Ms"].  The
-    gradient is that of the last update steps (update_feature_matrix, update_square_loss / update_kl_loss) at the couplings T[s] of the last outer
-    iteration, held constant — the treatment fgw_barycenters gives its couplings (barycenter.py:120) — and NOT what the reference's
-    fgw_barycenters_BAPG gives under autograd, which back-propagates through all 100 epochs of every fused_ACC_torch call.  There is no double
-    backward.  A finite difference of this function moves the plan, so it does not check this gradient.  Gradients of embedded inputs arrive in
-    the caller's own shapes, and a node without mass receives exactly zero.  A run that ends in NaN (below) gives NaN gradients.
-    Other deviations: ps=None means uniform weights (the reference raises a TypeError); the run is an fp64 iteration on the fp32 inputs, so
-    iteration counts follow the reference's fp64 run; a weight that is exactly ZERO marks an absent node (the reference lifts its entries by
-    1e-10 every epoch); a NaN result (exp under- / overflow at small rho) is the reference's NaN.  Runs on the GPU only."""
+def _barycenters_BAPG(name, solve, N, Ys, Cs, ps, p, lambdas, loss_fun, alpha, max_iter, tol, rho, log, init_C, init_Y, fixed_structure,
+                      fixed_features, seed):
+    """fgw_barycenters_BAPG and fgw_barycenters_BAPG_unrolled around their op `solve` (ops.fgw_mixup_barycenter_batched / _unrolled): the
+    reference's checks, the embedding of other sizes, the seeded start and the log."""
     if loss_fun not in ("square_loss", "kl_loss"):
         raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
     if fixed_structure and init_C is None:
@@ -265,7 +252,7 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
     N = int(N)
     Ys_in = Ys.unbind(0) if torch.is_tensor(Ys) else Ys
     if not all(torch.is_tensor(y) and y.is_cuda for y in Ys_in):
-        raise NotImplementedError("fgw_barycenters_BAPG runs on the GPU only: pass CUDA (ROCm) tensors")
+        raise NotImplementedError(f"{name} runs on the GPU only: pass CUDA (ROCm) tensors")
     Ys_l = [y.to(torch.float32) for y in Ys_in]
     Cs_l = [c.to(torch.float32) for c in (Cs.unbind(0) if torch.is_tensor(Cs) else Cs)]
     K, d = len(Ys_l), Ys_l[0].shape[1]
@@ -291,7 +278,7 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
             lam = torch.stack([torch.as_tensor(l, dtype=torch.float32, device=dev).reshape(()) for l in lambdas])
         else:
             lam = torch.as_tensor([float(l) for l in lambdas], dtype=torch.float32, device=dev)
-    res = ops.fgw_mixup_barycenter_batched(
+    res = solve(
         torch.stack(Ys_l).view(1, K, N, d), torch.stack(Cs_l).view(1, K, N, N), ps=ps_t, p=p_t, lambdas=lam,
         init_C=init_C.to(torch.float32).to(dev).view(1, N, N), init_Y=None if init_Y is None else init_Y.to(torch.float32).to(dev).view(1, N, d),
         alpha=alpha, rho=rho, max_iter=max_iter, tol=tol, epoch=100, eps=1e-5, fixed_structure=fixed_structure, fixed_features=fixed_features,
@@ -310,6 +297,45 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
             "p": p if p is not None else torch.ones(N_user, device=dev) / N_user,
             "Ms": Ms, "n_outer": outer, "n_inner": int(info[0, 1].item())}
     return Y, C, log_
+
+
+def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=None, lambdas=None, loss_fun="square_loss", alpha=0.5,
+                         max_iter=100, tol=1e-9, rho=1.0, verbose=False, log=False, init_C=None, init_Y=None, fixed_structure=False,
+                         fixed_features=False, seed=0, **kwargs):
+    """The FGWMixup barycenter, the reference's fgw_barycenters_BAPG (barycenter.py:259-390): the outer loop of fgw_barycenters around
+    fused_ACC_torch (100 epochs at most, eps = 1e-5, the caller's rho, always from p ps[s]^T).  This is not fgw_barycenters(solver="BAPG"),
+    which runs the Bregman projections of fgw_bregman.  Same argument names, defaults, ValueErrors, return values and log keys as the
+    reference (the log also carries n_outer and n_inner, the outer iterations and the epochs summed over all coupling solves).  Cs may be
+    directed.  Input graphs of other sizes are embedded with massless nodes, as in fgw_barycenters.
+    Differentiable in the project's fixed-plan convention, the one fgw_barycenters uses: Y and C carry gradients to Ys, Cs, p and lambdas (to
+    init_Y / init_C instead of Ys / Cs under fixed_features / fixed_structure); ps gets none, nor do log["T"], log["Ts_iter"] and log["Ms"].  The
+    gradient is that of the last update steps (update_feature_matrix, update_square_loss / update_kl_loss) at the couplings T[s] of the last outer
+    iteration, held constant — the treatment fgw_barycenters gives its couplings (barycenter.py:120) — and NOT what the reference's
+    fgw_barycenters_BAPG gives under autograd, which back-propagates through all 100 epochs of every fused_ACC_torch call.  There is no double
+    backward.  A finite difference of this function moves the plan, so it does not check this gradient.  Gradients of embedded inputs arrive in
+    the caller's own shapes, and a node without mass receives exactly zero.  A run that ends in NaN (below) gives NaN gradients.
+    Other deviations: ps=None means uniform weights (the reference raises a TypeError); the run is an fp64 iteration on the fp32 inputs, so
+    iteration counts follow the reference's fp64 run; a weight that is exactly ZERO marks an absent node (the reference lifts its entries by
+    1e-10 every epoch); a NaN result (exp under- / overflow at small rho) is the reference's NaN.  Runs on the GPU only.
+    fgw_barycenters_BAPG_unrolled is the same solve with the reference's gradient through every epoch of every coupling solve."""
+    return _barycenters_BAPG("fgw_barycenters_BAPG", ops.fgw_mixup_barycenter_batched, N, Ys, Cs, ps, p, lambdas, loss_fun, alpha, max_iter, tol, rho,
+                             log, init_C, init_Y, fixed_structure, fixed_features, seed)
+
+
+def fgw_barycenters_BAPG_unrolled(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=None, lambdas=None, loss_fun="square_loss", alpha=0.5,
+                                  max_iter=100, tol=1e-9, rho=1.0, verbose=False, log=False, init_C=None, init_Y=None, fixed_structure=False,
+                                  fixed_features=False, seed=0, **kwargs):
+    """fgw_barycenters_BAPG (same arguments, ValueErrors, embedding of other sizes, return values and log keys, the same solve bit for bit)
+    whose Y and C carry the gradient that torch autograd forms through the reference's fgw_barycenters_BAPG (barycenter.py:259-390, whose
+    coupling solves run with autograd on): through the update steps, the feature costs and every epoch of every fused_ACC_torch call of every
+    outer iteration, not at couplings held constant.  Gradients reach Ys, Cs, ps, p, lambdas, init_C and init_Y; those of embedded (other-size)
+    inputs arrive in the caller's shapes, and a node without mass receives exactly zero.  ps=None and p=None mean uniform weights and get no
+    gradient; the seeded random init_C (when none is given) is a constant; lambdas given as a list of 0-d tensors keeps its graph.
+    Deviations: log["T"], log["Ts_iter"] and log["Ms"] carry no gradient (the reference's have a graph); the stop decisions carry none; a
+    weight that is exactly zero marks an absent node; a run that ends in NaN gives NaN gradients.  No double backward.  The backward replays
+    every coupling solve (ops.fgw_mixup_barycenter_unrolled states its launches and workspace).  Runs on the GPU only."""
+    return _barycenters_BAPG("fgw_barycenters_BAPG_unrolled", ops.fgw_mixup_barycenter_unrolled, N, Ys, Cs, ps, p, lambdas, loss_fun, alpha, max_iter,
+                             tol, rho, log, init_C, init_Y, fixed_structure, fixed_features, seed)
 
 
 _FAILED = "Solver failed to produce a transport plan. You might want to increase the regularization parameter `epsilon`."

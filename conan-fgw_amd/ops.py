@@ -1202,7 +1202,8 @@ def fgw_mixup_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = 
     difference of this function moves the plan, so it does not check this gradient.  With only Ys requiring grad C is non-differentiable and
     the backward is conan_fgw_barycenter_bwd alone.  A molecule whose flags have bit 2 (NaN outputs) gives NaN gradients for its own inputs
     and, through the sum over molecules, for lambdas; they are not masked.  With no input requiring grad, or under torch.no_grad(), nothing
-    is saved and the call is the forward launch alone."""
+    is saved and the call is the forward launch alone.  fgw_mixup_barycenter_unrolled is the same solve with the reference's gradient through
+    every epoch of every coupling solve."""
     if loss_fun not in ("square_loss", "kl_loss"):
         raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
     rho, epoch, eps = _mixup_step(rho, epoch, eps)
@@ -1220,6 +1221,111 @@ def fgw_mixup_barycenter_batched(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = 
     prm = _fgw_params(alpha, 0.0, max_iter, tol, 0.0, 1, 0.0, fixed_structure, fixed_features, False, loss_fun)
     if kg:
         return _FgwMixupBarycenterFn.apply(Ys, Cs, ps, p, lambdas, init_C, init_Y, (prm, rho, epoch, eps, bool(keep_iterates)))
+    res = _mixup_barycenter_fwd(Ys, Cs, ps, p, lambdas, init_C, init_Y, prm, rho, epoch, eps, keep_iterates)
+    return res[:5] if res[5] is None else res
+
+
+# ------------------------------------------------------------------- the reference's gradient through the unrolled barycenter (fgw_mixup_grad.hip)
+class _FgwMixupUnrolledFn(torch.autograd.Function):
+    """fgw_mixup_barycenter_batched's solve (conan_fgw_mixup_barycenter_fwd_record: the same launches plus device-to-device copies of the fp64
+    state) with conan_fgw_mixup_barycenter_bwd as its backward: the gradient through every epoch of every coupling solve of every outer iteration,
+    as the reference's autograd delivers it, from the cotangents of Y and C to Ys, Cs, ps, p, lambdas, init_C and init_Y.  Kept from the forward:
+    the inputs, info and the state record.  params = (conan_fgw_params, rho, epoch, eps, keep_iterates).  No double backward, no host
+    synchronisation."""
+    @staticmethod
+    def forward(ctx, Ys, Cs, ps, p, lambdas, init_C, init_Y, params):
+        prm, rho, epoch, eps, keep_iterates = params
+        B, K, N, d = Ys.shape
+        dev = Ys.device
+        Y = torch.empty(B, N, d, dtype=f32, device=dev)
+        C = torch.empty(B, N, N, dtype=f32, device=dev)
+        T = torch.empty(B, K, N, N, dtype=f32, device=dev)
+        T_iter = torch.empty(prm.max_iter, B, K, N, N, dtype=f32, device=dev) if keep_iterates else None
+        info = torch.empty(B, 4, dtype=i32, device=dev)
+        errs = torch.empty(B, 2, prm.max_iter, dtype=f32, device=dev)
+        record = torch.empty((prm.max_iter + 1) * B * (N * N + N * d), dtype=torch.float64, device=dev)
+        ws = torch.empty(int(lib().conan_fgw_mixup_workspace_bytes(B, K, N, d)), dtype=torch.uint8, device=dev)
+        call("conan_fgw_mixup_barycenter_fwd_record", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_C), ptr(init_Y), B, K, N, d,
+             ctypes.byref(prm), rho, epoch, eps, ptr(Y), ptr(C), ptr(T), ptr(T_iter), ptr(info), ptr(errs), ptr(record), ptr(ws), stream_ptr())
+        ctx.save_for_backward(Ys, Cs, ps, p, lambdas, init_Y, info, record)
+        ctx.dims, ctx.params, ctx.has_init_C = (B, K, N, d), (prm, rho, epoch, eps), init_C is not None
+        ctx.set_materialize_grads(False)
+        nd = (T, info, errs) if T_iter is None else (T, info, errs, T_iter)
+        ctx.mark_non_differentiable(*nd)
+        return (Y, C) + nd
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dY, dC=None, *_):
+        if dY is None and dC is None:
+            return (None,) * 8
+        Ys, Cs, ps, p, lambdas, init_Y, info, record = ctx.saved_tensors
+        B, K, N, d = ctx.dims
+        prm, rho, epoch, eps = ctx.params
+        need = ctx.needs_input_grad
+        dev = Ys.device
+        dY = None if dY is None else _c(dY.to(f32))
+        dC = None if dC is None else _c(dC.to(f32))
+        new = lambda want, *shape: torch.empty(*shape, dtype=f32, device=dev) if want else None
+        start_in_Cs = not ctx.has_init_C                  # the start is Cs[:, 0]: its gradient goes there
+        dYs = new(need[0], B, K, N, d)
+        dCs = new(need[1], B, K, N, N)
+        dps = new(need[2] and ps is not None, B, K, N)
+        dp = new(need[3] and p is not None, B, N)
+        dlam = new(need[4] and lambdas is not None, K)
+        dinit_C = new(need[5] if ctx.has_init_C else need[1], B, N, N)
+        dinit_Y = new(need[6] and init_Y is not None, B, N, d)
+        nbytes = int(lib().conan_fgw_mixup_barycenter_bwd_workspace_bytes(B, K, N, d, epoch))
+        if nbytes == 0:
+            raise NotImplementedError(f"the unrolled FGWMixup barycenter gradient does not support N = {N}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("conan_fgw_mixup_barycenter_bwd", ptr(Ys, f32), ptr(Cs, f32), ptr(ps), ptr(p), ptr(lambdas), ptr(init_Y), B, K, N, d, ctypes.byref(prm),
+             rho, epoch, eps, ptr(info), ptr(record), ptr(dY), ptr(dC), ptr(dYs), ptr(dCs), ptr(dps), ptr(dp), ptr(dlam), ptr(dinit_C), ptr(dinit_Y),
+             None, None, ptr(ws), stream_ptr())
+        if start_in_Cs and dCs is not None:
+            dCs[:, 0] += dinit_C
+            dinit_C = None
+        return dYs, dCs, dps, dp, dlam, dinit_C, dinit_Y, None
+
+
+def fgw_mixup_barycenter_unrolled(Ys: Tensor, Cs: Tensor, ps: Optional[Tensor] = None, p: Optional[Tensor] = None, lambdas: Optional[Tensor] = None,
+                                  init_C: Optional[Tensor] = None, init_Y: Optional[Tensor] = None, *, alpha: float = 0.5, rho: float = 1.0,
+                                  max_iter: int = 100, tol: float = 1e-9, epoch: int = 100, eps: float = 1e-5, fixed_structure: bool = False,
+                                  fixed_features: bool = False, loss_fun: str = "square_loss", keep_iterates: bool = False):
+    """fgw_mixup_barycenter_batched's solve (same arguments, defaults, checks and return tuple; Y, C, T, info, errs and T_iter bit-identical)
+    whose Y and C carry the gradient that torch autograd forms through the reference's fgw_barycenters_BAPG (barycenter.py:259-390: its
+    coupling solves run with autograd on): through the update steps, the feature costs and every epoch of every coupling solve of every outer
+    iteration — the total derivative, not the one at couplings held constant that fgw_mixup_barycenter_batched delivers.  Gradients reach Ys,
+    Cs, ps, p, lambdas, init_C and init_Y.  With init_C=None the start is Cs[:, 0] and its gradient goes there; with init_Y=None the start is
+    a constant zero.  T, info, errs and T_iter are not differentiable (a deviation: the reference's log["T"] has a graph), and the stop
+    decisions carry no gradient.  A weight that is exactly zero marks an absent node: it gets exactly 0 in all its entries.  A molecule whose
+    info flags have bit 2 gets NaN in its own gradients and, through the sum over molecules, in dlambdas.
+    The forward adds device-to-device copies of the barycenter's fp64 state after init and after every update to the batched op's launches:
+    (max_iter + 1) * B * (N^2 + N d) * 8 bytes, kept for the backward with the inputs and info.  The backward (conan_fgw_mixup_barycenter_bwd)
+    is 2 max_iter + 1 launches: per outer iteration, descending, one workgroup per coupling that replays the solve (with the forward's
+    objective checks, so it stops where the forward did), forms the update steps' partials, walks the half-steps in reverse and differentiates
+    the feature cost, then one workgroup per molecule that sums the couplings' shares; one last launch rounds to fp32.  A molecule that ran
+    fewer outer iterations (info[:, 0], read on the device) leaves the earlier launches at once.  Its workspace holds the record of one
+    solve's half-steps per coupling, reused by every outer iteration: B * K * 2 epoch * N^2 * 8 bytes (2.2 GB at B K = 1280, N = 33, epoch
+    100), plus B K (4 N^2 + 2 N d) * 8 bytes of accumulators and five N x N fp64 matrices per coupling above N = 61.  When no input requires
+    grad, or under torch.no_grad(), nothing beyond the batched op's forward runs and nothing is saved.  No double backward, no host
+    synchronisation in either direction."""
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    rho, epoch, eps = _mixup_step(rho, epoch, eps)
+    if Ys.dim() != 4:
+        raise ValueError(f"Ys must be [B,K,N,d], not {list(Ys.shape)}")
+    B, K, N, d = Ys.shape
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (Ys, Cs, ps, p, lambdas, init_C, init_Y))
+    opt = lambda t, name, *shape: None if t is None else _mixup_tensor(t, name, *shape, keep_graph=kg)
+    Ys, Cs = opt(Ys, "Ys", B, K, N, d), opt(Cs, "Cs", B, K, N, N)
+    ps, p, lambdas = opt(ps, "ps", B, K, N), opt(p, "p", B, N), opt(lambdas, "lambdas", K)
+    init_C, init_Y = opt(init_C, "init_C", B, N, N), opt(init_Y, "init_Y", B, N, d)
+    if fixed_features and init_Y is None:
+        raise ValueError("If Y is fixed it must be initialized")
+    prm = _fgw_params(alpha, 0.0, max_iter, tol, 0.0, 1, 0.0, fixed_structure, fixed_features, False, loss_fun)
+    if kg:
+        return _FgwMixupUnrolledFn.apply(Ys, Cs, ps, p, lambdas, init_C, init_Y, (prm, rho, epoch, eps, bool(keep_iterates)))
     res = _mixup_barycenter_fwd(Ys, Cs, ps, p, lambdas, init_C, init_Y, prm, rho, epoch, eps, keep_iterates)
     return res[:5] if res[5] is None else res
 
