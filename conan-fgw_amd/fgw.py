@@ -7,7 +7,8 @@ distance carry gradients at the solved couplings, held constant: see their docst
 `fused_ACC_unrolled` and `fgw_mixup_distance_unrolled` are the pair solve and its distance with the reference's own gradient, the one torch
 autograd forms through every epoch of fused_ACC_torch; `fgw_unrolled`, `fgw_distance_unrolled` and `fgw_pairwise_distances_unrolled` are
 `fgw`, `fgw_distance` and `fgw_pairwise_distances` with the reference's own gradient too, the one torch autograd forms through every PGD / PPA
-iteration and Sinkhorn sweep of its fgw; `fgw_barycenters_BAPG_unrolled` is `fgw_barycenters_BAPG` with the gradient torch autograd forms
+iteration and Sinkhorn sweep of its fgw; `fgw_bregman_unrolled` and `fgw_bregman_distance_unrolled` are `fgw_bregman` and its distance with
+the gradient torch autograd forms through every Bregman half-step of the reference's fgw_bregman, for both losses; `fgw_barycenters_BAPG_unrolled` is `fgw_barycenters_BAPG` with the gradient torch autograd forms
 through the reference's, i.e. through every epoch of every coupling solve of every outer iteration).
 
 Same argument names, defaults and error behaviour (`ValueError` for unknown `loss_fun` / `stop_criterion` / `solver`,
@@ -492,6 +493,68 @@ def fgw_distance_unrolled(M, C1, C2, p=None, q=None, loss_fun="square_loss", eps
     and deviations as fgw_unrolled.  Runs on the GPU only."""
     T, dist, log_ = _pair_solve_unrolled("fgw_distance_unrolled", M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, solver, method, warmstart,
                                          kwargs)
+    if not log:
+        return dist
+    log_["fgw_dist"], log_["T"] = dist.detach(), T
+    return dist, log_
+
+
+def _bregman_solve_unrolled(fn, M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, marginal_loss):
+    """The refusals of the unrolled BAPG names, then one pair through ops.fgw_bregman_unrolled (B = 1) -> (T, dist, log without "fgw_dist" / "T")."""
+    if loss_fun not in ("square_loss", "kl_loss"):
+        raise ValueError(f"Unknown `loss_fun='{loss_fun}'`. Use one of: {'square_loss', 'kl_loss'}.")
+    if marginal_loss:
+        raise NotImplementedError("marginal_loss=True is not implemented")
+    for name, t in (("M", M), ("C1", C1), ("C2", C2), ("p", p), ("q", q), ("G0", G0)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"{fn} runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    one = lambda t: None if t is None else t.unsqueeze(0)
+    T, dist, info, errs = ops.fgw_bregman_unrolled(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter,
+                                                   tol=tol, loss_fun=loss_fun, symmetric=symmetric)
+    T, dist = T[0], dist[0]
+    if bool(torch.isnan(T.detach()).any()):                                 # bregman.py:267-270, one host synchronisation as in the reference
+        warnings.warn(_FAILED)
+    # bregman.py:274-275: fgw_dist - alpha sum(constC o T), constC = f1(C1) p 1^T + 1 (f2(C2) q)^T of init_matrix (utils.py:20-64), in torch
+    n1, n2 = M.shape
+    pw = torch.full((n1,), 1.0 / n1, dtype=T.dtype, device=T.device) if p is None else p.to(T.dtype)
+    qw = torch.full((n2,), 1.0 / n2, dtype=T.dtype, device=T.device) if q is None else q.to(T.dtype)
+    a, b = C1.to(T.dtype), C2.to(T.dtype)
+    f1, f2 = (a * a, b * b) if loss_fun == "square_loss" else (a * torch.log(a + 1e-15) - a, b)
+    constC = (f1 @ pw)[:, None] + (f2 @ qw)[None, :]
+    n_iter = int(info[0, 0].item())
+    return T, dist, {"err": [errs[0, i] for i in range((n_iter + 9) // 10)], "loss": dist - alpha * torch.sum(constC * T), "n_iter": n_iter, "n_sinkhorn": 0}
+
+
+def fgw_bregman_unrolled(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=1000, tol=1e-9,
+                         marginal_loss=False, verbose=False, log=False):
+    """fgw_bregman (same arguments, defaults, solve, warning and bits) with DIFFERENTIABLE outputs, as the reference's call delivers them: T, and
+    with log=True log["fgw_dist"] and log["loss"], carry the gradient torch autograd forms through the reference's fgw_bregman — back through
+    every executed Bregman half-step — to M, C1, C2, p, q and to G0 when one is given (ops.fgw_bregman_unrolled: one backward launch that
+    replays the iterations and walks the half-steps in reverse).  Both losses, symmetric True / False / None.  log=True: (T, {"err", "fgw_dist",
+    "loss", "n_iter", "n_sinkhorn": 0}); log["loss"] is the reference's fgw_dist - alpha sum(constC * T) (bregman.py:274-275), formed in torch
+    from T, fgw_dist and the constC torch computes from C1, C2, p, q, so its gradient is the reference's by composition.  marginal_loss=True
+    raises NotImplementedError.  Deviations from the reference beyond fgw_bregman's: log["err"] carries no gradient; a node whose weight is
+    exactly ZERO gets gradient 0 (the reference: NaN from 0 / 0); no double backward.  A solve the reference answers with a NaN plan gives NaN
+    gradients and the reference's warning.  The backward's workspace is (2 max_iter + 4) N^2 * 8 bytes, N = max(n1, n2): 1.8 MB at N = 33 for
+    max_iter = 100, 17.5 MB for the default 1000 (whatever the iterations run: the count stays on the device); the cap is the caller's choice.
+    Runs on the GPU only."""
+    T, dist, log_ = _bregman_solve_unrolled("fgw_bregman_unrolled", M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol, marginal_loss)
+    if not log:
+        return T
+    log_["fgw_dist"] = dist
+    return T, log_
+
+
+def fgw_bregman_distance_unrolled(M, C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, symmetric=None, alpha=0.5, G0=None, max_iter=1000,
+                                  tol=1e-9, marginal_loss=False, verbose=False, log=False):
+    """fgw_distance(solver="BAPG")'s value and bits with the TOTAL derivative, under fgw_bregman's signature: the 0-d distance carries the gradient
+    of the reference's log["fgw_dist"].backward() through fgw_bregman — the plan moving with the inputs — to M, C1, C2, p, q and the start G0,
+    where fgw_distance holds the plan fixed.  A central difference of this function (at a fixed iteration count) does check this gradient.
+    log=True: (dist, {"T": the plan, which carries the unrolled gradient too, "err", "fgw_dist" (detached), "loss", "n_iter", "n_sinkhorn": 0}).
+    Refusals, deviations and workspace ((2 max_iter + 4) N^2 * 8 bytes: 1.8 MB at N = 33 for max_iter = 100, 17.5 MB for 1000) as
+    fgw_bregman_unrolled.  Runs on the GPU only."""
+    T, dist, log_ = _bregman_solve_unrolled("fgw_bregman_distance_unrolled", M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_iter, tol,
+                                            marginal_loss)
     if not log:
         return dist
     log_["fgw_dist"], log_["T"] = dist.detach(), T

@@ -1601,6 +1601,86 @@ def fgw_pair_unrolled_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
     return [T[b, :n1, :n2] for b, (n1, n2) in enumerate(sizes)], dist, info, errs
 
 
+# ------------------------------------------------------------- the reference's gradient through the unrolled BAPG pair solve (fgw_bregman_grad.hip)
+class _FgwBregmanUnrolledFn(torch.autograd.Function):
+    """fgw_pair_batched(solver="BAPG")'s launch with conan_fgw_bregman_bwd as its backward: the gradient through the executed Bregman half-steps,
+    as the reference's autograd delivers it through fgw_bregman, from the cotangents of T and fgw_dist to M, C1, C2, p, q and G0.  The backward
+    is ONE launch that replays the iterations from the saved inputs (nothing but the inputs and info is kept from the forward).  No double
+    backward, no host synchronisation."""
+    @staticmethod
+    def forward(ctx, M, C1, C2, p, q, G0, dims, prm, sym_code, exact):
+        B, N = dims
+        T, dist, info, errs = _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, FGW_SOLVERS["BAPG"], sym_code, True)
+        ctx.save_for_backward(M, C1, C2, p, q, G0, info)
+        # exact: the caller's alpha, epsilon as Python floats (the forward's parameter block holds their fp32 roundings; the replay runs in fp64 on
+        # what the reference's fp64 run is given)
+        ctx.dims, ctx.cfg = dims, (*exact, int(prm.max_iter), int(prm.loss_fun), sym_code)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(info, errs)
+        return T, dist, info, errs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gT, gdist, *_):
+        M, C1, C2, p, q, G0, info = ctx.saved_tensors
+        B, N = ctx.dims
+        if gT is None and gdist is None:
+            return (None,) * 10
+        alpha, epsilon, max_iter, loss_code, sym_code = ctx.cfg
+        dev = M.device
+        gT = None if gT is None else _c(gT.to(f32))
+        gdist = None if gdist is None else _c(gdist.to(f32))
+        need = ctx.needs_input_grad
+        dM, dC1, dC2 = (torch.empty(B, N, N, dtype=f32, device=dev) for _ in range(3))
+        dp = torch.empty(B, N, dtype=f32, device=dev) if p is not None and need[3] else None
+        dq = torch.empty(B, N, dtype=f32, device=dev) if q is not None and need[4] else None
+        dG0 = torch.empty(B, N, N, dtype=f32, device=dev) if G0 is not None and need[5] else None
+        nbytes = int(lib().conan_fgw_bregman_bwd_workspace_bytes(B, N, max_iter))
+        if nbytes == 0:
+            raise NotImplementedError(f"the unrolled BAPG FGW gradient does not support N = {N}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("conan_fgw_bregman_bwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, alpha, epsilon, max_iter, loss_code,
+             sym_code, ptr(info), ptr(gT), ptr(gdist), ptr(dM), ptr(dC1), ptr(dC2), ptr(dp), ptr(dq), ptr(dG0), None, None, ptr(ws), stream_ptr())
+        return (dM if need[0] else None, dC1 if need[1] else None, dC2 if need[2] else None, dp, dq, dG0) + (None,) * 4
+
+
+def fgw_bregman_unrolled(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, G0: Optional[Tensor] = None, *,
+                         alpha: float = 0.5, epsilon: float = 0.1, max_iter: int = 1000, tol: float = 1e-9, loss_fun: str = "square_loss",
+                         symmetric=None):
+    """fgw_pair_batched(solver="BAPG")'s solve (same launch, same bits) -> (T, fgw_dist, info, errs), where T and fgw_dist carry the reference's
+    gradient through the unrolled solve — what torch autograd forms through its fgw_bregman (bregman.py:170-279: every executed Bregman
+    half-step) — to M, C1, C2, p, q, and to G0 when one is given: the total derivative, not the one at a plan held constant that
+    fgw_pair_distance delivers.  One backward launch per backward call (conan_fgw_bregman_bwd) serves both cotangents: it replays in fp64 the
+    iterations the forward ran (info[:, 0], read on the device, never re-decided), recording every half-step's input plan, and walks the
+    half-steps in reverse.  loss_fun "square_loss" or "kl_loss", symmetric True / False / None.  p / q given as None (uniform) get none; info
+    and errs are not differentiable (the reference's log["err"] is: a deviation), and the stop decisions carry no gradient.  A node without mass
+    (p_i = 0, q_j = 0, the padding of rectangular and own-size pairs) gets exactly 0 in its rows / columns of every gradient and in dp_i / dq_j,
+    where the reference's 0 / 0 gives NaN; a pair with info flags bit 2, or whose replay meets a zero sum or a non-finite plan, gets NaN
+    gradients, as the reference's autograd gives, beside healthy pairs that keep theirs.  Rectangular pairs are embedded as in fgw_pair_batched
+    and the gradients come back in the caller's shapes; a leaf shared by the batch (an expanded M) gets the sum.  The backward's workspace is
+    B * (2 max_iter + 4) N^2 * 8 bytes, N = max(n1, n2) (1.8 MB per 33 x 33 pair at max_iter = 100, 17.5 MB at the default 1000), plus five
+    N x N fp64 matrices per pair above N = 61; the cap is the caller's choice.  When no input requires grad nothing is saved and nothing beyond
+    the forward runs.  No double backward, no host synchronisation in either direction."""
+    prm, _, sym_code = _pair_params(alpha, epsilon, max_iter, tol, 1, 1e-9, loss_fun, "BAPG", symmetric)
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (M, C1, C2, p, q, G0))
+    M, C1, C2, p, q, G0, (B, N, n1, n2) = _pair_prepare(M, C1, C2, p, q, G0, keep_graph=kg, keep_start_graph=kg)
+    if kg:
+        T, dist, info, errs = _FgwBregmanUnrolledFn.apply(M, C1, C2, p, q, G0, (B, N), prm, sym_code, (float(alpha), float(epsilon)))
+    else:
+        T, dist, info, errs = _pair_fwd(M, C1, C2, p, q, G0, B, N, prm, FGW_SOLVERS["BAPG"], sym_code, True)
+    return (T if n1 == n2 else T[:, :n1, :n2]), dist, info, errs
+
+
+def fgw_bregman_unrolled_list(Ms, C1s, C2s, ps=None, qs=None, G0s=None, **params):
+    """fgw_bregman_unrolled for pairs of different sizes (the lists of fgw_pair_list, one forward and one backward launch) ->
+    ([T_b [n1_b,n2_b]], fgw_dist [B], info, errs); the gradients reach the list entries in their own shapes, and a pair's bits do not depend on
+    the batch it is part of."""
+    kg = torch.is_grad_enabled() and any(t is not None and t.requires_grad for ts in (Ms, C1s, C2s, ps, qs, G0s) if ts is not None for t in ts)
+    M, C1, C2, p, q, G0, sizes = _pair_list_stack(Ms, C1s, C2s, ps, qs, G0s, keep_graph=kg, keep_start_graph=kg)
+    T, dist, info, errs = fgw_bregman_unrolled(M, C1, C2, p, q, G0, **params)
+    return [T[b, :n1, :n2] for b, (n1, n2) in enumerate(sizes)], dist, info, errs
+
+
 # ------------------------------------------------------------------------------------------------ entropic OT on its own (sinkhorn.hip)
 SINKHORN_METHODS = {"sinkhorn_log": 0, "sinkhorn": 1}
 
