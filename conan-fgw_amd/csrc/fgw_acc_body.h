@@ -2,12 +2,12 @@
 // the two forward kernels of fgw_acc.hip and the replay of the unrolled gradient (fgw_acc_grad.hip), which has to retrace the forward's iterates
 // bit for bit.  The file comment of fgw_acc.hip describes the iteration.
 #pragma once
-#include "fgw_common.h"
+#include "fgw_unroll.h"
 
 namespace {
 
-constexpr int ACC_NW = 8;
-constexpr size_t ACC_LDS_LIMIT = 160 * 1024;
+constexpr int ACC_NW = UNROLL_NW;           // (the replay hands acc_epochs the backward's pm: one wavefront count for both)
+constexpr size_t ACC_LDS_LIMIT = LDS_LIMIT;
 
 // vectors: a, b, the scaling factors, |y_i|^2, |z_j|^2 [N] each, 16 doubles of reduction space, per-wavefront partial sums [NW][N]; rounded to 16 bytes
 __host__ __device__ inline size_t acc_vec_bytes(int N) { return ((size_t)((5 + ACC_NW) * N + 16) * 8 + 15) / 16 * 16; }

@@ -1,7 +1,7 @@
 // The reference's gradient through the unrolled epochs of FGWMixup's coupling solve for gfx950: the backward of conan_fgw_acc_pair_fwd
 // (fgw_acc.hip; the reference's fused_ACC_torch, barycenter.py:228-256, is plain differentiable torch) to M, A, Bm, a, b and the start X0, from the
 // cotangents of the returned plan and of the FGWMixup distance of that plan (ops.fgw_acc_pair_distance's formula).  B pairs per launch, one
-// workgroup of ACC_NW wavefronts per pair (conan_fgw_acc_pair_bwd; DESIGN.md 3.3, "FGWMixup: the unrolled gradient").
+// workgroup of UNROLL_NW wavefronts per pair (conan_fgw_acc_pair_bwd; DESIGN.md 3.3, "FGWMixup: the unrolled gradient").
 //
 // Two steps, for the epochs the forward ran (info[b,0], read here, clamped to [0, epoch]):
 //
@@ -21,16 +21,15 @@
 //
 // Six N^3 products per half-step against the forward's two, all on fp64 MFMA: A X, (A X) Bm, H and H X^T through mm_f64_glb, the two whose LEFT
 // operand is transposed (A^T H, (A X)^T dG) through the element-reader form mm_f64_pad.  dM, dA, dBm, da, db accumulate in fp64 over the whole
-// walk and are rounded to fp32 once.  Every sum has a fixed order, there are no atomics, nothing is shared between workgroups, every loop is
-// bounded by `epoch`.
+// walk and are rounded to fp32 once; every loop is bounded by `epoch`.  The conventions this kernel shares with its siblings (summation order,
+// nodes without mass, NaN, storage) are stated once, in fgw_unroll.h, with the pieces the kernels can share.
 //
 // Nodes without mass (a_i = 0 or b_j = 0: how rectangular and own-size pairs are embedded): their entries of every X_h are exactly zero and
 // constants of the solve, so Gb is held at zero there, their rows / columns of dM, dA, dBm and their da_i / db_j are written as exactly 0 (the
 // reference divides by the weight: the same documented deviation as the unrolled Sinkhorn gradient's).  A pair whose forward raised flags bit 2 (a
 // zero or non-finite line sum) gets NaN in every gradient, as the reference's autograd gives.
 //
-// Storage (fp64, pitch P = N | 1): five matrices X, AX, Gb, Z (then dG), E (then H), 40 bytes per entry: in LDS while they fit
-// (conan_fgw_acc_pair_bwd_lds_resident), else in the pair's slice of the workspace.  The three accumulators dM, dA, dBm are touched once per
+// Storage (fgw_unroll.h): the five matrices are X, AX, Gb, Z (then dG), E (then H).  The three accumulators dM, dA, dBm are touched once per
 // half-step and live in the workspace at every size (in LDS they would lower the residency bound from 61 to 49).  The launch bound of 4 waves
 // per SIMD holds the kernel at 128 VGPRs: two workgroups per CU.  The replay needs X, AX and alpha' M: it borrows Gb for the last.  Workspace per pair: (2 epoch + 3) N^2 * 8 bytes, + 5 N P * 8 outside LDS, rounded up to 256.
 #include "fgw_acc_body.h"
@@ -38,71 +37,43 @@
 
 namespace {
 
-struct AccBwdCall {
-    const float *M, *A, *Bm, *a, *b, *X0;
-    const int *info;
-    const float *dX, *ddist;
-    float *dM, *dA, *dBm, *da, *db, *dX0, *Xchk;
+struct AccBwdCall : UnrollPairIO {    // B = Bm, chk = X_chk
     int N, P, epoch;
     double alpha, rho;              // (fp64 from the host: the scalar unit has no fp64 conversions)
     char *ws;
     size_t ws_stride;               // bytes per pair
 };
 
-// vectors: a, b, sc, q, da, db, c1's two halves [N] each, 16 doubles of reduction space, per-wavefront partial sums [NW][N]; rounded to 16 bytes
-__host__ __device__ inline size_t accb_vec_bytes(int N) { return ((size_t)((8 + ACC_NW) * (size_t)N + 16) * 8 + 15) / 16 * 16; }
-inline size_t accb_mat_bytes(int N) { return (size_t)N * fgw_pitch(N) * 40; }
-inline bool accb_resident(int N) { return accb_vec_bytes(N) + accb_mat_bytes(N) <= ACC_LDS_LIMIT; }
-inline bool accb_supported(int N) { return N > 0 && N <= 16384 && accb_vec_bytes(N) <= ACC_LDS_LIMIT; }      // (N P and N N stay far inside int)
-inline size_t accb_stride(int N, int epoch) {
-    const size_t NN = (size_t)N * N;
-    return al256(((size_t)2 * epoch + 3) * NN * 8 + (accb_resident(N) ? 0 : accb_mat_bytes(N)));
-}
+// vectors: a, b, sc, q, da, db, c1's two halves [N] each, and reduction space
+using AccStore = UnrollStore<8, true>;
+inline size_t accb_stride(int N, int epoch) { return AccStore::stride(N, ((size_t)2 * epoch + 3) * N * N * 8); }      // the record and the three accumulators
 
 template <bool LDS>
-__global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall c) {      // 4 waves per SIMD = two workgroups per CU: 128 VGPRs (131 without the bound)
+__global__ void __launch_bounds__(64 * UNROLL_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall c) {      // 4 waves per SIMD = two workgroups per CU: 128 VGPRs (131 without the bound)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = ACC_NW, NT = 64 * NW;
+    constexpr int NW = UNROLL_NW, NT = 64 * NW;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = c.N, P = c.P, NN = N * N;
     double *pa = reinterpret_cast<double *>(smem), *qb = pa + N, *sc = qb + N, *qv = sc + N, *dac = qv + N, *dbc = dac + N, *ca = dbc + N, *cb = ca + N;
     double *red = cb + N, *pm = red + 16;
     double *rec = reinterpret_cast<double *>(c.ws + (size_t)b * c.ws_stride);                  // X_0 .. X_(2 epoch - 1) [N,N] each
     double *dMa = rec + (size_t)2 * c.epoch * NN, *dAa = dMa + NN, *dBa = dAa + NN;
-    double *X = LDS ? reinterpret_cast<double *>(smem + accb_vec_bytes(N)) : dBa + NN;
+    double *X = LDS ? reinterpret_cast<double *>(smem + AccStore::vec_bytes(N)) : dBa + NN;
     double *AX = X + N * P, *Gb = AX + N * P, *Z = Gb + N * P, *E = Z + N * P;
-    const float *Mg = c.M + (size_t)b * NN, *Ag = c.A + (size_t)b * NN, *Bg = c.Bm + (size_t)b * NN;
+    const float *Mg = c.M + (size_t)b * NN, *Ag = c.A + (size_t)b * NN, *Bg = c.B + (size_t)b * NN;
     const float *Xs = c.X0 ? c.X0 + (size_t)b * NN : nullptr, *dXg = c.dX ? c.dX + (size_t)b * NN : nullptr;
     const double alpha = c.alpha, om = 1.0 - alpha, four_alpha = 4.0 * alpha, two_alpha = 2.0 * alpha, inv_rho = 1.0 / c.rho;
     const int epochs = __builtin_amdgcn_readfirstlane(min(max(c.info[b * 4 + 0], 0), c.epoch));      // a corrupt info can neither leave the record nor lengthen a loop
     const bool flagged = (__builtin_amdgcn_readfirstlane(c.info[b * 4 + 2]) & 4) != 0;
 
-    // out[l] = sum over the entries e of line l of f(offset of (l, e), e): rows (col = false) or columns.  Lane <-> line, the wavefronts split
-    // its entries, then the partial sums in wavefront order.  Workgroup-collective, ends on a barrier.
-    auto line_sums = [&](bool col, auto f, double *out) {
-        const int sl = col ? 1 : P, se = col ? P : 1;
-        for (int l = lane; l < N; l += 64) {
-            double s = 0.0;
-            for (int e = wave; e < N; e += NW) s += f(l * sl + e * se, e);
-            pm[wave * N + l] = s;
-        }
-        __syncthreads();
-        for (int l = tid; l < N; l += NT) {
-            double s = 0.0;
-#pragma unroll
-            for (int u = 0; u < NW; ++u) s += pm[u * N + l];
-            out[l] = s;
-        }
-        __syncthreads();
-    };
-
+    auto line_sums = [&](bool col, auto f, double *out) { unroll_line_sums(tid, lane, wave, N, P, pm, col, f, out); };
+    auto live = [&](int i, int j) { return unroll_live(pa, qb, i, j); };
     for (int i = tid; i < N; i += NT) {
         pa[i] = c.a ? (double)c.a[(size_t)b * N + i] : 1.0 / (double)N;
         qb[i] = c.b ? (double)c.b[(size_t)b * N + i] : 1.0 / (double)N;
         dac[i] = 0.0; dbc[i] = 0.0;
     }
     __syncthreads();
-    auto live = [&](int i, int j) { return pa[i] > 0.0 && qb[j] > 0.0; };
 
     // ---- step 1: the forward's epochs again (its start, its alpha' M, its loop), every half-step's input to the record ----------------------
     for (int t = tid; t < NN; t += NT) {
@@ -119,12 +90,12 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall 
             for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; r[t] = Xc[i * P + j]; }
         });
     }
-    if (c.Xchk)
-        for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; c.Xchk[(size_t)b * NN + t] = (float)X[i * P + j]; }
+    if (c.chk)
+        for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; c.chk[(size_t)b * NN + t] = (float)X[i * P + j]; }
     if (flagged) {                                                          // (workgroup-uniform) the reference's autograd gives NaN: so do we, everywhere
         const float nan = __builtin_nanf("");
         for (int t = tid; t < NN; t += NT) {
-            c.dM[(size_t)b * NN + t] = nan; c.dA[(size_t)b * NN + t] = nan; c.dBm[(size_t)b * NN + t] = nan;
+            c.dM[(size_t)b * NN + t] = nan; c.dA[(size_t)b * NN + t] = nan; c.dB[(size_t)b * NN + t] = nan;
             if (c.dX0) c.dX0[(size_t)b * NN + t] = nan;
         }
         for (int i = tid; i < N; i += NT) {
@@ -137,8 +108,8 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall 
     // ---- step 2a: the cotangent of the final X and the direct partials of the distance -------------------------------------------------------
     if (c.ddist) {                                                          // (workgroup-uniform)
         const double dd = (double)c.ddist[b];
-        line_sums(false, [&](int o, int) { return X[o]; }, sc);            // r = X 1
-        line_sums(true, [&](int o, int) { return X[o]; }, qv);             // c = X^T 1
+        line_sums(false, [&](int, int, int o) { return X[o]; }, sc);           // r = X 1
+        line_sums(true, [&](int, int, int o) { return X[o]; }, qv);            // c = X^T 1
         for (int i = tid; i < N; i += NT) {
             double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
             for (int k = 0; k < N; ++k) {
@@ -194,8 +165,8 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall 
             E[i * P + j] = e; Z[i * P + j] = e * x;
         });
         __syncthreads();
-        line_sums(col, [&](int o, int) { return Z[o]; }, sc);              // r
-        line_sums(col, [&](int o, int) { return Gb[o] * Z[o]; }, qv);      // sum of Gb o Z: s = (w / r) times it
+        line_sums(col, [&](int, int, int o) { return Z[o]; }, sc);              // r
+        line_sums(col, [&](int, int, int o) { return Gb[o] * Z[o]; }, qv);      // sum of Gb o Z: s = (w / r) times it
         for (int l = tid; l < N; l += NT) {
             const double wl = w[l];
             const double f = wl > 0.0 ? wl / sc[l] : 0.0, s = f * qv[l], q = wl > 0.0 ? s / wl : 0.0;
@@ -223,8 +194,7 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall 
 
     // ---- the start: its own gradient, or through a b^T to the weights ------------------------------------------------------------------------
     if (!Xs) {
-        line_sums(false, [&](int o, int e) { return Gb[o] * qb[e]; }, sc);
-        line_sums(true, [&](int o, int e) { return Gb[o] * pa[e]; }, qv);
+        unroll_start_sums(tid, lane, wave, N, P, pm, Gb, pa, qb, sc, qv);
         for (int i = tid; i < N; i += NT) { dac[i] += sc[i]; dbc[i] += qv[i]; }
         __syncthreads();
     }
@@ -232,7 +202,7 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall 
         const int i = t / N, j = t - i * N;
         c.dM[(size_t)b * NN + t] = live(i, j) ? (float)dMa[t] : 0.f;
         c.dA[(size_t)b * NN + t] = (pa[i] > 0.0 && pa[j] > 0.0) ? (float)dAa[t] : 0.f;
-        c.dBm[(size_t)b * NN + t] = (qb[i] > 0.0 && qb[j] > 0.0) ? (float)dBa[t] : 0.f;
+        c.dB[(size_t)b * NN + t] = (qb[i] > 0.0 && qb[j] > 0.0) ? (float)dBa[t] : 0.f;
         if (c.dX0) c.dX0[(size_t)b * NN + t] = live(i, j) ? (float)Gb[i * P + j] : 0.f;
     }
     for (int i = tid; i < N; i += NT) {
@@ -245,30 +215,24 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_acc_pair_bwd(AccBwdCall 
 
 extern "C" {
 
-int conan_fgw_acc_pair_bwd_lds_resident(int N) { return N > 0 && accb_resident(N) ? 1 : 0; }
+int conan_fgw_acc_pair_bwd_lds_resident(int N) { return N > 0 && AccStore::resident(N) ? 1 : 0; }
 
 long long conan_fgw_acc_pair_bwd_workspace_bytes(int B, int N, int epoch) {
-    if (B <= 0 || epoch <= 0 || !accb_supported(N)) return 0;
+    if (B <= 0 || epoch <= 0 || !AccStore::supported(N)) return 0;
     return (long long)((size_t)B * accb_stride(N, epoch));
 }
 
 int conan_fgw_acc_pair_bwd(const float *M, const float *A, const float *Bm, const float *a, const float *b, const float *X0, int B, int N, double alpha,
                            double rho, int epoch, const int *info, const float *dX, const float *ddist, float *dM, float *dA, float *dBm, float *da,
                            float *db, float *dX0, float *X_chk, void *workspace, void *stream) {
-    if (!M || !A || !Bm || !info || !dM || !dA || !dBm || !workspace || B <= 0 || N <= 0 || epoch <= 0) return CONAN_E_BADARG;
-    if (!dX && !ddist) return CONAN_E_BADARG;
-    if ((da && !a) || (db && !b) || (dX0 && !X0)) return CONAN_E_BADARG;
-    if (!(rho > 0.0 && rho <= 1.79769313486231570815e308) || !(alpha == alpha)) return CONAN_E_BADARG;
-    if (!accb_supported(N)) return CONAN_E_UNSUPPORTED;
-    const bool lds = accb_resident(N);
     AccBwdCall c{};
-    c.M = M; c.A = A; c.Bm = Bm; c.a = a; c.b = b; c.X0 = X0; c.info = info; c.dX = dX; c.ddist = ddist;
-    c.dM = dM; c.dA = dA; c.dBm = dBm; c.da = da; c.db = db; c.dX0 = dX0; c.Xchk = X_chk;
+    static_cast<UnrollPairIO &>(c) = {M, A, Bm, a, b, X0, info, dX, ddist, dM, dA, dBm, da, db, dX0, X_chk};
+    if (epoch <= 0 || unroll_pair_args(c, B, N, workspace, rho, alpha) != CONAN_OK) return CONAN_E_BADARG;
+    if (!AccStore::supported(N)) return CONAN_E_UNSUPPORTED;
     c.N = N; c.P = pitch_of(N); c.epoch = epoch; c.alpha = alpha; c.rho = rho;
     c.ws = static_cast<char *>(workspace); c.ws_stride = accb_stride(N, epoch);
-    const size_t bytes = accb_vec_bytes(N) + (lds ? accb_mat_bytes(N) : 0);
-    if (lds) launch_lds(k_fgw_acc_pair_bwd<true>, B, 64 * ACC_NW, bytes, as_stream(stream), c);
-    else launch_lds(k_fgw_acc_pair_bwd<false>, B, 64 * ACC_NW, bytes, as_stream(stream), c);
+    if (AccStore::resident(N)) launch_lds(k_fgw_acc_pair_bwd<true>, B, 64 * UNROLL_NW, AccStore::lds_bytes(N), as_stream(stream), c);
+    else launch_lds(k_fgw_acc_pair_bwd<false>, B, 64 * UNROLL_NW, AccStore::lds_bytes(N), as_stream(stream), c);
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;
 }

@@ -1,6 +1,6 @@
 // The reference's gradient through the unrolled Bregman half-steps of the pairwise BAPG FGW solve for gfx950: the backward of conan_fgw_pair_fwd
 // (fgw_pair.hip) with solver BAPG (the reference's fgw_bregman, bregman.py:170-279: plain differentiable torch), square or kl loss, to M, C1, C2,
-// p, q and the start G0, from the cotangents of the returned plan and of fgw_dist.  B pairs per launch, one workgroup of BG_NW wavefronts per
+// p, q and the start G0, from the cotangents of the returned plan and of fgw_dist.  B pairs per launch, one workgroup of UNROLL_NW wavefronts per
 // pair (conan_fgw_bregman_bwd; DESIGN.md 3.3, "Pairwise FGW, BAPG: the unrolled gradient").
 //
 // With h = 2 C2 (square) or log(C2 + 1e-15) (kl), alpha' = 1 - alpha, a half-step with input plan T is
@@ -30,32 +30,22 @@
 // forward's 2; not symmetric 4 in the replay and 4 + 9 in the walk.  Under kl h is formed once, in fp64, in the workspace (the forward takes the
 // logarithm at every operand read).
 //
-// Conventions of the sibling kernels (fgw_pair_grad.hip, fgw_acc_grad.hip): fp32 in and out, fp64 in between; dM, dC1, dC2, dp, dq accumulate
-// in fp64 over the whole walk and are rounded once; every sum has a fixed order (lane <-> line, the wavefronts split its entries, partial sums
-// in wavefront order), no atomics, nothing shared between workgroups; every loop is bounded by max_iter: a corrupt info can neither leave the
-// record nor lengthen a loop.
+// The conventions this kernel shares with its siblings (precisions, summation order, loop bounds, nodes without mass, NaN, storage) are
+// stated once, in fgw_unroll.h, with the pieces the kernels can share.
 //
 // Nodes without mass (p_i = 0 or q_j = 0: how rectangular and own-size pairs are embedded): their entries of every T_k are exactly zero and
 // their scaling factor is 0, so Gb and D are zero there, their rows / columns of dM, dC1, dC2, dG0 and their dp_i / dq_j are written as exactly
 // 0.  A pair whose forward raised flags bit 2, or whose replay meets a zero (or NaN) sum on a node with mass or a non-finite plan entry, gets
 // NaN in every gradient and binfo flag bit 2.
 //
-// Storage (fp64, pitch P = N | 1): five matrices T_k, X, Gb, D and a product buffer, 40 bytes per entry: in LDS while they fit beside the vectors
-// (conan_fgw_bregman_bwd_lds_resident: N <= 61), else in the pair's slice of the workspace; the same code, so the same arithmetic, on both
-// paths.  The record, the three accumulators and h live in the workspace at every size.
-#include "fgw_common.h"
+// Storage (fgw_unroll.h): the five matrices are T_k, X, Gb, D and a product buffer (conan_fgw_bregman_bwd_lds_resident: N <= 61).  The record,
+// the three accumulators and h live in the workspace at every size.
+#include "fgw_unroll.h"
 #include "../../include/conan_fgw_hip_bregman_grad.h"
 
 namespace {
 
-constexpr int BG_NW = 8;
-constexpr size_t BG_LDS_LIMIT = 160 * 1024;
-
-struct BregmanBwdCall {
-    const float *M, *C1, *C2, *p, *q, *G0;
-    const int *info;
-    const float *dT, *ddist;
-    float *dM, *dC1, *dC2, *dp, *dq, *dG0, *Tchk;
+struct BregmanBwdCall : UnrollPairIO {      // A = C1, B = C2, a = p, b = q, X0 = G0, dX = dT, chk = T_chk
     int *binfo;
     int N, P, max_iter, symmetric;
     double alpha, eps;                // (fp64 from the host: the scalar unit has no fp64 conversions)
@@ -63,15 +53,9 @@ struct BregmanBwdCall {
     size_t ws_stride;                 // bytes per pair
 };
 
-// vectors: p, q, the sums s, the scalings, g, dp, dq, c0, r0, two work lines (T 1 and T^T 1, the sums of the start) [N] each, per-wavefront partial sums [NW][N]; rounded to 16 bytes
-__host__ __device__ inline size_t bgb_vec_bytes(int N) { return ((size_t)(11 + BG_NW) * (size_t)N * 8 + 15) / 16 * 16; }
-inline size_t bgb_mat_bytes(int N) { return (size_t)N * fgw_pitch(N) * 40; }
-inline bool bgb_resident(int N) { return bgb_vec_bytes(N) + bgb_mat_bytes(N) <= BG_LDS_LIMIT; }
-inline bool bgb_supported(int N) { return N > 0 && N <= 16384 && bgb_vec_bytes(N) <= BG_LDS_LIMIT; }      // (N P and N N stay far inside int)
-inline size_t bgb_stride(int N, int max_iter) {
-    const size_t NN = (size_t)N * N;
-    return al256(((size_t)2 * max_iter + 4) * NN * 8 + (bgb_resident(N) ? 0 : bgb_mat_bytes(N)));
-}
+// vectors: p, q, the sums s, the scalings, g, dp, dq, c0, r0, two work lines (T 1 and T^T 1, the sums of the start) [N] each; no reduction space
+using BregmanStore = UnrollStore<11, false>;
+inline size_t bgb_stride(int N, int max_iter) { return BregmanStore::stride(N, ((size_t)2 * max_iter + 4) * N * N * 8); }      // the record, the three accumulators and h
 
 // Registers (-Rpass-analysis=kernel-resource-usage): the second __launch_bounds__ argument, 4 = held at 128 VGPRs so that two
 // workgroups share a CU, 2 = unbounded.  Unbounded the compiler takes 127 (LDS, square, symmetric), 129 - 138 (the other LDS-resident
@@ -86,9 +70,9 @@ inline size_t bgb_stride(int N, int max_iter) {
 #endif
 constexpr int bgb_min_blocks(bool lds, bool kl, bool asym) { return ((lds && (kl || asym)) != (CONAN_BREGMAN_BWD_AB != 0)) ? 4 : 2; }
 template <bool LDS, bool KL, bool ASYM>
-__global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_fgw_bregman_bwd(BregmanBwdCall c) {
+__global__ void __launch_bounds__(64 * UNROLL_NW, bgb_min_blocks(LDS, KL, ASYM)) k_fgw_bregman_bwd(BregmanBwdCall c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = BG_NW, NT = 64 * NW;
+    constexpr int NW = UNROLL_NW, NT = 64 * NW;
     using h_t = std::conditional_t<KL, double, float>;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = c.N, P = c.P, NN = N * N;
@@ -97,10 +81,10 @@ __global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_f
     double *pm = wc + N;
     double *rec = reinterpret_cast<double *>(c.ws + (size_t)b * c.ws_stride);                  // the input plan of half-step 0 .. 2 max_iter - 1, [N,N] each
     double *dMa = rec + (size_t)2 * c.max_iter * NN, *dC1a = dMa + NN, *dC2a = dC1a + NN, *hm = dC2a + NN;
-    double *Tk = LDS ? reinterpret_cast<double *>(smem + bgb_vec_bytes(N)) : hm + NN;
+    double *Tk = LDS ? reinterpret_cast<double *>(smem + BregmanStore::vec_bytes(N)) : hm + NN;
     double *Xb = Tk + N * P, *Gb = Xb + N * P, *D = Gb + N * P, *A = D + N * P;
-    const float *Mg = c.M + (size_t)b * NN, *C1g = c.C1 + (size_t)b * NN, *C2g = c.C2 + (size_t)b * NN;
-    const float *G0g = c.G0 ? c.G0 + (size_t)b * NN : nullptr, *dTg = c.dT ? c.dT + (size_t)b * NN : nullptr;
+    const float *Mg = c.M + (size_t)b * NN, *C1g = c.A + (size_t)b * NN, *C2g = c.B + (size_t)b * NN;
+    const float *G0g = c.X0 ? c.X0 + (size_t)b * NN : nullptr, *dTg = c.dX ? c.dX + (size_t)b * NN : nullptr;
     const double alpha = c.alpha, om = 1.0 - alpha, eps = c.eps;
     constexpr double hs = KL ? 1.0 : 2.0;                                                       // h = hs * (the matrix the products read)
     const double ah = alpha * hs;
@@ -111,24 +95,8 @@ __global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_f
     const h_t *hg;                                                                              // kl: log(C2 + 1e-15) in fp64; square: C2 itself
     if constexpr (KL) hg = hm; else hg = C2g;
 
-    // out[l] = sum over the entries e of line l of f(l, e, offset of the entry): rows (col = false) or columns.  Lane <-> line, the wavefronts
-    // split its entries, then the partial sums in wavefront order.  Workgroup-collective, ends on a barrier.
-    auto line_sums = [&](bool col, auto f, double *out) {
-        const int sl = col ? 1 : P, se = col ? P : 1;
-        for (int l = lane; l < N; l += 64) {
-            double s = 0.0;
-            for (int e = wave; e < N; e += NW) s += f(l, e, l * sl + e * se);
-            pm[wave * N + l] = s;
-        }
-        __syncthreads();
-        for (int l = tid; l < N; l += NT) {
-            double s = 0.0;
-#pragma unroll
-            for (int u = 0; u < NW; ++u) s += pm[u * N + l];
-            out[l] = s;
-        }
-        __syncthreads();
-    };
+    auto line_sums = [&](bool col, auto f, double *out) { unroll_line_sums(tid, lane, wave, N, P, pm, col, f, out); };
+    auto live = [&](int i, int j) { return unroll_live(pa, qb, i, j); };
     // X h (WT = false) or X h^T (WT = true) without the factor hs; X [N,N] at pitch P
     auto mm_h = [&](auto wt, const double *X, auto st) { mm_f64_glb<NW, decltype(wt)::value>(N, N, N, X, P, hg, N, st); };
     auto f1 = [&](double a) { return KL ? a * log(a + 1e-15) - a : a * a; };
@@ -138,14 +106,13 @@ __global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_f
     auto hd = [&](double e) { return KL ? 1.0 / (e + 1e-15) : 2.0; };
 
     for (int i = tid; i < N; i += NT) {
-        pa[i] = c.p ? (double)c.p[(size_t)b * N + i] : 1.0 / (double)N;
-        qb[i] = c.q ? (double)c.q[(size_t)b * N + i] : 1.0 / (double)N;
+        pa[i] = c.a ? (double)c.a[(size_t)b * N + i] : 1.0 / (double)N;
+        qb[i] = c.b ? (double)c.b[(size_t)b * N + i] : 1.0 / (double)N;
         dpa[i] = 0.0; dqa[i] = 0.0;
     }
     if constexpr (KL)
         for (int t = tid; t < NN; t += NT) hm[t] = log((double)C2g[t] + 1e-15);
     __syncthreads();
-    auto live = [&](int i, int j) { return pa[i] > 0.0 && qb[j] > 0.0; };
     for (int i = tid; i < N; i += NT) {                                     // the untransposed init_matrix (fgw_dist's, in every case)
         double s1 = 0.0, s2 = 0.0;
         for (int k = 0; k < N; ++k) { s1 += f1((double)C1g[i * N + k]) * pa[k]; s2 += f2((double)C2g[i * N + k]) * qb[k]; }
@@ -204,8 +171,8 @@ __global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_f
         }
         __syncthreads();
     }
-    if (c.Tchk)
-        for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; c.Tchk[(size_t)b * NN + t] = (float)Tk[i * P + j]; }
+    if (c.chk)
+        for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; c.chk[(size_t)b * NN + t] = (float)Tk[i * P + j]; }
     const bool flagged = __syncthreads_or(bad) != 0 || (fwd_flags & 4) != 0;                                            // (workgroup-uniform)
     if (c.binfo && tid == 0) {
         c.binfo[b * 2 + 0] = iters;
@@ -214,12 +181,12 @@ __global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_f
     if (flagged) {                                                          // the reference's autograd gives NaN: so do we, everywhere
         const float nan = __builtin_nanf("");
         for (int t = tid; t < NN; t += NT) {
-            c.dM[(size_t)b * NN + t] = nan; c.dC1[(size_t)b * NN + t] = nan; c.dC2[(size_t)b * NN + t] = nan;
-            if (c.dG0) c.dG0[(size_t)b * NN + t] = nan;
+            c.dM[(size_t)b * NN + t] = nan; c.dA[(size_t)b * NN + t] = nan; c.dB[(size_t)b * NN + t] = nan;
+            if (c.dX0) c.dX0[(size_t)b * NN + t] = nan;
         }
         for (int i = tid; i < N; i += NT) {
-            if (c.dp) c.dp[(size_t)b * N + i] = nan;
-            if (c.dq) c.dq[(size_t)b * N + i] = nan;
+            if (c.da) c.da[(size_t)b * N + i] = nan;
+            if (c.db) c.db[(size_t)b * N + i] = nan;
         }
         return;
     }
@@ -329,21 +296,20 @@ __global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_f
 
     // ---- the start: its own gradient, or through p q^T to the weights -----------------------------------------------------------------------------
     if (!G0g) {
-        line_sums(false, [&](int, int e, int o) { return Gb[o] * qb[e]; }, zc);
-        line_sums(true, [&](int, int e, int o) { return Gb[o] * pa[e]; }, wc);
+        unroll_start_sums(tid, lane, wave, N, P, pm, Gb, pa, qb, zc, wc);
         for (int i = tid; i < N; i += NT) { dpa[i] += zc[i]; dqa[i] += wc[i]; }
         __syncthreads();
     }
     for (int t = tid; t < NN; t += NT) {
         const int i = t / N, j = t - i * N;
         c.dM[(size_t)b * NN + t] = live(i, j) ? (float)dMa[t] : 0.f;
-        c.dC1[(size_t)b * NN + t] = (pa[i] > 0.0 && pa[j] > 0.0) ? (float)dC1a[t] : 0.f;
-        c.dC2[(size_t)b * NN + t] = (qb[i] > 0.0 && qb[j] > 0.0) ? (float)dC2a[t] : 0.f;
-        if (c.dG0) c.dG0[(size_t)b * NN + t] = live(i, j) ? (float)Gb[i * P + j] : 0.f;
+        c.dA[(size_t)b * NN + t] = (pa[i] > 0.0 && pa[j] > 0.0) ? (float)dC1a[t] : 0.f;
+        c.dB[(size_t)b * NN + t] = (qb[i] > 0.0 && qb[j] > 0.0) ? (float)dC2a[t] : 0.f;
+        if (c.dX0) c.dX0[(size_t)b * NN + t] = live(i, j) ? (float)Gb[i * P + j] : 0.f;
     }
     for (int i = tid; i < N; i += NT) {
-        if (c.dp) c.dp[(size_t)b * N + i] = pa[i] > 0.0 ? (float)dpa[i] : 0.f;
-        if (c.dq) c.dq[(size_t)b * N + i] = qb[i] > 0.0 ? (float)dqa[i] : 0.f;
+        if (c.da) c.da[(size_t)b * N + i] = pa[i] > 0.0 ? (float)dpa[i] : 0.f;
+        if (c.db) c.db[(size_t)b * N + i] = qb[i] > 0.0 ? (float)dqa[i] : 0.f;
     }
 }
 
@@ -351,33 +317,28 @@ __global__ void __launch_bounds__(64 * BG_NW, bgb_min_blocks(LDS, KL, ASYM)) k_f
 
 extern "C" {
 
-int conan_fgw_bregman_bwd_lds_resident(int N) { return N > 0 && bgb_resident(N) ? 1 : 0; }
+int conan_fgw_bregman_bwd_lds_resident(int N) { return N > 0 && BregmanStore::resident(N) ? 1 : 0; }
 
 long long conan_fgw_bregman_bwd_workspace_bytes(int B, int N, int max_iter) {
-    if (B <= 0 || max_iter <= 0 || !bgb_supported(N)) return 0;
+    if (B <= 0 || max_iter <= 0 || !BregmanStore::supported(N)) return 0;
     return (long long)((size_t)B * bgb_stride(N, max_iter));
 }
 
 int conan_fgw_bregman_bwd(const float *M, const float *C1, const float *C2, const float *p, const float *q, const float *G0, int B, int N, double alpha,
                           double epsilon, int max_iter, int loss_fun, int symmetric, const int *info, const float *dT, const float *ddist, float *dM,
                           float *dC1, float *dC2, float *dp, float *dq, float *dG0, float *T_chk, int *binfo, void *workspace, void *stream) {
-    if (!M || !C1 || !C2 || !info || !dM || !dC1 || !dC2 || !workspace || B <= 0 || N <= 0 || max_iter <= 0) return CONAN_E_BADARG;
-    if (!dT && !ddist) return CONAN_E_BADARG;
-    if ((dp && !p) || (dq && !q) || (dG0 && !G0)) return CONAN_E_BADARG;
-    if (!(epsilon > 0.0 && epsilon <= 1.79769313486231570815e308) || !(alpha == alpha)) return CONAN_E_BADARG;
-    if (loss_fun < 0 || loss_fun > 1 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
-    if (!bgb_supported(N)) return CONAN_E_UNSUPPORTED;
-    const bool lds = bgb_resident(N);
     BregmanBwdCall c{};
-    c.M = M; c.C1 = C1; c.C2 = C2; c.p = p; c.q = q; c.G0 = G0; c.info = info; c.dT = dT; c.ddist = ddist;
-    c.dM = dM; c.dC1 = dC1; c.dC2 = dC2; c.dp = dp; c.dq = dq; c.dG0 = dG0; c.Tchk = T_chk; c.binfo = binfo;
+    static_cast<UnrollPairIO &>(c) = {M, C1, C2, p, q, G0, info, dT, ddist, dM, dC1, dC2, dp, dq, dG0, T_chk};
+    if (max_iter <= 0 || unroll_pair_args(c, B, N, workspace, epsilon, alpha) != CONAN_OK) return CONAN_E_BADARG;
+    if (loss_fun < 0 || loss_fun > 1 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
+    if (!BregmanStore::supported(N)) return CONAN_E_UNSUPPORTED;
+    c.binfo = binfo;
     c.N = N; c.P = pitch_of(N); c.max_iter = max_iter; c.symmetric = symmetric;
     c.alpha = alpha; c.eps = epsilon;
     c.ws = static_cast<char *>(workspace); c.ws_stride = bgb_stride(N, max_iter);
-    const size_t bytes = bgb_vec_bytes(N) + (lds ? bgb_mat_bytes(N) : 0);
     with_flags([&](auto L, auto K, auto A) {
-        launch_lds(k_fgw_bregman_bwd<decltype(L)::value, decltype(K)::value, decltype(A)::value>, B, 64 * BG_NW, bytes, as_stream(stream), c);
-    }, lds, loss_fun == 1, symmetric != 1);
+        launch_lds(k_fgw_bregman_bwd<decltype(L)::value, decltype(K)::value, decltype(A)::value>, B, 64 * UNROLL_NW, BregmanStore::lds_bytes(N), as_stream(stream), c);
+    }, BregmanStore::resident(N), loss_fun == 1, symmetric != 1);
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;
 }

@@ -6,7 +6,7 @@
 // The forward's state (C_t, Y_t), t = 0 .. n (n = info[b,0], read here, clamped to [0, max_iter]), comes from the record that
 // conan_fgw_mixup_barycenter_fwd_record keeps in fp64.  From (Yb_n, Cb_n) = the caller's cotangents, for t = n - 1 .. 0, TWO launches:
 //
-// k_fgw_mixup_bwd_coupling, one workgroup of ACC_NW wavefronts per coupling (b, s); a molecule with n <= t leaves at once:
+// k_fgw_mixup_bwd_coupling, one workgroup of UNROLL_NW wavefronts per coupling (b, s); a molecule with n <= t leaves at once:
 //   (1) Replay.  M_s from Y_t as k_fgw_acc_coupling forms it, then acc_epochs (fgw_acc_body.h, the forward's own text, AccProblem<double>, WITH
 //       its objective checks: the forward kept only the sum of the epoch counts, so the replay stops where the forward's rule stops) from
 //       p ps_s^T, recording the fp64 input of every half-step.  Its final X_s is the forward's plan of that iteration bit for bit (T_chk for
@@ -28,24 +28,21 @@
 // dlam_s are fp64 accumulators owned by the coupling's workgroup across all outer iterations; every loop is bounded by epoch / max_iter.
 //
 // The reverse walk is a SECOND COPY of fgw_acc_grad.hip's, with A read from the fp64 state and (1 - alpha) M from the workspace: moved into a
-// shared header (two factorings tried) k_fgw_acc_pair_bwd no longer compiled to the parent's instructions, so that file stays as it is.
+// shared header (three factorings tried, fgw_unroll.h) k_fgw_acc_pair_bwd no longer compiled to the parent's instructions or registers.
 //
 // Nodes without mass (p_i = 0, ps_sj = 0: how other sizes are embedded) get exactly 0 everywhere.  A molecule whose forward raised flags bit 2
 // gets NaN in all its gradients and, through the sum over molecules, in dlambdas.
 //
-// Storage (fp64, pitch P = N | 1), as the pair backward: five matrices X, AX, Gb, Z, E in LDS while they fit
-// (conan_fgw_mixup_barycenter_bwd_lds_resident, N <= 61), else in the coupling's slice of the workspace; the record, the accumulators and
-// the shares in the workspace at every size.  The half-step record is reused by every outer iteration.
+// Storage and the conventions shared with the sibling kernels: fgw_unroll.h.  The five matrices are X, AX, Gb, Z, E
+// (conan_fgw_mixup_barycenter_bwd_lds_resident, N <= 61); the record, the accumulators and the shares live in the workspace at every size.
+// The half-step record is reused by every outer iteration.
 #include "fgw_acc_body.h"
 #include "../../include/conan_fgw_hip_mixup_grad.h"
 
 namespace {
 
-// vectors: a, b, sc, q, da, db, |y_i|^2, |z_j|^2 [N] each, 16 doubles of reduction space, per-wavefront partial sums [NW][N]; rounded to 16 bytes
-__host__ __device__ inline size_t mixb_vec_bytes(int N) { return ((size_t)((8 + ACC_NW) * (size_t)N + 16) * 8 + 15) / 16 * 16; }
-inline size_t mixb_mat_bytes(int N) { return (size_t)N * fgw_pitch(N) * 40; }
-inline bool mixb_resident(int N) { return mixb_vec_bytes(N) + mixb_mat_bytes(N) <= ACC_LDS_LIMIT; }
-inline bool mixb_supported(int N) { return N > 0 && N <= 16384 && mixb_vec_bytes(N) <= ACC_LDS_LIMIT; }
+// vectors: a, b, sc, q, da, db, |y_i|^2, |z_j|^2 [N] each, and reduction space
+using MixStore = UnrollStore<8, true>;
 
 // Byte offsets of the workspace's regions, in this order, and the total the size query returns.
 struct MixWs {
@@ -56,7 +53,7 @@ struct MixWs {
 };
 MixWs mix_workspace(int B, int K, int N, int d, int epoch) {
     MixWs w{};
-    if (B <= 0 || K <= 0 || d <= 0 || epoch <= 0 || !mixb_supported(N)) return w;
+    if (B <= 0 || K <= 0 || d <= 0 || epoch <= 0 || !MixStore::supported(N)) return w;
     const size_t NN = (size_t)N * N, Nd = (size_t)N * d, BK = (size_t)B * K;
     size_t end = 0;
     auto region = [&](size_t doubles) { const size_t at = end; end += al256(doubles * 8); return at; };
@@ -65,7 +62,7 @@ MixWs mix_workspace(int B, int K, int N, int d, int epoch) {
     w.dCsacc = region(BK * NN); w.dYsacc = region(BK * Nd); w.dpsacc = region(BK * N); w.dlamacc = region(BK);
     w.dM = region(BK * NN); w.Mraw = region(BK * NN);
     w.rec = region(BK * 2 * (size_t)epoch * NN);
-    w.mats = region(mixb_resident(N) ? 0 : BK * 5 * (size_t)N * pitch_of(N));
+    w.mats = region(MixStore::resident(N) ? 0 : BK * 5 * (size_t)N * pitch_of(N));
     w.total = end;
     return w;
 }
@@ -99,9 +96,9 @@ __device__ __forceinline__ double mix_ybar(const MixBwdCall &c, bool first, int 
 }
 
 template <bool LDS>
-__global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_mixup_bwd_coupling(MixBwdCall c, int t_out) {
+__global__ void __launch_bounds__(64 * UNROLL_NW, 4) k_fgw_mixup_bwd_coupling(MixBwdCall c, int t_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = ACC_NW, NT = 64 * NW;
+    constexpr int NW = UNROLL_NW, NT = 64 * NW;
     const int cid = blockIdx.x, b = cid / c.K, s = cid - b * c.K;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = c.N, P = c.P, d = c.d, NN = N * N, Nd = N * d, B = c.B, K = c.K;
@@ -118,7 +115,7 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_mixup_bwd_coupling(MixBw
     double *dAa = mix_at(c, c.w.Apart) + (size_t)cid * NN, *dBa = mix_at(c, c.w.dCsacc) + (size_t)cid * NN;
     double *Yp = mix_at(c, c.w.Ypart) + (size_t)cid * Nd, *dYa = mix_at(c, c.w.dYsacc) + (size_t)cid * Nd;
     double *dpp = mix_at(c, c.w.dppart) + (size_t)cid * N, *dpsa = mix_at(c, c.w.dpsacc) + (size_t)cid * N, *dla = mix_at(c, c.w.dlamacc) + cid;
-    double *X = LDS ? reinterpret_cast<double *>(smem + mixb_vec_bytes(N)) : mix_at(c, c.w.mats) + (size_t)cid * 5 * N * P;
+    double *X = LDS ? reinterpret_cast<double *>(smem + MixStore::vec_bytes(N)) : mix_at(c, c.w.mats) + (size_t)cid * 5 * N * P;
     double *AX = X + N * P, *Gb = AX + N * P, *Z = Gb + N * P, *E = Z + N * P;
     const float *Zg = c.Ys + (size_t)cid * Nd, *Bg = c.Cs + (size_t)cid * NN;
     const double *C0 = c.Crec + ((size_t)t_out * B + b) * NN, *C1 = c.Crec + ((size_t)(t_out + 1) * B + b) * NN;
@@ -127,24 +124,7 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_mixup_bwd_coupling(MixBw
     const double lam = c.lambdas ? (double)c.lambdas[s] : 1.0 / (double)K;
     const int y_zero = (t_out == 0 && !c.has_init_Y) ? 1 : 0;
 
-    // out[l] = sum over the entries e of line l of f(offset of (l, e), e): rows (col = false) or columns.  Lane <-> line, the wavefronts split
-    // its entries, then the partial sums in wavefront order.  Workgroup-collective, ends on a barrier.
-    auto line_sums = [&](bool col, auto f, double *out) {
-        const int sl = col ? 1 : P, se = col ? P : 1;
-        for (int l = lane; l < N; l += 64) {
-            double sum = 0.0;
-            for (int e = wave; e < N; e += NW) sum += f(l * sl + e * se, e);
-            pm[wave * N + l] = sum;
-        }
-        __syncthreads();
-        for (int l = tid; l < N; l += NT) {
-            double sum = 0.0;
-#pragma unroll
-            for (int u = 0; u < NW; ++u) sum += pm[u * N + l];
-            out[l] = sum;
-        }
-        __syncthreads();
-    };
+    auto line_sums = [&](bool col, auto f, double *out) { unroll_line_sums(tid, lane, wave, N, P, pm, col, f, out); };
 
     // ---- step 1: the forward's coupling solve of this outer iteration again (k_fgw_acc_coupling's text up to acc_epochs), recorded -----------
     for (int i = tid; i < N; i += NT) {
@@ -168,7 +148,7 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_mixup_bwd_coupling(MixBw
         }
     }
     __syncthreads();
-    auto live = [&](int i, int j) { return pa[i] > 0.0 && qb[j] > 0.0; };
+    auto live = [&](int i, int j) { return unroll_live(pa, qb, i, j); };
     double *Mb = Gb;                                                        // (1 - alpha) M: the replay borrows Gb for it
     for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; X[i * P + j] = pa[i] * qb[j]; }
     if (!y_zero) mm_f64_glb<NW, true>(N, N, d, Y0, d, Zg, d, [&](int i, int j, double v) { Mb[i * P + j] = v; });
@@ -255,8 +235,8 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_mixup_bwd_coupling(MixBw
             E[i * P + j] = e; Z[i * P + j] = e * x;
         });
         __syncthreads();
-        line_sums(col, [&](int o, int) { return Z[o]; }, sc);              // r
-        line_sums(col, [&](int o, int) { return Gb[o] * Z[o]; }, qv);      // sum of Gb o Z: s = (w / r) times it
+        line_sums(col, [&](int, int, int o) { return Z[o]; }, sc);              // r
+        line_sums(col, [&](int, int, int o) { return Gb[o] * Z[o]; }, qv);      // sum of Gb o Z: s = (w / r) times it
         for (int l = tid; l < N; l += NT) {
             const double wl = w[l];
             const double f = wl > 0.0 ? wl / sc[l] : 0.0, sv = f * qv[l], q = wl > 0.0 ? sv / wl : 0.0;
@@ -282,8 +262,7 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_mixup_bwd_coupling(MixBw
         __syncthreads();
     }
     // the start p ps_s^T passes its gradient to the weights
-    line_sums(false, [&](int o, int e) { return Gb[o] * qb[e]; }, sc);
-    line_sums(true, [&](int o, int e) { return Gb[o] * pa[e]; }, qv);
+    unroll_start_sums(tid, lane, wave, N, P, pm, Gb, pa, qb, sc, qv);
     for (int i = tid; i < N; i += NT) {
         dpp[i] = pa[i] > 0.0 ? dac[i] + sc[i] : 0.0;
         dpsa[i] += qb[i] > 0.0 ? dbc[i] + qv[i] : 0.0;
@@ -292,8 +271,8 @@ __global__ void __launch_bounds__(64 * ACC_NW, 4) k_fgw_mixup_bwd_coupling(MixBw
     // ---- step 4: the feature cost, through the clamp -------------------------------------------------------------------------------------------
     for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; Z[i * P + j] = Mraw[t] >= 0.0 ? dMa[t] : 0.0; }
     __syncthreads();
-    line_sums(false, [&](int o, int) { return Z[o]; }, sc);
-    line_sums(true, [&](int o, int) { return Z[o]; }, qv);
+    line_sums(false, [&](int, int, int o) { return Z[o]; }, sc);
+    line_sums(true, [&](int, int, int o) { return Z[o]; }, qv);
     mm_f64_glb<NW, false>(N, d, N, Z, P, Zg, d, [&](int i, int k, double v) { Yp[i * d + k] = 2.0 * (sc[i] * Y0[i * d + k] - v); });
     mm_f64_pad<NW>(N, d, N, [&](int j, int k) { return Z[k * P + j]; }, [&](int k, int e) { return Y0[k * d + e]; },
                    [&](int j, int e, double v) { dYa[j * d + e] += 2.0 * (qv[j] * (double)Zg[j * d + e] - v); });
@@ -387,7 +366,7 @@ __global__ void __launch_bounds__(256) k_fgw_mixup_bwd_final(MixBwdCall c) {
 
 extern "C" {
 
-int conan_fgw_mixup_barycenter_bwd_lds_resident(int N) { return N > 0 && mixb_resident(N) ? 1 : 0; }
+int conan_fgw_mixup_barycenter_bwd_lds_resident(int N) { return N > 0 && MixStore::resident(N) ? 1 : 0; }
 
 long long conan_fgw_mixup_barycenter_bwd_workspace_bytes(int B, int K, int N, int d, int epoch) {
     return (long long)mix_workspace(B, K, N, d, epoch).total;
@@ -403,8 +382,8 @@ int conan_fgw_mixup_barycenter_bwd(const float *Ys, const float *Cs, const float
     if (params->max_iter <= 0 || epoch <= 0 || !(rho > 0.0 && rho <= 1.79769313486231570815e308) || !(eps == eps)) return CONAN_E_BADARG;
     if (params->fixed_features && !init_Y) return CONAN_E_BADARG;
     if (params->loss_fun != 0 && params->loss_fun != 1) return CONAN_E_BADARG;
-    if (!mixb_supported(N)) return CONAN_E_UNSUPPORTED;
-    const bool lds = mixb_resident(N);
+    if (!MixStore::supported(N)) return CONAN_E_UNSUPPORTED;
+    const bool lds = MixStore::resident(N);
     const int max_iter = params->max_iter;
     MixBwdCall c{};
     c.Ys = Ys; c.Cs = Cs; c.ps = ps; c.p = p; c.lambdas = lambdas; c.info = info;
@@ -416,10 +395,10 @@ int conan_fgw_mixup_barycenter_bwd(const float *Ys, const float *Cs, const float
     c.alpha = (double)params->alpha; c.rho = rho; c.eps = eps;
     c.ws = static_cast<char *>(workspace); c.w = mix_workspace(B, K, N, d, epoch);
     hipStream_t st = as_stream(stream);
-    const size_t bytes = mixb_vec_bytes(N) + (lds ? mixb_mat_bytes(N) : 0);
+    const size_t bytes = MixStore::lds_bytes(N);
     for (int t = max_iter - 1; t >= 0; --t) {
-        if (lds) launch_lds(k_fgw_mixup_bwd_coupling<true>, B * K, 64 * ACC_NW, bytes, st, c, t);
-        else launch_lds(k_fgw_mixup_bwd_coupling<false>, B * K, 64 * ACC_NW, bytes, st, c, t);
+        if (lds) launch_lds(k_fgw_mixup_bwd_coupling<true>, B * K, 64 * UNROLL_NW, bytes, st, c, t);
+        else launch_lds(k_fgw_mixup_bwd_coupling<false>, B * K, 64 * UNROLL_NW, bytes, st, c, t);
         k_fgw_mixup_bwd_reduce<<<B, 256, 0, st>>>(c, t);
     }
     k_fgw_mixup_bwd_final<<<B, 256, 0, st>>>(c);

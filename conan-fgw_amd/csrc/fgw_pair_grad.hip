@@ -1,7 +1,7 @@
 // The reference's gradient through the unrolled iterations of the pairwise entropic FGW solve for gfx950: the backward of conan_fgw_pair_fwd
 // (fgw_pair.hip) with solver PGD or PPA and the square loss (the reference's fgw_projected, bregman.py:70-167, around sinkhorn_log,
 // sinkhorn.py:388-450: plain differentiable torch) to M, C1, C2, p, q and the start G0, from the cotangents of the returned plan and of fgw_dist.
-// B pairs per launch, one workgroup of PG_NW wavefronts per pair (conan_fgw_pair_bwd; DESIGN.md 3.3, "Pairwise FGW: the unrolled gradient").
+// B pairs per launch, one workgroup of UNROLL_NW wavefronts per pair (conan_fgw_pair_bwd; DESIGN.md 3.3, "Pairwise FGW: the unrolled gradient").
 //
 // With c_i = sum_l C1_il^2 p_l, r_j = sum_l C2_jl^2 q_l (c', r': the same of the transposes), alpha' = 1 - alpha, an outer iteration is
 //     tens = 2 alpha (c 1^T + 1 r^T) - 4 alpha C1 T_k C2^T + alpha' M                                                       (symmetric)
@@ -30,10 +30,8 @@
 // (C1 T_k, which is kept for D^T (C1 T_k), and (C1 T_k) C2^T) + the factor product + 4 = 7 of size N^3 (the factor product is N^2 * 2 S_k);
 // not symmetric 4 + 1 + 9.  Each Sinkhorn sweep is two matrix-vector passes forward and two in reverse.
 //
-// Conventions of the sibling kernels (fgw_acc_grad.hip, sinkhorn_grad.hip): fp32 in and out, fp64 in between; dM, dC1, dC2, dp, dq accumulate in
-// fp64 over the whole walk and are rounded once; every sum has a fixed order (lane <-> line, the wavefronts split its entries, partial sums
-// in wavefront order), no atomics, nothing shared between workgroups; every loop is bounded by max_iter / num_iter_max: a corrupt info can
-// neither leave the record nor lengthen a loop.
+// The conventions this kernel shares with its siblings (precisions, summation order, loop bounds, nodes without mass, NaN, storage) are
+// stated once, in fgw_unroll.h, with the pieces the kernels can share.
 //
 // Nodes without mass (p_i = 0 or q_j = 0: how rectangular and own-size pairs are embedded): their entries of K and of every T_k are exactly
 // zero and constants of the solve, so Gb and D are zero there, their rows / columns of dM, dC1, dC2, dG0 and their dp_i / dq_j are written as
@@ -41,22 +39,14 @@
 // entry or, under PPA, an exact zero of an input plan at an entry with mass (log 0: the reference's NaN), gets NaN in every gradient and binfo
 // flag bit 2.
 //
-// Storage (fp64, pitch P = N | 1): five matrices T_k, K, Gb, D and a product buffer, 40 bytes per entry: in LDS while they fit
-// (conan_fgw_pair_bwd_lds_resident: N <= 61), else in the pair's slice of the workspace; the same code, so the same bits, on both paths.  The
-// record, the three accumulators and the Sinkhorn factors of the current iteration live in the workspace at every size.
-#include "fgw_common.h"
+// Storage (fgw_unroll.h): the five matrices are T_k, K, Gb, D and a product buffer (conan_fgw_pair_bwd_lds_resident: N <= 61).  The record, the
+// three accumulators and the Sinkhorn factors of the current iteration live in the workspace at every size.
+#include "fgw_unroll.h"
 #include "../../include/conan_fgw_hip_pair_grad.h"
 
 namespace {
 
-constexpr int PG_NW = 8;
-constexpr size_t PG_LDS_LIMIT = 160 * 1024;
-
-struct PairBwdCall {
-    const float *M, *C1, *C2, *p, *q, *G0;
-    const int *info;
-    const float *dT, *ddist;
-    float *dM, *dC1, *dC2, *dp, *dq, *dG0, *Tchk;
+struct PairBwdCall : UnrollPairIO {   // A = C1, B = C2, a = p, b = q, X0 = G0, dX = dT, chk = T_chk
     int *binfo;
     int N, P, max_iter, num_iter_max, ppa, symmetric;
     double alpha, eps, stop_thr;      // (fp64 from the host: the scalar unit has no fp64 conversions)
@@ -64,16 +54,11 @@ struct PairBwdCall {
     size_t ws_stride;                 // bytes per pair
 };
 
-// vectors: p, q, u, v, fb, gb, la, lb, z, w, dp, dq, the row / column constants of tens and of fgw_dist [N] each, 16 doubles of reduction
-// space, per-wavefront partial sums [NW][N]; rounded to 16 bytes
-__host__ __device__ inline size_t pgb_vec_bytes(int N) { return ((size_t)((16 + PG_NW) * (size_t)N + 16) * 8 + 15) / 16 * 16; }
-inline size_t pgb_mat_bytes(int N) { return (size_t)N * fgw_pitch(N) * 40; }
-inline bool pgb_resident(int N) { return pgb_vec_bytes(N) + pgb_mat_bytes(N) <= PG_LDS_LIMIT; }
-inline bool pgb_supported(int N) { return N > 0 && N <= 16384 && pgb_vec_bytes(N) <= PG_LDS_LIMIT; }      // (N P and N N stay far inside int)
+// vectors: p, q, u, v, fb, gb, la, lb, z, w, dp, dq, the row / column constants of tens and of fgw_dist [N] each, and reduction space
+using PairStore = UnrollStore<16, true>;
 __host__ __device__ inline size_t pgb_srec_bytes(int max_iter) { return (size_t)((max_iter + 1) / 2) * 8; }
-inline size_t pgb_stride(int N, int max_iter, int nim) {
-    const size_t NN = (size_t)N * N;
-    return al256(((size_t)max_iter + 3) * NN * 8 + ((size_t)4 * nim + 2) * N * 8 + pgb_srec_bytes(max_iter) + (pgb_resident(N) ? 0 : pgb_mat_bytes(N)));
+inline size_t pgb_stride(int N, int max_iter, int nim) {      // the record, the three accumulators, the Sinkhorn factors and the sweep counts
+    return PairStore::stride(N, ((size_t)max_iter + 3) * N * N * 8 + ((size_t)4 * nim + 2) * N * 8 + pgb_srec_bytes(max_iter));
 }
 
 // Registers: unbounded the compiler takes 177 (LDS) / 183 (streamed) VGPRs, one workgroup of 8 wavefronts per CU; held at 128 it spills 232 / 212
@@ -81,9 +66,9 @@ inline size_t pgb_stride(int N, int max_iter, int nim) {
 // build is 1.33 - 1.49 times faster (more workgroups than CUs: the second one hides the first one's barriers and LDS round trips); at
 // N = 90, B = 192 it is 2 - 7 % slower.  So the LDS-resident kernel is held at 128 and the streamed one is not.
 template <bool LDS>
-__global__ void __launch_bounds__(64 * PG_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBwdCall c) {
+__global__ void __launch_bounds__(64 * UNROLL_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBwdCall c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = PG_NW, NT = 64 * NW;
+    constexpr int NW = UNROLL_NW, NT = 64 * NW;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = c.N, P = c.P, NN = N * N, nim = c.num_iter_max;
     double *pa = reinterpret_cast<double *>(smem), *qb = pa + N, *uc = qb + N, *vc = uc + N, *fb = vc + N, *gb = fb + N, *la = gb + N, *lb = la + N;
@@ -96,10 +81,10 @@ __global__ void __launch_bounds__(64 * PG_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBw
     double *hZ = hV + (size_t)(nim + 1) * N;                                                    // z^1 .. z^nim [nim][N]
     double *hW = hZ + (size_t)nim * N;                                                          // w^1 .. w^nim
     int *srec = reinterpret_cast<int *>(hW + (size_t)nim * N);                                  // S_0 .. S_(max_iter - 1)
-    double *Tk = LDS ? reinterpret_cast<double *>(smem + pgb_vec_bytes(N)) : reinterpret_cast<double *>(reinterpret_cast<char *>(srec) + pgb_srec_bytes(c.max_iter));
+    double *Tk = LDS ? reinterpret_cast<double *>(smem + PairStore::vec_bytes(N)) : reinterpret_cast<double *>(reinterpret_cast<char *>(srec) + pgb_srec_bytes(c.max_iter));
     double *K = Tk + N * P, *Gb = K + N * P, *D = Gb + N * P, *A = D + N * P;
-    const float *Mg = c.M + (size_t)b * NN, *C1g = c.C1 + (size_t)b * NN, *C2g = c.C2 + (size_t)b * NN;
-    const float *G0g = c.G0 ? c.G0 + (size_t)b * NN : nullptr, *dTg = c.dT ? c.dT + (size_t)b * NN : nullptr;
+    const float *Mg = c.M + (size_t)b * NN, *C1g = c.A + (size_t)b * NN, *C2g = c.B + (size_t)b * NN;
+    const float *G0g = c.X0 ? c.X0 + (size_t)b * NN : nullptr, *dTg = c.dX ? c.dX + (size_t)b * NN : nullptr;
     const double alpha = c.alpha, om = 1.0 - alpha, four_alpha = 4.0 * alpha, two_alpha = 2.0 * alpha, eps = c.eps;
     const bool ppa = c.ppa != 0;
     const int iters = __builtin_amdgcn_readfirstlane(min(max(c.info[b * 4 + 0], 0), c.max_iter));      // a corrupt info can neither leave the record nor lengthen a loop
@@ -107,32 +92,14 @@ __global__ void __launch_bounds__(64 * PG_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBw
     const bool sym = c.symmetric < 0 ? __builtin_amdgcn_readfirstlane(c.info[b * 4 + 3]) != 0 : c.symmetric == 1;
     const double ninf = -__builtin_inf();
 
-    // out[l] = sum over the entries e of line l of f(l, e, offset of the entry): rows (col = false) or columns.  Lane <-> line, the wavefronts
-    // split its entries, then the partial sums in wavefront order.  Workgroup-collective, ends on a barrier.
-    auto line_sums = [&](bool col, auto f, double *out) {
-        const int sl = col ? 1 : P, se = col ? P : 1;
-        for (int l = lane; l < N; l += 64) {
-            double s = 0.0;
-            for (int e = wave; e < N; e += NW) s += f(l, e, l * sl + e * se);
-            pm[wave * N + l] = s;
-        }
-        __syncthreads();
-        for (int l = tid; l < N; l += NT) {
-            double s = 0.0;
-#pragma unroll
-            for (int u = 0; u < NW; ++u) s += pm[u * N + l];
-            out[l] = s;
-        }
-        __syncthreads();
-    };
-
+    auto line_sums = [&](bool col, auto f, double *out) { unroll_line_sums(tid, lane, wave, N, P, pm, col, f, out); };
+    auto live = [&](int i, int j) { return unroll_live(pa, qb, i, j); };
     for (int i = tid; i < N; i += NT) {
-        pa[i] = c.p ? (double)c.p[(size_t)b * N + i] : 1.0 / (double)N;
-        qb[i] = c.q ? (double)c.q[(size_t)b * N + i] : 1.0 / (double)N;
+        pa[i] = c.a ? (double)c.a[(size_t)b * N + i] : 1.0 / (double)N;
+        qb[i] = c.b ? (double)c.b[(size_t)b * N + i] : 1.0 / (double)N;
         dpa[i] = 0.0; dqa[i] = 0.0;
     }
     __syncthreads();
-    auto live = [&](int i, int j) { return pa[i] > 0.0 && qb[j] > 0.0; };
     for (int i = tid; i < N; i += NT) {                                     // init_matrix of the problem and of its transpose
         double s1 = 0.0, s1t = 0.0, s2 = 0.0, s2t = 0.0;
         for (int k = 0; k < N; ++k) {
@@ -253,8 +220,8 @@ __global__ void __launch_bounds__(64 * PG_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBw
         }
         __syncthreads();
     }
-    if (c.Tchk)
-        for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; c.Tchk[(size_t)b * NN + t] = (float)Tk[i * P + j]; }
+    if (c.chk)
+        for (int t = tid; t < NN; t += NT) { const int i = t / N, j = t - i * N; c.chk[(size_t)b * NN + t] = (float)Tk[i * P + j]; }
     const bool flagged = __syncthreads_or(bad) != 0 || (fwd_flags & 4) != 0;                                            // (workgroup-uniform)
     if (c.binfo && tid == 0) {
         c.binfo[b * 2 + 0] = sk_total;
@@ -263,12 +230,12 @@ __global__ void __launch_bounds__(64 * PG_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBw
     if (flagged) {                                                          // the reference's autograd gives NaN: so do we, everywhere
         const float nan = __builtin_nanf("");
         for (int t = tid; t < NN; t += NT) {
-            c.dM[(size_t)b * NN + t] = nan; c.dC1[(size_t)b * NN + t] = nan; c.dC2[(size_t)b * NN + t] = nan;
-            if (c.dG0) c.dG0[(size_t)b * NN + t] = nan;
+            c.dM[(size_t)b * NN + t] = nan; c.dA[(size_t)b * NN + t] = nan; c.dB[(size_t)b * NN + t] = nan;
+            if (c.dX0) c.dX0[(size_t)b * NN + t] = nan;
         }
         for (int i = tid; i < N; i += NT) {
-            if (c.dp) c.dp[(size_t)b * N + i] = nan;
-            if (c.dq) c.dq[(size_t)b * N + i] = nan;
+            if (c.da) c.da[(size_t)b * N + i] = nan;
+            if (c.db) c.db[(size_t)b * N + i] = nan;
         }
         return;
     }
@@ -416,21 +383,20 @@ __global__ void __launch_bounds__(64 * PG_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBw
 
     // ---- the start: its own gradient, or through p q^T to the weights -----------------------------------------------------------------------------
     if (!G0g) {
-        line_sums(false, [&](int, int e, int o) { return Gb[o] * qb[e]; }, zc);
-        line_sums(true, [&](int, int e, int o) { return Gb[o] * pa[e]; }, wc);
+        unroll_start_sums(tid, lane, wave, N, P, pm, Gb, pa, qb, zc, wc);
         for (int i = tid; i < N; i += NT) { dpa[i] += zc[i]; dqa[i] += wc[i]; }
         __syncthreads();
     }
     for (int t = tid; t < NN; t += NT) {
         const int i = t / N, j = t - i * N;
         c.dM[(size_t)b * NN + t] = live(i, j) ? (float)dMa[t] : 0.f;
-        c.dC1[(size_t)b * NN + t] = (pa[i] > 0.0 && pa[j] > 0.0) ? (float)dC1a[t] : 0.f;
-        c.dC2[(size_t)b * NN + t] = (qb[i] > 0.0 && qb[j] > 0.0) ? (float)dC2a[t] : 0.f;
-        if (c.dG0) c.dG0[(size_t)b * NN + t] = live(i, j) ? (float)Gb[i * P + j] : 0.f;
+        c.dA[(size_t)b * NN + t] = (pa[i] > 0.0 && pa[j] > 0.0) ? (float)dC1a[t] : 0.f;
+        c.dB[(size_t)b * NN + t] = (qb[i] > 0.0 && qb[j] > 0.0) ? (float)dC2a[t] : 0.f;
+        if (c.dX0) c.dX0[(size_t)b * NN + t] = live(i, j) ? (float)Gb[i * P + j] : 0.f;
     }
     for (int i = tid; i < N; i += NT) {
-        if (c.dp) c.dp[(size_t)b * N + i] = pa[i] > 0.0 ? (float)dpa[i] : 0.f;
-        if (c.dq) c.dq[(size_t)b * N + i] = qb[i] > 0.0 ? (float)dqa[i] : 0.f;
+        if (c.da) c.da[(size_t)b * N + i] = pa[i] > 0.0 ? (float)dpa[i] : 0.f;
+        if (c.db) c.db[(size_t)b * N + i] = qb[i] > 0.0 ? (float)dqa[i] : 0.f;
     }
 }
 
@@ -438,10 +404,10 @@ __global__ void __launch_bounds__(64 * PG_NW, LDS ? 4 : 2) k_fgw_pair_bwd(PairBw
 
 extern "C" {
 
-int conan_fgw_pair_bwd_lds_resident(int N) { return N > 0 && pgb_resident(N) ? 1 : 0; }
+int conan_fgw_pair_bwd_lds_resident(int N) { return N > 0 && PairStore::resident(N) ? 1 : 0; }
 
 long long conan_fgw_pair_bwd_workspace_bytes(int B, int N, int max_iter, int num_iter_max) {
-    if (B <= 0 || max_iter <= 0 || num_iter_max <= 0 || !pgb_supported(N)) return 0;
+    if (B <= 0 || max_iter <= 0 || num_iter_max <= 0 || !PairStore::supported(N)) return 0;
     return (long long)((size_t)B * pgb_stride(N, max_iter, num_iter_max));
 }
 
@@ -449,22 +415,17 @@ int conan_fgw_pair_bwd(const float *M, const float *C1, const float *C2, const f
                        double epsilon, int max_iter, int num_iter_max, double stop_thr, int solver, int symmetric, const int *info, const float *dT,
                        const float *ddist, float *dM, float *dC1, float *dC2, float *dp, float *dq, float *dG0, float *T_chk, int *binfo,
                        void *workspace, void *stream) {
-    if (!M || !C1 || !C2 || !info || !dM || !dC1 || !dC2 || !workspace || B <= 0 || N <= 0 || max_iter <= 0 || num_iter_max <= 0) return CONAN_E_BADARG;
-    if (!dT && !ddist) return CONAN_E_BADARG;
-    if ((dp && !p) || (dq && !q) || (dG0 && !G0)) return CONAN_E_BADARG;
-    if (!(epsilon > 0.0 && epsilon <= 1.79769313486231570815e308) || !(alpha == alpha) || !(stop_thr == stop_thr)) return CONAN_E_BADARG;
-    if (solver < 0 || solver > 1 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
-    if (!pgb_supported(N)) return CONAN_E_UNSUPPORTED;
-    const bool lds = pgb_resident(N);
     PairBwdCall c{};
-    c.M = M; c.C1 = C1; c.C2 = C2; c.p = p; c.q = q; c.G0 = G0; c.info = info; c.dT = dT; c.ddist = ddist;
-    c.dM = dM; c.dC1 = dC1; c.dC2 = dC2; c.dp = dp; c.dq = dq; c.dG0 = dG0; c.Tchk = T_chk; c.binfo = binfo;
+    static_cast<UnrollPairIO &>(c) = {M, C1, C2, p, q, G0, info, dT, ddist, dM, dC1, dC2, dp, dq, dG0, T_chk};
+    if (max_iter <= 0 || num_iter_max <= 0 || unroll_pair_args(c, B, N, workspace, epsilon, alpha) != CONAN_OK || !(stop_thr == stop_thr)) return CONAN_E_BADARG;
+    if (solver < 0 || solver > 1 || symmetric < -1 || symmetric > 1) return CONAN_E_BADARG;
+    if (!PairStore::supported(N)) return CONAN_E_UNSUPPORTED;
+    c.binfo = binfo;
     c.N = N; c.P = pitch_of(N); c.max_iter = max_iter; c.num_iter_max = num_iter_max; c.ppa = solver == 1; c.symmetric = symmetric;
     c.alpha = alpha; c.eps = epsilon; c.stop_thr = stop_thr;
     c.ws = static_cast<char *>(workspace); c.ws_stride = pgb_stride(N, max_iter, num_iter_max);
-    const size_t bytes = pgb_vec_bytes(N) + (lds ? pgb_mat_bytes(N) : 0);
-    if (lds) launch_lds(k_fgw_pair_bwd<true>, B, 64 * PG_NW, bytes, as_stream(stream), c);
-    else launch_lds(k_fgw_pair_bwd<false>, B, 64 * PG_NW, bytes, as_stream(stream), c);
+    if (PairStore::resident(N)) launch_lds(k_fgw_pair_bwd<true>, B, 64 * UNROLL_NW, PairStore::lds_bytes(N), as_stream(stream), c);
+    else launch_lds(k_fgw_pair_bwd<false>, B, 64 * UNROLL_NW, PairStore::lds_bytes(N), as_stream(stream), c);
     CONAN_LAUNCH_CHECK();
     return CONAN_OK;
 }

@@ -1443,6 +1443,29 @@ def _acc_dist(M, A, Bm, a, b, X, B, N, alpha):
     return dist
 
 
+def _pair_unrolled_backward(ctx, saved, gX, gdist, entry, ws_query, ws_args, scalars, what, n_chk):
+    """The backward of the three pair-form unrolled ops: `entry`(M, A, Bm, a, b, X0, B, N, *scalars, info, gX, gdist, dM, dA, dBm, da, db, dX0,
+    n_chk null check outputs, workspace, stream) -> the gradients of M, A, Bm, a, b, X0 (None where not needed).  `ws_query`(B, N, *ws_args) = 0
+    says that N is not supported: NotImplementedError naming `what`."""
+    M, A, Bm, a, b, X0, info = saved
+    B, N = ctx.dims
+    dev = M.device
+    gX = None if gX is None else _c(gX.to(f32))
+    gdist = None if gdist is None else _c(gdist.to(f32))
+    need = ctx.needs_input_grad
+    dM, dA, dBm = (torch.empty(B, N, N, dtype=f32, device=dev) for _ in range(3))
+    da = torch.empty(B, N, dtype=f32, device=dev) if a is not None and need[3] else None
+    db = torch.empty(B, N, dtype=f32, device=dev) if b is not None and need[4] else None
+    dX0 = torch.empty(B, N, N, dtype=f32, device=dev) if X0 is not None and need[5] else None
+    nbytes = int(getattr(lib(), ws_query)(B, N, *ws_args))
+    if nbytes == 0:
+        raise NotImplementedError(f"the unrolled {what} gradient does not support N = {N}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call(entry, ptr(M, f32), ptr(A, f32), ptr(Bm, f32), ptr(a), ptr(b), ptr(X0), B, N, *scalars, ptr(info), ptr(gX), ptr(gdist), ptr(dM), ptr(dA),
+         ptr(dBm), ptr(da), ptr(db), ptr(dX0), *(None,) * n_chk, ptr(ws), stream_ptr())
+    return dM if need[0] else None, dA if need[1] else None, dBm if need[2] else None, da, db, dX0
+
+
 class _FgwAccUnrolledFn(torch.autograd.Function):
     """fgw_acc_pair_batched's launch and fgw_acc_pair_distance's distance with conan_fgw_acc_pair_bwd as their backward: the gradient through the
     executed epochs, as the reference's autograd delivers it, from the cotangents of X and dist to M, A, Bm, a, b and X0.  The backward is ONE
@@ -1462,25 +1485,10 @@ class _FgwAccUnrolledFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gX, gdist, *_):
-        M, A, Bm, a, b, X0, info = ctx.saved_tensors
-        B, N = ctx.dims
         if gX is None and gdist is None:
             return (None,) * 11
-        dev = M.device
-        gX = None if gX is None else _c(gX.to(f32))
-        gdist = None if gdist is None else _c(gdist.to(f32))
-        need = ctx.needs_input_grad
-        dM, dA, dBm = (torch.empty(B, N, N, dtype=f32, device=dev) for _ in range(3))
-        da = torch.empty(B, N, dtype=f32, device=dev) if a is not None and need[3] else None
-        db = torch.empty(B, N, dtype=f32, device=dev) if b is not None and need[4] else None
-        dX0 = torch.empty(B, N, N, dtype=f32, device=dev) if X0 is not None and need[5] else None
-        nbytes = int(lib().conan_fgw_acc_pair_bwd_workspace_bytes(B, N, ctx.epoch))
-        if nbytes == 0:
-            raise NotImplementedError(f"the unrolled FGWMixup gradient does not support N = {N}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        call("conan_fgw_acc_pair_bwd", ptr(M, f32), ptr(A, f32), ptr(Bm, f32), ptr(a), ptr(b), ptr(X0), B, N, ctx.alpha, ctx.rho, ctx.epoch, ptr(info),
-             ptr(gX), ptr(gdist), ptr(dM), ptr(dA), ptr(dBm), ptr(da), ptr(db), ptr(dX0), None, ptr(ws), stream_ptr())
-        return (dM if need[0] else None, dA if need[1] else None, dBm if need[2] else None, da, db, dX0) + (None,) * 5
+        return _pair_unrolled_backward(ctx, ctx.saved_tensors, gX, gdist, "conan_fgw_acc_pair_bwd", "conan_fgw_acc_pair_bwd_workspace_bytes", (ctx.epoch,),
+                                       (ctx.alpha, ctx.rho, ctx.epoch), "FGWMixup", 1) + (None,) * 5
 
 
 def fgw_acc_pair_unrolled(M: Tensor, A: Tensor, Bm: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = None, X0: Optional[Tensor] = None, *,
@@ -1530,27 +1538,11 @@ class _FgwPairUnrolledFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gT, gdist, *_):
-        M, C1, C2, p, q, G0, info = ctx.saved_tensors
-        B, N = ctx.dims
         if gT is None and gdist is None:
             return (None,) * 11
-        alpha, epsilon, max_iter, num_iter_max, stop_thr, solver_code, sym_code = ctx.cfg
-        dev = M.device
-        gT = None if gT is None else _c(gT.to(f32))
-        gdist = None if gdist is None else _c(gdist.to(f32))
-        need = ctx.needs_input_grad
-        dM, dC1, dC2 = (torch.empty(B, N, N, dtype=f32, device=dev) for _ in range(3))
-        dp = torch.empty(B, N, dtype=f32, device=dev) if p is not None and need[3] else None
-        dq = torch.empty(B, N, dtype=f32, device=dev) if q is not None and need[4] else None
-        dG0 = torch.empty(B, N, N, dtype=f32, device=dev) if G0 is not None and need[5] else None
-        nbytes = int(lib().conan_fgw_pair_bwd_workspace_bytes(B, N, max_iter, num_iter_max))
-        if nbytes == 0:
-            raise NotImplementedError(f"the unrolled pairwise FGW gradient does not support N = {N}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        call("conan_fgw_pair_bwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, alpha, epsilon, max_iter, num_iter_max, stop_thr,
-             solver_code, sym_code, ptr(info), ptr(gT), ptr(gdist), ptr(dM), ptr(dC1), ptr(dC2), ptr(dp), ptr(dq), ptr(dG0), None, None, ptr(ws),
-             stream_ptr())
-        return (dM if need[0] else None, dC1 if need[1] else None, dC2 if need[2] else None, dp, dq, dG0) + (None,) * 5
+        max_iter, num_iter_max = ctx.cfg[2:4]
+        return _pair_unrolled_backward(ctx, ctx.saved_tensors, gT, gdist, "conan_fgw_pair_bwd", "conan_fgw_pair_bwd_workspace_bytes", (max_iter, num_iter_max),
+                                       ctx.cfg, "pairwise FGW", 2) + (None,) * 5
 
 
 def _pair_unrolled_params(alpha, epsilon, max_iter, tol, num_iter_max, stop_thr, loss_fun, solver, symmetric):
@@ -1622,26 +1614,10 @@ class _FgwBregmanUnrolledFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gT, gdist, *_):
-        M, C1, C2, p, q, G0, info = ctx.saved_tensors
-        B, N = ctx.dims
         if gT is None and gdist is None:
             return (None,) * 10
-        alpha, epsilon, max_iter, loss_code, sym_code = ctx.cfg
-        dev = M.device
-        gT = None if gT is None else _c(gT.to(f32))
-        gdist = None if gdist is None else _c(gdist.to(f32))
-        need = ctx.needs_input_grad
-        dM, dC1, dC2 = (torch.empty(B, N, N, dtype=f32, device=dev) for _ in range(3))
-        dp = torch.empty(B, N, dtype=f32, device=dev) if p is not None and need[3] else None
-        dq = torch.empty(B, N, dtype=f32, device=dev) if q is not None and need[4] else None
-        dG0 = torch.empty(B, N, N, dtype=f32, device=dev) if G0 is not None and need[5] else None
-        nbytes = int(lib().conan_fgw_bregman_bwd_workspace_bytes(B, N, max_iter))
-        if nbytes == 0:
-            raise NotImplementedError(f"the unrolled BAPG FGW gradient does not support N = {N}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        call("conan_fgw_bregman_bwd", ptr(M, f32), ptr(C1, f32), ptr(C2, f32), ptr(p), ptr(q), ptr(G0), B, N, alpha, epsilon, max_iter, loss_code,
-             sym_code, ptr(info), ptr(gT), ptr(gdist), ptr(dM), ptr(dC1), ptr(dC2), ptr(dp), ptr(dq), ptr(dG0), None, None, ptr(ws), stream_ptr())
-        return (dM if need[0] else None, dC1 if need[1] else None, dC2 if need[2] else None, dp, dq, dG0) + (None,) * 4
+        return _pair_unrolled_backward(ctx, ctx.saved_tensors, gT, gdist, "conan_fgw_bregman_bwd", "conan_fgw_bregman_bwd_workspace_bytes", (ctx.cfg[2],),
+                                       ctx.cfg, "BAPG FGW", 2) + (None,) * 4
 
 
 def fgw_bregman_unrolled(M: Tensor, C1: Tensor, C2: Tensor, p: Optional[Tensor] = None, q: Optional[Tensor] = None, G0: Optional[Tensor] = None, *,
