@@ -257,6 +257,9 @@ __global__ void __launch_bounds__(256) k_cfconv_bwd_wp128(const float *__restric
                 ga[u] = reinterpret_cast<const float4 *>(dout + (size_t)b0 * F)[l32];
                 xb[u] = reinterpret_cast<const float4 *>(x + (size_t)a1 * F)[l32];
                 gb[u] = reinterpret_cast<const float4 *>(dout + (size_t)b1 * F)[l32];
+                // a one-direction pair has no second edge: the two loads above fetched row 0 as a stand-in.  SELECT it away — 0 * x[0] * dout[0] is NaN
+                // when row 0 holds a NaN or an Inf, and would put it into every one-direction pair.  The expression below stays as it is (same bits).
+                if (mm[u] == 0.f) { xb[u] = make_float4(0.f, 0.f, 0.f, 0.f); gb[u] = make_float4(0.f, 0.f, 0.f, 0.f); }
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -320,7 +323,7 @@ __global__ void __launch_bounds__(256) k_cfconv_bwd_xw128(const float *__restric
                 }
             }
             for (int k2 = 0; k2 < cnt; k2 += 2 * U) {
-                float4 w4[U], g4[U], x4[U];
+                float4 w4[U], g4[U], x4[U], d4[U];
                 float m[U], mm[U], cc[U];
                 int rr[U], own[U];
 #pragma unroll
@@ -337,6 +340,9 @@ __global__ void __launch_bounds__(256) k_cfconv_bwd_xw128(const float *__restric
                     // ANYX: x[t] for every edge (its address does not wait for the pair table; an edge that does not own its pair wastes an L2 row read);
                     // else: such an edge re-reads the row this wavefront holds
                     x4[u] = reinterpret_cast<const float4 *>(x + (size_t)((ANYX || own[u]) ? t : j) * F)[l32];
+                    // a one-direction pair does not depend on x[t] and dout[j]: selected away as in k_cfconv_bwd_wp128 (0 * NaN is NaN), same expression below
+                    d4[u] = ds;
+                    if (mm[u] == 0.f) { x4[u] = make_float4(0.f, 0.f, 0.f, 0.f); d4[u] = make_float4(0.f, 0.f, 0.f, 0.f); }
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -347,10 +353,10 @@ __global__ void __launch_bounds__(256) k_cfconv_bwd_xw128(const float *__restric
                 for (int u = 0; u < U; ++u) {
                     if (!own[u]) continue;
                     float4 r;
-                    r.x = (xs.x * g4[u].x + mm[u] * x4[u].x * ds.x) * cc[u];
-                    r.y = (xs.y * g4[u].y + mm[u] * x4[u].y * ds.y) * cc[u];
-                    r.z = (xs.z * g4[u].z + mm[u] * x4[u].z * ds.z) * cc[u];
-                    r.w = (xs.w * g4[u].w + mm[u] * x4[u].w * ds.w) * cc[u];
+                    r.x = (xs.x * g4[u].x + mm[u] * x4[u].x * d4[u].x) * cc[u];
+                    r.y = (xs.y * g4[u].y + mm[u] * x4[u].y * d4[u].y) * cc[u];
+                    r.z = (xs.z * g4[u].z + mm[u] * x4[u].z * d4[u].z) * cc[u];
+                    r.w = (xs.w * g4[u].w + mm[u] * x4[u].w * d4[u].w) * cc[u];
                     reinterpret_cast<float4 *>(dWp + (size_t)rr[u] * F)[l32] = r;
                     amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
                 }

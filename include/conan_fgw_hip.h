@@ -416,7 +416,9 @@ int conan_cfconv_bwd_x(const float *W, const float *dout, const int *t_rowptr, c
 /* Pair-level filter gradient (before the cosine cutoff): dWp[p,:] = C(d_p) * sum over the (1 or 2) edges of pair p of
  * x[src(e),:] * dout[tgt(e),:].  gmax (nullable, num_filters = 128 only): one device float, ZEROED by the caller before the call; the
  * kernel raises it to max |dWp| as it writes.  conan_filter_bwd / conan_linear_wgrad take that word to run their products on two
- * fp16 planes of the gradient scaled into fp16's range (half the matrix-pipe work of the three-plane bf16 form). */
+ * fp16 planes of the gradient scaled into fp16's range (half the matrix-pipe work of the three-plane bf16 form).
+ * A pair with one direction only (pair_e1 = -1) depends on x[src(e0)] and dout[tgt(e0)] and on no other row: a NaN or Inf elsewhere in x / dout
+ * does not reach it (the same holds in conan_cfconv_bwd_xw_pairs). */
 int conan_cfconv_bwd_w_pairs(const float *x, const float *dout, const int *num_pairs_dev, int max_pairs, const int *pair_e0,
                              const int *pair_e1, const int *col, const int *tgt, int num_filters, const float *pair_dist,
                              float cutoff, float *dWp, float *gmax, void *stream);
