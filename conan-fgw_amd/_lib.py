@@ -13,6 +13,11 @@ _LIB = None
 ABI_VERSION = 6            # == CONAN_FGW_ABI_VERSION of include/conan_fgw_hip.h (tests/test_abi.py compares the two)
 
 c_int, c_float, c_void_p, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong
+f32, i32, i64 = torch.float32, torch.int32, torch.int64      # the dtype aliases of ops.py and ot_ops.py
+
+
+def _c(t: torch.Tensor) -> torch.Tensor:
+    return t if t.is_contiguous() else t.contiguous()
 
 
 class FgwParams(ctypes.Structure):

@@ -33,7 +33,7 @@ from typing import List, Optional, Sequence, Union
 import torch
 from torch import Tensor
 
-from . import ops
+from . import ops, ot_ops
 
 
 def _embed_graphs(N, Ys_l, Cs_l, ps, p, sizes, d, dev):
@@ -138,7 +138,7 @@ def fgw_barycenters(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, p=No
             lam = torch.as_tensor(lambdas, dtype=torch.float32, device=Ys_t.device)
     # adjacency-like inputs (integers in [0, 255]: what to_dense_adj produces) take the byte-wide LDS layout of the N <= 64 kernel
     small_int = bool(((Cs_t == Cs_t.round()) & (Cs_t >= 0) & (Cs_t <= 255)).all())
-    res = ops.fgw_barycenter_batched(
+    res = ot_ops.fgw_barycenter_batched(
         Ys_t.view(1, K, N, d), Cs_t.view(1, K, N, N), ps=ps_t, p=p_t, lambdas=lam,
         init_C=init_C.to(torch.float32).view(1, N, N), init_Y=None if init_Y is None else init_Y.to(torch.float32).view(1, N, d),
         alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, inner_tol=1e-4, num_iter_max=num_iter_max, stop_thr=stop_thr,
@@ -182,7 +182,7 @@ def fused_ACC_torch(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=1e-
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"fused_ACC_torch runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
     one = lambda t: None if t is None else t.unsqueeze(0)
-    Xo, objs, info = ops.fgw_acc_pair_batched(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps)
+    Xo, objs, info = ot_ops.fgw_acc_pair_batched(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps)
     stored = int(info[0, 1].item())
     return Xo[0], [objs[0, k] for k in range(stored)]
 
@@ -201,7 +201,7 @@ def fgw_mixup_distance(M, A, B, a=None, b=None, X=None, alpha=0, epoch=200, eps=
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"fgw_mixup_distance runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
     one = lambda t: None if t is None else t.unsqueeze(0)
-    dist, Xo, objs, info = ops.fgw_acc_pair_distance(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps,
+    dist, Xo, objs, info = ot_ops.fgw_acc_pair_distance(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps,
                                                      return_plan=True)
     if not log:
         return dist[0]
@@ -214,7 +214,7 @@ def _unrolled_pair(fn, M, A, B, a, b, X, alpha, epoch, eps, rho):
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"{fn} runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
     one = lambda t: None if t is None else t.unsqueeze(0)
-    Xo, dist, objs, info = ops.fgw_acc_pair_unrolled(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps)
+    Xo, dist, objs, info = ot_ops.fgw_acc_pair_unrolled(one(M), one(A), one(B), one(a), one(b), one(X), alpha=alpha, rho=rho, epoch=epoch, eps=eps)
     stored = int(info[0, 1].item())
     return Xo[0], dist[0], [objs[0, k] for k in range(stored)]
 
@@ -319,7 +319,7 @@ def fgw_barycenters_BAPG(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None,
     iteration counts follow the reference's fp64 run; a weight that is exactly ZERO marks an absent node (the reference lifts its entries by
     1e-10 every epoch); a NaN result (exp under- / overflow at small rho) is the reference's NaN.  Runs on the GPU only.
     fgw_barycenters_BAPG_unrolled is the same solve with the reference's gradient through every epoch of every coupling solve."""
-    return _barycenters_BAPG("fgw_barycenters_BAPG", ops.fgw_mixup_barycenter_batched, N, Ys, Cs, ps, p, lambdas, loss_fun, alpha, max_iter, tol, rho,
+    return _barycenters_BAPG("fgw_barycenters_BAPG", ot_ops.fgw_mixup_barycenter_batched, N, Ys, Cs, ps, p, lambdas, loss_fun, alpha, max_iter, tol, rho,
                              log, init_C, init_Y, fixed_structure, fixed_features, seed)
 
 
@@ -335,7 +335,7 @@ def fgw_barycenters_BAPG_unrolled(N, Ys: Sequence[Tensor], Cs: Sequence[Tensor],
     Deviations: log["T"], log["Ts_iter"] and log["Ms"] carry no gradient (the reference's have a graph); the stop decisions carry none; a
     weight that is exactly zero marks an absent node; a run that ends in NaN gives NaN gradients.  No double backward.  The backward replays
     every coupling solve (ops.fgw_mixup_barycenter_unrolled states its launches and workspace).  Runs on the GPU only."""
-    return _barycenters_BAPG("fgw_barycenters_BAPG_unrolled", ops.fgw_mixup_barycenter_unrolled, N, Ys, Cs, ps, p, lambdas, loss_fun, alpha, max_iter,
+    return _barycenters_BAPG("fgw_barycenters_BAPG_unrolled", ot_ops.fgw_mixup_barycenter_unrolled, N, Ys, Cs, ps, p, lambdas, loss_fun, alpha, max_iter,
                              tol, rho, log, init_C, init_Y, fixed_structure, fixed_features, seed)
 
 
@@ -351,9 +351,9 @@ def _pair_solve(M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, alpha, max_it
     kw = dict(alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, num_iter_max=num_iter_max, stop_thr=stop_thr, loss_fun=loss_fun, solver=solver,
               symmetric=symmetric)
     if distance:
-        dist, T, info, errs = ops.fgw_pair_distance(one(M), one(C1), one(C2), one(p), one(q), one(G0), return_plan=True, **kw)
+        dist, T, info, errs = ot_ops.fgw_pair_distance(one(M), one(C1), one(C2), one(p), one(q), one(G0), return_plan=True, **kw)
     else:
-        T, dist, info, errs = ops.fgw_pair_batched(one(M), one(C1), one(C2), one(p), one(q), one(G0), with_dist=bool(log), **kw)
+        T, dist, info, errs = ot_ops.fgw_pair_batched(one(M), one(C1), one(C2), one(p), one(q), one(G0), with_dist=bool(log), **kw)
     T = T[0]
     # bregman.py:159-162 (PGD / PPA: the plan's total mass) and :267-270 (BAPG: a NaN), one host synchronisation as in the reference
     failed = bool(torch.isnan(T).any()) if solver == "BAPG" else bool(abs(T.sum() - 1) > 1e-5)
@@ -459,7 +459,7 @@ def _pair_solve_unrolled(fn, M, C1, C2, p, q, G0, loss_fun, epsilon, symmetric, 
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"{fn} runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
     one = lambda t: None if t is None else t.unsqueeze(0)
-    T, dist, info, errs = ops.fgw_pair_unrolled(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol,
+    T, dist, info, errs = ot_ops.fgw_pair_unrolled(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol,
                                                 num_iter_max=num_iter_max, stop_thr=stop_thr, loss_fun=loss_fun, solver=solver, symmetric=symmetric)
     T = T[0]
     if bool(abs(T.detach().sum() - 1) > 1e-5):                              # bregman.py:159-162, one host synchronisation as in the reference
@@ -509,7 +509,7 @@ def _bregman_solve_unrolled(fn, M, C1, C2, p, q, G0, loss_fun, epsilon, symmetri
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise NotImplementedError(f"{fn} runs on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
     one = lambda t: None if t is None else t.unsqueeze(0)
-    T, dist, info, errs = ops.fgw_bregman_unrolled(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter,
+    T, dist, info, errs = ot_ops.fgw_bregman_unrolled(one(M), one(C1), one(C2), one(p), one(q), one(G0), alpha=alpha, epsilon=epsilon, max_iter=max_iter,
                                                    tol=tol, loss_fun=loss_fun, symmetric=symmetric)
     T, dist = T[0], dist[0]
     if bool(torch.isnan(T.detach()).any()):                                 # bregman.py:267-270, one host synchronisation as in the reference
@@ -593,7 +593,7 @@ def _pairwise(name, Ys, Cs, ps, kw, with_grad, without_grad):
     return out
 
 
-_PLAIN_PAIRS = (lambda *a, **k: ops.fgw_pair_batched(*a, **k)[1], lambda *a, **k: ops.fgw_pair_list(*a, **k)[1])
+_PLAIN_PAIRS = (lambda *a, **k: ot_ops.fgw_pair_batched(*a, **k)[1], lambda *a, **k: ot_ops.fgw_pair_list(*a, **k)[1])
 
 
 def fgw_pairwise_distances(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, alpha=0.5, epsilon=0.1, loss_fun="square_loss", symmetric=None,
@@ -608,7 +608,7 @@ def fgw_pairwise_distances(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, 
     are the same as before."""
     kw = dict(alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, num_iter_max=numItermax, stop_thr=stopThr, loss_fun=loss_fun, solver=solver,
               symmetric=symmetric)
-    return _pairwise("fgw_pairwise_distances", Ys, Cs, ps, kw, (ops.fgw_pair_distance, ops.fgw_pair_distance_list), _PLAIN_PAIRS)
+    return _pairwise("fgw_pairwise_distances", Ys, Cs, ps, kw, (ot_ops.fgw_pair_distance, ot_ops.fgw_pair_distance_list), _PLAIN_PAIRS)
 
 
 def fgw_pairwise_distances_unrolled(Ys: Sequence[Tensor], Cs: Sequence[Tensor], ps=None, alpha=0.5, epsilon=0.1, loss_fun="square_loss", symmetric=None,
@@ -619,9 +619,9 @@ def fgw_pairwise_distances_unrolled(Ys: Sequence[Tensor], Cs: Sequence[Tensor], 
     kw = dict(alpha=alpha, epsilon=epsilon, max_iter=max_iter, tol=tol, num_iter_max=numItermax, stop_thr=stopThr, loss_fun=loss_fun, solver=solver,
               symmetric=symmetric)
     if solver == "BAPG" or (solver in ("PGD", "PPA") and loss_fun == "kl_loss"):
-        ops._pair_unrolled_params(**kw)                                     # (raises: NotImplementedError under the new names)
+        ot_ops._pair_unrolled_params(**kw)                                     # (raises: NotImplementedError under the new names)
     return _pairwise("fgw_pairwise_distances_unrolled", Ys, Cs, ps, kw,
-                     (lambda *a, **k: ops.fgw_pair_unrolled(*a, **k)[1], lambda *a, **k: ops.fgw_pair_unrolled_list(*a, **k)[1]), _PLAIN_PAIRS)
+                     (lambda *a, **k: ot_ops.fgw_pair_unrolled(*a, **k)[1], lambda *a, **k: ot_ops.fgw_pair_unrolled_list(*a, **k)[1]), _PLAIN_PAIRS)
 
 
 def normalize_tensor(tensor: Tensor, a: float, b: float) -> Tensor:

@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 from torch.nn import Embedding, Linear, ModuleList, Sequential
 
-from . import ops
+from . import ops, ot_ops
 
 OptTensor = Optional[Tensor]
 
@@ -259,7 +259,7 @@ class SchNetNoSum(torch.nn.Module):
             max_nodes = int((gp[1:] - gp[:-1]).max().item())                # host sync (to_dense_batch does the same, :242)
         Ys, _ = ops.fgw_densify(node_feature, graph, max_nodes, self.FEATURE_SHIFT, adjacency=False)      # (to_dense_adj, :249-252, is read by the solver from the graph's ragged lists)       # :242-252 with :41-87
         N, d = max_nodes, node_feature.shape[1]
-        Y, C, T, info, errs = ops.fgw_barycenter_batched(Ys.view(batch_size, K, N, d), None, adjacency=graph)   # :259-306
+        Y, C, T, info, errs = ot_ops.fgw_barycenter_batched(Ys.view(batch_size, K, N, d), None, adjacency=graph)   # :259-306
         self.last_fgw = dict(Y=Y, C=C, T=T, info=info, errs=errs, Ys=Ys)
         return Y, graph
 

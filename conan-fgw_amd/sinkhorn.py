@@ -33,7 +33,7 @@ from typing import Optional, Sequence
 import torch
 from torch import Tensor
 
-from . import ops
+from . import ot_ops
 from .fgw import feature_cost
 
 _NOT_CONVERGED = ("Sinkhorn did not converge. You might want to increase the number of iterations `numItermax` or the regularization "
@@ -63,11 +63,11 @@ def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost
     warm = None if warmstart is None else (warmstart[0].unsqueeze(0), warmstart[1].unsqueeze(0))
     kw = dict(reg=reg, method=method, num_iter_max=numItermax, stop_thr=stopThr, warmstart=warm)
     if grad == "unrolled":
-        T, loss, log_u, log_v, info, errs = ops.sinkhorn_unrolled(M.unsqueeze(0), a, b, **kw)
+        T, loss, log_u, log_v, info, errs = ot_ops.sinkhorn_unrolled(M.unsqueeze(0), a, b, **kw)
     elif cost:
-        loss, T, log_u, log_v, info, errs = ops.sinkhorn_loss(M.unsqueeze(0), a, b, return_plan=True, **kw)
+        loss, T, log_u, log_v, info, errs = ot_ops.sinkhorn_loss(M.unsqueeze(0), a, b, return_plan=True, **kw)
     else:
-        T, loss, log_u, log_v, info, errs = ops.sinkhorn_batched(M.unsqueeze(0), a, b, **kw)
+        T, loss, log_u, log_v, info, errs = ot_ops.sinkhorn_batched(M.unsqueeze(0), a, b, **kw)
     res = loss[0] if cost else T[0]
     if not (log or warn or method == "sinkhorn"):
         return res
@@ -111,9 +111,9 @@ def _solve_ext(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, 
     warm = None if warmstart is None else (warmstart[0].unsqueeze(0), warmstart[1].unsqueeze(0))
     kw = dict(reg=reg, method=method, num_iter_max=numItermax, stop_thr=stopThr, warmstart=warm, **params)
     if cost:
-        loss, T, log_u, log_v, alpha, beta, info, errs, extra = ops.sinkhorn_ext_loss(M.unsqueeze(0), a, b, return_plan=True, **kw)
+        loss, T, log_u, log_v, alpha, beta, info, errs, extra = ot_ops.sinkhorn_ext_loss(M.unsqueeze(0), a, b, return_plan=True, **kw)
     else:
-        T, loss, log_u, log_v, alpha, beta, info, errs, extra = ops.sinkhorn_ext_batched(M.unsqueeze(0), a, b, **kw)
+        T, loss, log_u, log_v, alpha, beta, info, errs, extra = ot_ops.sinkhorn_ext_batched(M.unsqueeze(0), a, b, **kw)
     res = loss[0] if cost else T[0]
     niter, flags, nchk, last = info[0].tolist()
     if method == "sinkhorn_epsilon_scaling":
@@ -172,14 +172,14 @@ def sinkhorn(a, b, M, reg, method="sinkhorn_log", numItermax=100, stopThr=1e-5, 
     tau, print_period, and epsilon0, numInnerItermax, through **kwargs).  warmstart and grad ("plan" / "unrolled"): see the module docstring,
     also for the deviations."""
     m = str(method).lower()
-    _check_grad(grad, m if m in ops.SINKHORN_EXT_METHODS else None)
+    _check_grad(grad, m if m in ot_ops.SINKHORN_EXT_METHODS else None)
     if m == "greenkhorn":                                                  # (the reference hands greenkhorn no **kwargs)
         return greenkhorn(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, log=log, warn=warn, warmstart=warmstart)
     if m == "sinkhorn_stabilized":
         return sinkhorn_stabilized(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, warmstart=warmstart, log=log, warn=warn, **kwargs)
     if m == "sinkhorn_epsilon_scaling":
         return sinkhorn_epsilon_scaling(a, b, M, reg, numItermax=numItermax, stopThr=stopThr, warmstart=warmstart, log=log, warn=warn, **kwargs)
-    if m not in ops.SINKHORN_METHODS:
+    if m not in ot_ops.SINKHORN_METHODS:
         raise ValueError("Unknown method '%s'." % method)
     return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, grad=grad)
 
@@ -194,7 +194,7 @@ def sinkhorn2(a, b, M, reg, method="sinkhorn", numItermax=1000, stopThr=1e-9, ve
     if m == "sinkhorn_stabilized":
         return _solve_ext(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True, tau=kwargs.get("tau", 1e3),
                           print_period=kwargs.get("print_period", 20))
-    if m not in ops.SINKHORN_METHODS:                                      # (the reference's sinkhorn2 knows neither greenkhorn nor epsilon scaling)
+    if m not in ot_ops.SINKHORN_METHODS:                                      # (the reference's sinkhorn2 knows neither greenkhorn nor epsilon scaling)
         raise ValueError("Unknown method '%s'." % method)
     return _solve(a, b, M, reg, m, numItermax, stopThr, log, warn, warmstart, cost=True, grad=grad)
 
@@ -212,7 +212,7 @@ def wasserstein_pairwise_distances(Ys: Sequence[Tensor], ps=None, reg=0.1, metho
     if ps is not None and len(ps) != G:
         raise ValueError("Ys and ps must have one entry per cloud")
     m = str(method).lower()
-    if m not in ops.SINKHORN_METHODS:
+    if m not in ot_ops.SINKHORN_METHODS:
         raise ValueError("Unknown method '%s'." % method)
     if not all(torch.is_tensor(t) and t.is_cuda for t in Ys):
         raise NotImplementedError("wasserstein_pairwise_distances runs on the GPU only: pass CUDA (ROCm) tensors")
@@ -227,10 +227,10 @@ def wasserstein_pairwise_distances(Ys: Sequence[Tensor], ps=None, reg=0.1, metho
     unrolled = grad == "unrolled"
     if len({int(y.shape[0]) for y in Ys}) == 1:
         st = lambda ts: None if ts is None else torch.stack([(t if unrolled else t.detach()).to(torch.float32) for t in ts])
-        cost = ops.sinkhorn_loss(torch.stack(Ms), st(pick(ia)), st(pick(ib)), **kw)
+        cost = ot_ops.sinkhorn_loss(torch.stack(Ms), st(pick(ia)), st(pick(ib)), **kw)
     else:
-        M, a, b, _w, n1, n2, _sizes = ops._sinkhorn_list_stack(Ms, pick(ia), pick(ib), None, None, keep_graph=True, keep_vec_graph=unrolled)
-        cost = ops.sinkhorn_loss(M, a, b, n1=n1, n2=n2, **kw)
+        M, a, b, _w, n1, n2, _sizes = ot_ops._sinkhorn_list_stack(Ms, pick(ia), pick(ib), None, None, keep_graph=True, keep_vec_graph=unrolled)
+        cost = ot_ops.sinkhorn_loss(M, a, b, n1=n1, n2=n2, **kw)
     out[ia, ib] = cost
     out[ib, ia] = cost
     return out

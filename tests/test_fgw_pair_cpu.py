@@ -10,7 +10,7 @@ import torch
 
 from helpers import golden_files
 from conan_fgw_amd import fgw as pfgw
-from conan_fgw_amd import ops
+from conan_fgw_amd import ops, ot_ops
 from oracle import fgw as ofgw
 
 ALL = golden_files("fgw_pair_")
@@ -65,8 +65,9 @@ def no_library(monkeypatch):
     """The refusals below must come before the library is touched: any C call fails the test."""
     def boom(*a, **k):
         raise AssertionError("the library was called")
-    monkeypatch.setattr(ops, "call", boom)
-    monkeypatch.setattr(ops, "lib", boom)
+    for mod in (ops, ot_ops):          # the solver code binds them in ot_ops
+        monkeypatch.setattr(mod, "call", boom)
+        monkeypatch.setattr(mod, "lib", boom)
 
 
 def test_unknown_solver_is_the_references_value_error(no_library):
