@@ -216,6 +216,13 @@ EXT_TABLES = {
         "conan_fgw_bregman_bwd_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
         "conan_fgw_bregman_bwd": (c_int, [_P] * 6 + [c_int, c_int, _D, _D, c_int, c_int, c_int] + [_P] * 13),
     },
+    "conan_fgw_hip_sinkhorn_hists.h": {
+        "conan_sinkhorn_hists_max_hists": (c_int, [c_int, c_int]),
+        "conan_sinkhorn_hists_lds_resident": (c_int, [c_int, c_int, c_int]),
+        "conan_sinkhorn_hists_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+        "conan_sinkhorn_hists_fwd": (c_int, [_P] * 8 + [c_int] * 4 + [c_ll, _D, c_int, _D] + [_P] * 7),
+        "conan_sinkhorn_hists_loss_bwd": (c_int, [_P] * 7 + [c_int] * 4 + [c_ll, _D] + [_P] * 2),
+    },
     "conan_fgw_hip_mixup_grad.h": {
         "conan_fgw_mixup_barycenter_fwd_record": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, ctypes.POINTER(FgwParams), _D, c_int, _D] + [_P] * 9),
         "conan_fgw_mixup_barycenter_bwd_lds_resident": (c_int, [c_int]),

@@ -20,7 +20,7 @@ __all__ = ["PROD_FGW", "FGW_SOLVERS", "SINKHORN_METHODS", "SINKHORN_EXT_METHODS"
            "fgw_barycenter_batched", "fgw_pair_batched", "fgw_pair_list", "fgw_acc_pair_batched", "fgw_mixup_barycenter_batched",
            "fgw_mixup_barycenter_unrolled", "fgw_pair_distance", "fgw_pair_distance_list", "fgw_pair_dist", "fgw_acc_pair_distance",
            "fgw_acc_pair_unrolled", "fgw_pair_unrolled", "fgw_pair_unrolled_list", "fgw_bregman_unrolled", "fgw_bregman_unrolled_list",
-           "sinkhorn_batched", "sinkhorn_list", "sinkhorn_loss", "sinkhorn_unrolled", "sinkhorn_unrolled_list", "sinkhorn_ext_batched",
+           "sinkhorn_batched", "sinkhorn_list", "sinkhorn_loss", "sinkhorn_hists_batched", "sinkhorn_hists_loss", "sinkhorn_unrolled", "sinkhorn_unrolled_list", "sinkhorn_ext_batched",
            "sinkhorn_ext_list", "sinkhorn_ext_loss"]
 
 
@@ -1021,6 +1021,94 @@ def sinkhorn_loss(M: Tensor, a: Optional[Tensor] = None, b: Optional[Tensor] = N
     Mp, a, b, wu, wv, n1, n2, (B, N1, N2, code) = _sinkhorn_prepare(M, a, b, warmstart, n1, n2, method, keep_graph=True)
     out = _SinkhornLossFn.apply(Mp, lambda: _sinkhorn_fwd(Mp.detach(), a, b, wu, wv, n1, n2, B, N1, N2, code, reg, num_iter_max, stop_thr))
     return out if return_plan else out[0]
+
+
+# --------------------------------------------------------------------------- several histograms at once: a 2-D b (sinkhorn_hists.hip)
+def _sinkhorn_hists_prepare(M, a, b, warmstart, n1, n2, nh, keep_graph=False):
+    """The checked, contiguous operands of conan_sinkhorn_hists_fwd -> (M, a, b, wu, wv, n1, n2, nh, (B, N1, N2, H)).  M [B,N1,N2], or [N1,N2]
+    shared by the B problems of b (m_batch_stride = 0); b [B,N2,H]."""
+    if not torch.is_tensor(M) or not M.is_cuda:
+        raise NotImplementedError("the Sinkhorn solve runs on the GPU only: M is a CPU tensor")
+    if M.dim() not in (2, 3):
+        raise ValueError(f"M must be [B,N1,N2] or [N1,N2], not {list(M.shape)}")
+    if not torch.is_tensor(b) or b.dim() != 3:
+        raise ValueError("b must be [B,N2,H]" + (f", not {list(b.shape)}" if torch.is_tensor(b) else ""))
+    N1, N2 = int(M.shape[-2]), int(M.shape[-1])
+    B, H = int(b.shape[0]), int(b.shape[2])
+    M = _operand(M, "Sinkhorn", "M", [(B, N1, N2), (N1, N2)], keep_graph=keep_graph)
+    b = _operand(b, "Sinkhorn", "b", [(B, N2, H)])
+    a = None if a is None else _sinkhorn_vec(a, "a", B, N1)
+    wu, wv = (None, None) if warmstart is None else (_operand(warmstart[0], "Sinkhorn", "warmstart[0]", [(B, N1, H)]),
+                                                     _operand(warmstart[1], "Sinkhorn", "warmstart[1]", [(B, N2, H)]))
+    size = lambda t, name: None if t is None else _operand(t, "Sinkhorn", name, [(B,)], i32)
+    return M, a, b, wu, wv, size(n1, "n1"), size(n2, "n2"), size(nh, "nh"), (B, N1, N2, H)
+
+
+def _sinkhorn_hists_fwd(M, a, b, wu, wv, n1, n2, nh, B, N1, N2, H, reg, num_iter_max, stop_thr):
+    """conan_sinkhorn_hists_fwd on prepared operands -> loss [B,H], log_u [B,N1,H], log_v [B,N2,H], info [B,4], errs.  No host synchronisation."""
+    dev = M.device
+    new = lambda *shape, dtype=f32: torch.empty(*shape, dtype=dtype, device=dev)
+    loss, log_u, log_v, info = new(B, H), new(B, N1, H), new(B, N2, H), new(B, 4, dtype=i32)
+    errs = new(B, (int(num_iter_max) + 9) // 10)
+    ws = torch.empty(max(int(lib().conan_sinkhorn_hists_workspace_bytes(B, N1, N2, H)), 1), dtype=torch.uint8, device=dev)
+    call("conan_sinkhorn_hists_fwd", ptr(M, f32), ptr(a), ptr(b), ptr(wu), ptr(wv), ptr(n1), ptr(n2), ptr(nh), B, N1, N2, H,
+         N1 * N2 if M.dim() == 3 else 0, float(reg), int(num_iter_max), float(stop_thr), ptr(loss), ptr(log_u), ptr(log_v), ptr(info), ptr(errs),
+         ptr(ws), stream_ptr())
+    return loss, log_u, log_v, info, errs
+
+
+def sinkhorn_hists_batched(M: Tensor, a: Optional[Tensor], b: Tensor, *, reg: float, num_iter_max: int = 1000, stop_thr: float = 1e-9,
+                           warmstart=None, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None, nh: Optional[Tensor] = None):
+    """B one-to-many entropic OT problems in one launch (one workgroup per problem): the reference's sinkhorn_knopp with a 2-D b
+    (sinkhorn.py:207-315): per problem one cost matrix, one source histogram and H target histograms, solved JOINTLY: one Frobenius error over
+    all H columns decides the stop, and a numerical error in any column restores the previous u, v of all.  M [B,N1,N2] costs, or [N1,N2] shared
+    by the whole batch; a [B,N1] or None (uniform over the problem's own rows); b [B,N2,H]; warmstart (log_u [B,N1,H], log_v [B,N2,H]) or None;
+    n1 / n2 / nh [B] int32 device tensors: the problems' own sizes inside the containers, or None.
+    -> loss [B,H] (the H transport costs; no plan is formed), log_u [B,N1,H], log_v [B,N2,H], info [B,4] int32 = {niter, flags (bit 0: stopped on
+    err < stop_thr, bit 1: the numerical-errors exit), checks executed, 0}, errs [B, ceil(num_iter_max / 10)] (NaN where not executed).  Outside a
+    problem's own block every output is zero; a problem's bits do not depend on the batch, its position or the container.  (N1, N2, H) whose
+    scaling matrices do not fit the LDS (H > conan_sinkhorn_hists_max_hists(N1, N2)) is refused.  No gradient (sinkhorn_hists_loss is the
+    differentiable form) and no host synchronisation."""
+    M, a, b, wu, wv, n1, n2, nh, (B, N1, N2, H) = _sinkhorn_hists_prepare(M, a, b, warmstart, n1, n2, nh)
+    return _sinkhorn_hists_fwd(M, a, b, wu, wv, n1, n2, nh, B, N1, N2, H, reg, num_iter_max, stop_thr)
+
+
+class _SinkhornHistsLossFn(torch.autograd.Function):
+    """loss [B,H] of sinkhorn_hists_batched as a differentiable value under the fixed-plan convention: u, v are constants of the backward,
+    dM = K o sum_k g_k u_k v_k^T from conan_sinkhorn_hists_loss_bwd (K recomputed, no [H,N1,N2] tensor); an M shared by the batch gets the sum
+    over the problems.  `run()` is _sinkhorn_hists_fwd.  No double backward."""
+    @staticmethod
+    def forward(ctx, M, run, sizes, reg):
+        loss, log_u, log_v, info, errs = run()
+        ctx.save_for_backward(M, log_u, log_v, *(t for t in sizes if t is not None))
+        ctx.have, ctx.reg = [t is not None for t in sizes], reg
+        ctx.mark_non_differentiable(log_u, log_v, info, errs)
+        return loss, log_u, log_v, info, errs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        M, log_u, log_v, *rest = ctx.saved_tensors
+        rest = iter(rest)
+        n1, n2, nh = (next(rest) if h else None for h in ctx.have)
+        B, N1, H = log_u.shape
+        N2 = log_v.shape[1]
+        dM = torch.empty(B, N1, N2, dtype=f32, device=M.device)
+        call("conan_sinkhorn_hists_loss_bwd", ptr(M, f32), ptr(log_u), ptr(log_v), ptr(_c(g.to(f32))), ptr(n1), ptr(n2), ptr(nh), B, N1, N2, H,
+             N1 * N2 if M.dim() == 3 else 0, ctx.reg, ptr(dM), stream_ptr())
+        return (dM.sum(0) if M.dim() == 2 else dM), None, None, None
+
+
+def sinkhorn_hists_loss(M: Tensor, a: Optional[Tensor], b: Tensor, *, reg: float, num_iter_max: int = 1000, stop_thr: float = 1e-9,
+                        warmstart=None, n1: Optional[Tensor] = None, n2: Optional[Tensor] = None, nh: Optional[Tensor] = None,
+                        return_log: bool = False):
+    """The costs of sinkhorn_hists_batched as a loss: the same arguments, the same launch, the same bits -> loss [B,H], which carries the gradient
+    at the RETURNED u, v, held constant, to M: dM = K o sum_k g_k u_k v_k^T (one backward launch; an M shared by the batch gets the sum over the
+    problems); a, b and the warm start get none.  No double backward; no host synchronisation.  return_log: (loss, log_u, log_v, info, errs)."""
+    Mp, a, b, wu, wv, n1, n2, nh, (B, N1, N2, H) = _sinkhorn_hists_prepare(M, a, b, warmstart, n1, n2, nh, keep_graph=True)
+    out = _SinkhornHistsLossFn.apply(Mp, lambda: _sinkhorn_hists_fwd(Mp.detach(), a, b, wu, wv, n1, n2, nh, B, N1, N2, H, reg, num_iter_max, stop_thr),
+                                     (n1, n2, nh), float(reg))
+    return out if return_log else out[0]
 
 
 # --------------------------------------------------------------------------- the reference's unrolled gradient (sinkhorn_grad.hip)

@@ -5,10 +5,20 @@ HIP kernels of csrc/sinkhorn.hip and csrc/sinkhorn_ext.hip (one workgroup per pr
 
 Same return values (`log=True`: the reference's dict with the reference's keys), the same warnings with the reference's texts, the same
 `ValueError` for an unknown method, the same warm starts: (log u, log v) for "sinkhorn_log", "sinkhorn" and "greenkhorn", (alpha, beta) in cost
-units for "sinkhorn_stabilized" and "sinkhorn_epsilon_scaling".  Deviations, each a `NotImplementedError`: a 2-D `b` (several histograms at once)
-is not implemented (the reference's Knopp form stops all histograms jointly, which one workgroup per problem does not reproduce, and its
-stabilized form cannot run there at all: loop over the columns, or stack them through ops.sinkhorn_batched / ops.sinkhorn_ext_batched with a
-shared M); CPU tensors (the solve runs on the GPU only).  `verbose` is ignored.  Epsilon scaling warns ONCE when any of its inner solves ran to
+units for "sinkhorn_stabilized" and "sinkhorn_epsilon_scaling".
+
+Several histograms at once: b [n2,H] (the reference's one-to-many form: one M, one a, H target histograms) returns the H transport costs [H],
+no plan, from `sinkhorn`, `sinkhorn2`, `sinkhorn_knopp` and `sinkhorn_log`.  Method "sinkhorn" solves the columns JOINTLY as the reference
+does (csrc/sinkhorn_hists.hip through ops.sinkhorn_hists_loss: one Frobenius error over all n2 H entries decides the stop, a numerical error
+in any column restores the previous u, v of all; log: {"err", "niter", "u" [n1,H], "v" [n2,H]}; warmstart = (log u [n1,H], log v [n2,H])).
+Method "sinkhorn_log" solves each column on its own, as the reference's loop does: H problems of ONE ops.sinkhorn_loss launch with M shared;
+log: {"log_u", "log_v", "u", "v"} as [n,H]; warmstart = a list of H pairs; "did not converge" is given once if any column ran out, whatever
+`warn` says (the reference does not hand `warn` to its inner calls); H = 1 without a warm start is solved, where the reference crashes.
+grad="plan": the costs carry the fixed-plan gradient to M (Knopp: dM = K o sum_k g_k u_k v_k^T from one backward launch, no [H,n1,n2]
+tensor); grad="unrolled" with a 2-D b raises NotImplementedError.
+
+Deviations, each a `NotImplementedError`: a 2-D `b` with "greenkhorn", "sinkhorn_stabilized" or "sinkhorn_epsilon_scaling" (the reference has
+no such form: its stabilized solver raises TypeError there); CPU tensors (the solve runs on the GPU only).  `verbose` is ignored.  Epsilon scaling warns ONCE when any of its inner solves ran to
 `numInnerItermax` (the reference warns once per such solve, always from the same line, which Python's default filter shows once as well), and
 once, with the last one's iteration, when inner solves left on numerical errors.  Outputs are fp32 (`alpha`, `beta` of the last two methods:
 fp64, since epsilon scaling's potentials carry an offset of ~epsilon0 log n that fp32 resolves to 2e-3 only); the iteration runs in fp64, so iteration
@@ -52,8 +62,7 @@ def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost
     """One problem through ops (B = 1) with the reference's return value and warnings (one host synchronisation, as fgw._pair_solve)."""
     _check_grad(grad)
     if b is not None and torch.is_tensor(b) and b.dim() > 1:
-        raise NotImplementedError("several histograms at once (a 2-D b) are not implemented: solve them one by one, or as a batch with a shared M "
-                                  "through ops.sinkhorn_batched")
+        return _solve_hists(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, grad)
     tensors = [("M", M), ("a", a), ("b", b)] + ([] if warmstart is None else [("warmstart[0]", warmstart[0]), ("warmstart[1]", warmstart[1])])
     for name, t in tensors:
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
@@ -85,14 +94,64 @@ def _solve(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, cost
     return res, log_
 
 
+def _solve_hists(a, b, M, reg, method, numItermax, stopThr, log, warn, warmstart, grad):
+    """The reference's one-to-many form, b [n2,H]: the H transport costs of one M and one a against the H columns of b, with the reference's
+    return value and warnings (one host synchronisation).  "sinkhorn": the joint Knopp solve of ops.sinkhorn_hists_loss (B = 1).
+    "sinkhorn_log": the H columns as H problems of ONE ops.sinkhorn_loss launch with M shared, each with its own stop, as the reference's loop."""
+    if b.dim() != 2:
+        raise ValueError(f"b must be [n2] or [n2,H], not {list(b.shape)}")
+    H = int(b.shape[1])
+    per_column = method == "sinkhorn_log"
+    if warmstart is None:
+        warms = []
+    elif per_column:
+        if len(warmstart) != H or any(w is None for w in warmstart):
+            raise ValueError("warmstart must be a list of one (log u, log v) pair per column of b, or None")
+        warms = [t for w in warmstart for t in w]
+    else:
+        warms = list(warmstart)
+    tensors = [("M", M), ("a", a), ("b", b)] + [("warmstart", t) for t in warms]
+    for name, t in tensors:
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise NotImplementedError(f"several histograms at once (a 2-D b) run on the GPU only: pass CUDA (ROCm) tensors ({name} is not one)")
+    if grad == "unrolled":
+        raise NotImplementedError("grad='unrolled' is not implemented for several histograms at once (a 2-D b): the costs carry the fixed-plan "
+                                  "gradient (grad='plan') only")
+    a = None if a is None or len(a) == 0 else a
+    kw = dict(reg=reg, num_iter_max=numItermax, stop_thr=stopThr)
+    if per_column:
+        warm = None if warmstart is None else (torch.stack([w[0] for w in warmstart]), torch.stack([w[1] for w in warmstart]))
+        cost, _T, log_u, log_v, info, _errs = ot_ops.sinkhorn_loss(M, None if a is None else a.unsqueeze(0).expand(H, -1), b.t(), method=method,
+                                                                   warmstart=warm, return_plan=True, **kw)
+        if not bool((info[:, 1] & 1).all()):                               # (the reference's inner calls are not handed `warn`: they warn by default)
+            warnings.warn(_NOT_CONVERGED)
+        if not log:
+            return cost
+        log_u, log_v = log_u.t(), log_v.t()
+        return cost, {"log_u": log_u, "log_v": log_v, "u": torch.exp(log_u), "v": torch.exp(log_v)}
+    warm = None if warmstart is None else (warmstart[0].unsqueeze(0), warmstart[1].unsqueeze(0))
+    loss, log_u, log_v, info, errs = ot_ops.sinkhorn_hists_loss(M.unsqueeze(0), None if a is None else a.unsqueeze(0), b.unsqueeze(0), warmstart=warm,
+                                                                return_log=True, **kw)
+    niter, flags, nchk, _ = info[0].tolist()
+    if flags & 2:
+        warnings.warn("Warning: numerical errors at iteration %d" % niter)
+    elif not flags & 1 and warn:
+        warnings.warn(_NOT_CONVERGED)
+    if not log:
+        return loss[0]
+    return loss[0], {"err": [errs[0, i] for i in range(nchk)], "niter": niter, "u": torch.exp(log_u[0]), "v": torch.exp(log_v[0])}
+
+
 def sinkhorn_knopp(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, grad="plan", **kwargs):
     """The reference's sinkhorn_knopp (sinkhorn.py:207-315): T [n1,n2]; log=True: (T, {"err", "niter", "u", "v"}).  The numerical-errors exit
-    (a zero K^T u, a NaN or Inf in u or v: the previous u, v are returned, with the reference's warning) is decided on fp64 values."""
+    (a zero K^T u, a NaN or Inf in u or v: the previous u, v are returned, with the reference's warning) is decided on fp64 values.
+    b [n2,H]: the H costs [H] instead of a plan, solved jointly (one error over all columns, one exit); u, v of the log are [n1,H], [n2,H]."""
     return _solve(a, b, M, reg, "sinkhorn", numItermax, stopThr, log, warn, warmstart, grad=grad)
 
 
 def sinkhorn_log(a, b, M, reg, numItermax=1000, stopThr=1e-9, verbose=False, log=False, warn=True, warmstart=None, grad="plan", **kwargs):
-    """The reference's sinkhorn_log (sinkhorn.py:318-450): T [n1,n2]; log=True: (T, {"err", "niter", "log_u", "log_v", "u", "v"})."""
+    """The reference's sinkhorn_log (sinkhorn.py:318-450): T [n1,n2]; log=True: (T, {"err", "niter", "log_u", "log_v", "u", "v"}).
+    b [n2,H]: the H costs [H], every column solved on its own in one launch; log=True: (costs, {"log_u", "log_v", "u", "v"}) as [n,H]."""
     return _solve(a, b, M, reg, "sinkhorn_log", numItermax, stopThr, log, warn, warmstart, grad=grad)
 
 
@@ -188,7 +247,7 @@ def sinkhorn2(a, b, M, reg, method="sinkhorn", numItermax=1000, stopThr=1e-9, ve
               **kwargs):
     """The reference's sinkhorn2 (sinkhorn.py:94-204): the transport cost sum(M * T) of the entropic plan as a 0-d tensor (log=True: with the
     solver's log).  grad="plan": it carries the gradient dM = T at the returned plan, held constant; a and b get none.  grad="unrolled": the
-    reference's gradient through the sweeps to M, a, b and warmstart[0]."""
+    reference's gradient through the sweeps to M, a, b and warmstart[0].  b [n2,H]: the H costs [H] (module docstring), grad="plan" only."""
     m = str(method).lower()
     _check_grad(grad, m if m == "sinkhorn_stabilized" else None)
     if m == "sinkhorn_stabilized":
